@@ -21,8 +21,10 @@ own RCCL communicator (dzo_comm_* behind the C ABI) -- a hard requirement: if th
 be created the run fails (BENCH_DIST_BACKEND=gloo is the explicit CPU-transport rehearsal for a 1-GPU
 box, where two ranks cannot share a device under RCCL).  scaling = "weak".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and
-`cpu_baseline` objects.
+Prints ONE JSON line on rank 0, with a `roofline` object.  A plain
+run only sets up, warms up, times --steps steps, writes --dump-outputs and prints the line; `--full`
+adds what takes runs of its own at N = 1: the two-pass roofline leg, the `cpu_baseline` object, the
+`sustained` stretch and the `secondary` object.
 """
 import argparse
 import json
@@ -264,6 +266,37 @@ def host_cores():
     if n > 64:
         n = int(os.environ.get("BENCH_HOST_CORES", "16"))
     return max(1, n)
+
+
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_SAMPLE = 1 << 20          # vector fields longer than this are written as a fixed sample of their elements
+DUMP_SEED = 7
+DUMP_FIELDS = ("current_point", "current_gradient", "step_direction", "delta_point", "delta_gradient")
+
+
+def dump_sample_index(n):
+    """Sorted, distinct element indices of the --dump-outputs sample: every index when n <= DUMP_SAMPLE, else the distinct
+    floor(u n) of DUMP_SAMPLE PCG32 draws (seed DUMP_SEED) -- the same for every run and every build at this n."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.unique((pcg32_uniform(DUMP_SAMPLE, DUMP_SEED) * n).astype(np.int64))
+
+
+def dump_outputs(opt, out_dir):
+    """What a caller of step!() holds after the last timed step: the optimizer's public vector fields (a fixed sample of
+    their elements when n > DUMP_SAMPLE; `sample_index` names them) and scalars, each as out_dir/<name>.npy in float64.
+    Reads go through the library's copy-out (no pointer hand-out): they leave the optimizer's state as it was."""
+    idx = dump_sample_index(opt.n)
+    arrays = {"sample_index": idx.astype(np.float64)}
+    for name in DUMP_FIELDS:
+        arrays[name] = getattr(opt, name).to_host()[idx].astype(np.float64)
+    for name in ("current_objective_value", "delta_objective_value", "last_step_length", "iteration_count"):
+        arrays[name] = np.array([getattr(opt, name)], np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 # ------------------------------------------------------------------------------ secondary workloads
@@ -882,7 +915,7 @@ def main():
     ap.add_argument("--event-sample", type=int, default=1,
                     help="lbfgs: bracket the roofline kernel's launches with HIP events in every Nth step of the timed region only (a "
                          "bracket costs about 8 us of stream time; measured in round 4, five interleaved runs on one box: 2531 step!()/s with every step "
-                         "bracketed, 2565 with every 4th, i.e. +1.4 %; the default stays every step -- every launch of the timed region is then in the average)")
+                         "bracketed, 2565 with every 4th, i.e. +1.4 %%; the default stays every step -- every launch of the timed region is then in the average)")
     ap.add_argument("--workload", default="lbfgs", choices=["lbfgs", "bfgs_dense", "bfgs_batched", "lbfgs_lse_f32", "adgd", "launch_check"],
                     help="lbfgs = BASELINE configs[2] (the headline; default). The others are the remaining "
                          "BASELINE configs, reported as secondary lines.")
@@ -895,7 +928,16 @@ def main():
     ap.add_argument("--batch", type=int, default=1024, help="bfgs_batched: instances per GPU (config 5 shard)")
     ap.add_argument("--batched-steps", type=int, default=0,
                     help="N > 1: timed synchronous steps of the config-5 `batched` object (default: max(--steps, 100))")
+    ap.add_argument("--full", action="store_true",
+                    help="lbfgs line at N = 1: after the headline also run the two-pass roofline leg, the CPU baseline, the `sustained` "
+                         "stretch and the `secondary` object (--no-two-pass, --no-cpu-baseline, --no-secondary drop parts of it again). "
+                         "Off: set up, warm up, time --steps steps, write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="lbfgs: after the timed steps write the optimizer's public fields as the last timed step left them to "
+                         "DIR/<name>.npy (float64; vectors longer than 2^20 as a fixed sample, DIR/sample_index.npy)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "lbfgs" or args.variant):
+        ap.error("--dump-outputs is for the lbfgs line (no --workload, no --variant)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the driver's own multi-GPU form as a child, before anything here touches the GPU
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -964,6 +1006,8 @@ def main():
     _barrier(world)
     elapsed = time.perf_counter() - t0
     dzo.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(opt, args.dump_outputs)
 
     elapsed = sharding.max_over_ranks(elapsed)
     # N > 1: every rank's own rate and trial count (the replicas start from different points, so their numbers of
@@ -990,9 +1034,9 @@ def main():
     # The two-loop recursion proper ((4k+2) n T per direction): the same workload on the
     # two-pass path -- Gram pass + reduce + finish + combine per step, what callbacks / any other
     # objective run -- measured in this process on a second optimizer created with the single-pass step
-    # switched off.  N = 1 only (a reported roofline leg, not part of `value`).
+    # switched off.  N = 1 and --full only (a reported roofline leg, not part of `value`).
     two_pass = None
-    if world == 1 and opt.single_pass_steps > 0 and not args.no_two_pass and args.mode == "gram":
+    if args.full and world == 1 and opt.single_pass_steps > 0 and not args.no_two_pass and args.mode == "gram":
         two_pass = _two_pass_leg(dzo, n, m, esize, args)
 
     k = opt.history_count
@@ -1092,7 +1136,7 @@ def main():
         out["sharded_per_rank"] = batched.get("per_rank_instance_steps_per_s")
         out["sharded_instances_total"] = batched.get("config", {}).get("instances_total")
         out["rccl_world_size"] = batched.get("config", {}).get("rccl_world_size")
-    if not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N = 1 only
         threads = host_cores()
         cn = args.cpu_n or n
         scale = 1.0 if cn == n else cn / n
@@ -1104,7 +1148,7 @@ def main():
                                          f"(= the host cores this job may use) and {args.cpu_steps_single} more on one core"
                                          + ("" if cn == n else f"; rates scaled by {cn}/{n}")}
         out["cpu_baseline"]["julia"] = julia_host_probe(n)
-    if world == 1 and not args.no_cpu_baseline and not args.no_secondary and not opt.is_stuck:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.no_secondary and not opt.is_stuck:
         # The same optimizer run on: 1000 more step!() calls, timed as a block without any event record.  `value` above is
         # the contract's window (W warm-up steps after the history filled, then K steps); early in this trajectory more
         # first trials are rejected (8 of 50 there against 11 % over 20 000 steps), so the rate of a long run is higher --
@@ -1123,9 +1167,9 @@ def main():
         out["sustained"] = {"steps": done1, "step_calls_per_s": round(done1 / el1, 2), "ms_per_step": round(1e3 * el1 / max(done1, 1), 4),
                             "objective_evals_per_step": round(sus_trials / max(done1, 1), 3), "f_end": opt.current_objective_value,
                             "note": "the same optimizer continued after the timed region (no HIP event records in this stretch); not part of `value`"}
-    if world == 1 and not args.no_cpu_baseline and not args.no_secondary and n == 10_000_000 and m == 20:
-        # the remaining BASELINE configs, measured by whoever runs the default line (the full default line only: the
-        # profiling / A-B commands all pass --no-cpu-baseline and stay as they were)
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.no_secondary and n == 10_000_000 and m == 20:
+        # the remaining BASELINE configs, measured by whoever runs the --full line (the profiling / A-B commands all pass
+        # --no-cpu-baseline and stay as they were)
         opt.close()
         out["secondary"] = secondary_in_line(args, dzo, sharding, info)
         # (the log-sum-exp variants stay out of the default line: config 4's problem is done after two or three steps, tools/lse_steps.py)

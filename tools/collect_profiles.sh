@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
-CMD="python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-kernel-events"
+CMD="python3 bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-kernel-events"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD > $OUT/trace.log 2>&1
 echo "trace done"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o f -- $CMD > $OUT/fetch.log 2>&1
@@ -33,7 +33,7 @@ with open(f'profiles/{tag}_two_pass_kernel_stats.csv', 'w') as f:
         w.writerow(r)
 PY
 bash tools/sq_counters.sh ${TAG} "lbfgs_point_pass_kernel<double, 20, false, 1, false, 0>" > profiles/${TAG}_sq_counters_pass.txt 2>&1 || true
-python3 bench.py > profiles/${TAG}_bench_line.json 2> $OUT/bench.err
+python3 bench.py --full > profiles/${TAG}_bench_line.json 2> $OUT/bench.err
 echo "bench line done"
 for w in bfgs_dense bfgs_batched lbfgs_lse_f32; do python3 bench.py --workload $w > profiles/${TAG}_bench_$w.json 2> $OUT/bench_$w.err; echo "$w done"; done
 python3 bench.py --workload adgd --steps 200 --warmup 10 > profiles/${TAG}_bench_adgd.json 2> $OUT/bench_adgd.err

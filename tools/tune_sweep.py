@@ -17,7 +17,7 @@ if len(sys.argv) > 1:
 for cfg in configs:
     env = dict(os.environ)
     env.update({k: str(v) for k, v in cfg.items()})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--full",
                           "--no-cpu-baseline"], env=env, capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])
