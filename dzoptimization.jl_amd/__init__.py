@@ -32,6 +32,8 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 F32, F64 = 0, 1
 ROSENBROCK2D, ROSENBROCK_CHAIN, QUADRATIC, LSE, QUADRATIC_CHAIN = 0, 1, 2, 3, 4
+PAIRWISE_LJ = 5                 # n = 3N, point = [x | y | z] (src/ExampleFunctions.jl)
+RADIAL_LENNARD_JONES = 0        # lj_energy / lj_first_derivative / lj_second_derivative (:16-72)
 TWOLOOP_CHAIN, TWOLOOP_GRAM = 0, 1
 LINE_SEARCH_BACKTRACKING, LINE_SEARCH_WOLFE = 0, 1
 STEP_NULL, STEP_GRADIENT_DESCENT, STEP_BFGS = 0, 1, 2
@@ -176,6 +178,11 @@ ABI = {
     "dzo_calibrate_read_bandwidth": [_i64, _i32, _P(_dbl)],
     "dzo_selftest_fast_div": [C.c_uint64, _i64, _i32, _P(_i64), _P(_i64), _P(_dbl)],
     "dzo_calibrate_read_bandwidth_of": [_vp, _i64, _i32, _P(_dbl)],
+    "dzo_calibrate_fma_rate": [_i32, _i64, _P(_dbl)],
+    "dzo_pairwise_energy": [_i32, _i64, _i32, _vp, _vp, _vp, _P(_dbl)],
+    "dzo_pairwise_gradient": [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dzo_pairwise_hvp": [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dzo_pairwise_energy_delta": [_i32, _i64, _i32, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _P(_dbl)],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -410,6 +417,44 @@ def box_clamp_(x, lower_bound, upper_bound):
 
 def trial_point_(dst, t, d, x):
     _check(lib().dzo_trial_point(x.size, _dt(x.dtype), dst.ptr, t, d.ptr, x.ptr)); return dst
+
+
+def calibrate_fma_rate(dtype=np.float64, iters=1 << 16):
+    """GFLOP/s (2 per fma) of a register-only loop of independent fma chains on every CU."""
+    _need_init()
+    r = C.c_double()
+    _check(lib().dzo_calibrate_fma_rate(_dt(dtype), int(iters), C.byref(r)))
+    return r.value
+
+
+# ------------------------------------------------------------------------------ pairwise radial N-body functions
+# src/ExampleFunctions.jl with the radial function selected by ``radial`` (the reference passes lj_energy etc.); x, y, z
+# (and the outputs) are DeviceArrays of N elements each, views at any element offset included
+def pairwise_radial_energy(x, y, z, radial=RADIAL_LENNARD_JONES):
+    """``accelerated_pairwise_radial_energy(lj_energy, x, y, z)`` (:152-173)."""
+    r = C.c_double()
+    _check(lib().dzo_pairwise_energy(radial, x.size, _dt(x.dtype), x.ptr, y.ptr, z.ptr, C.byref(r)))
+    return r.value
+
+
+def pairwise_radial_gradient_(gx, gy, gz, x, y, z, radial=RADIAL_LENNARD_JONES):
+    """``accelerated_pairwise_radial_gradient!(gx, gy, gz, lj_first_derivative, x, y, z)`` (:265-294)."""
+    _check(lib().dzo_pairwise_gradient(radial, x.size, _dt(x.dtype), gx.ptr, gy.ptr, gz.ptr, x.ptr, y.ptr, z.ptr))
+    return gx, gy, gz
+
+
+def pairwise_radial_hvp_(px, py, pz, x, y, z, u, v, w, radial=RADIAL_LENNARD_JONES):
+    """``accelerated_pairwise_radial_hvp!(px, py, pz, lj_first_derivative, lj_second_derivative, x, y, z, u, v, w)`` (:427-468)."""
+    _check(lib().dzo_pairwise_hvp(radial, x.size, _dt(x.dtype), px.ptr, py.ptr, pz.ptr, x.ptr, y.ptr, z.ptr, u.ptr, v.ptr, w.ptr))
+    return px, py, pz
+
+
+def pairwise_radial_energy_delta(x, y, z, i, x_new, y_new, z_new, radial=RADIAL_LENNARD_JONES):
+    """``pairwise_radial_energy_delta(lj_energy, x, y, z, i, x_new, y_new, z_new)`` (:477-534); ``i`` is 0-based."""
+    r = C.c_double()
+    _check(lib().dzo_pairwise_energy_delta(radial, x.size, _dt(x.dtype), x.ptr, y.ptr, z.ptr, int(i), float(x_new), float(y_new),
+                                           float(z_new), C.byref(r)))
+    return r.value
 
 
 # ------------------------------------------------------------------------------ profiling

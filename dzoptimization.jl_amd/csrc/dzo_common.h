@@ -61,6 +61,8 @@ struct Context {
     hipStream_t stream = nullptr;       // default stream for handle-less primitives
     double *scratch = nullptr;          // device: partial sums for handle-less reductions
     double *host_scalar = nullptr;      // pinned host: results of blocking reductions
+    double *pair_ws = nullptr;          // device: workspace of the handle-less dzo_pairwise_* entry points (grown on demand)
+    int64_t pair_ws_doubles = 0;
 };
 // One context per HIP device; ctx() is the context of the device the CALLING THREAD last selected
 // with dzo_init (or entered through a DeviceScope), the first initialised device otherwise.

@@ -314,6 +314,7 @@ int32_t dzo_shutdown(void) {
         DeviceScope scope(d);
         (void)hipStreamSynchronize(c.stream);
         (void)hipFree(c.scratch);
+        if (c.pair_ws) (void)hipFree(c.pair_ws);
         (void)hipHostFree(c.host_scalar);
         (void)hipStreamDestroy(c.stream);
         c = Context();

@@ -8,6 +8,7 @@
 #include <limits>
 
 #include "dzo_problems.h"
+#include "dzo_pairwise.h"
 #include "dzo_rosen.h"
 
 namespace dzo {
@@ -1095,6 +1096,12 @@ template <typename T> static int32_t eval_async_t(dzo_problem_s *p, hipStream_t 
         DZO_HIP(hipMemcpyAsync(result_dev, res, sizeof(double), hipMemcpyDeviceToDevice, s));
         break;
     }
+    case DZO_PROBLEM_PAIRWISE_LJ: {                          // point = [x | y | z], N = n / 3 (dzo_pairwise.hip)
+        DZO_TIMED("objective_pairwise_lj", s);
+        const int64_t N = n / 3;
+        DZO_TRY(pairwise_energy_async(s, DZO_RADIAL_LENNARD_JONES, N, p->dtype, x, x + N, x + 2 * N, p->scratch, result_dev));
+        break;
+    }
     default:
         set_error("unknown problem kind %d", p->kind);
         return DZO_ERR_INVALID;
@@ -1141,6 +1148,12 @@ template <typename T> static int32_t grad_async_t(dzo_problem_s *p, hipStream_t 
         hipLaunchKernelGGL(lse_finish_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, mx, p->lambda, res);
         hipLaunchKernelGGL(lse_grad_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, g, x, (const T *)p->c, mx, res + 1,
                            p->lambda);
+        break;
+    }
+    case DZO_PROBLEM_PAIRWISE_LJ: {
+        DZO_TIMED("gradient_pairwise_lj", s);
+        const int64_t N = n / 3;
+        DZO_TRY(pairwise_gradient_async(s, DZO_RADIAL_LENNARD_JONES, N, p->dtype, g, g + N, g + 2 * N, x, x + N, x + 2 * N, p->scratch));
         break;
     }
     default:
@@ -1346,8 +1359,12 @@ int32_t problem_grad_async(dzo_problem_s *p, hipStream_t s, void *g, const void 
 
 static int32_t problem_alloc_workspace(dzo_problem_s *p) {
     const int64_t n = p->n;
-    const int64_t scratch = (p->kind == DZO_PROBLEM_QUADRATIC ? (6 * n > 2 * kMaxPartialBlocks ? 6 * n : 2 * kMaxPartialBlocks)
-                                                              : 2 * kMaxPartialBlocks) + 16;
+    int64_t scratch = (p->kind == DZO_PROBLEM_QUADRATIC ? (6 * n > 2 * kMaxPartialBlocks ? 6 * n : 2 * kMaxPartialBlocks)
+                                                        : 2 * kMaxPartialBlocks) + 16;
+    if (p->kind == DZO_PROBLEM_PAIRWISE_LJ) {                // row partials of a split j range, energy partials
+        const int64_t pw = pairwise_workspace_doubles(n / 3);
+        if (pw + 16 > scratch) scratch = pw + 16;
+    }
     p->scratch_doubles = scratch - 16;
     hipError_t e = hipMalloc((void **)&p->scratch, sizeof(double) * (size_t)scratch);
     if (e != hipSuccess) { p->scratch = nullptr; return hip_fail(e, "hipMalloc(problem scratch)", __FILE__, __LINE__); }
@@ -1399,7 +1416,9 @@ int32_t dzo_problem_create(int32_t kind, int64_t n, int32_t dtype, const void *A
     DZO_TRY(require_init());
     DZO_REQUIRE(out, DZO_ERR_INVALID, "null out");
     DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
-    DZO_REQUIRE(kind >= 0 && kind <= DZO_PROBLEM_QUADRATIC_CHAIN, DZO_ERR_INVALID, "unknown problem kind %d", kind);
+    DZO_REQUIRE(kind >= 0 && kind <= DZO_PROBLEM_PAIRWISE_LJ, DZO_ERR_INVALID, "unknown problem kind %d", kind);
+    DZO_REQUIRE(kind != DZO_PROBLEM_PAIRWISE_LJ || (n >= 3 && n % 3 == 0 && n / 3 <= ((int64_t)1 << 28)), DZO_ERR_INVALID,
+                "the pairwise Lennard-Jones objective needs n = 3 N, the point being [x | y | z] (got n = %lld)", (long long)n);
     DZO_REQUIRE(kind != DZO_PROBLEM_QUADRATIC_CHAIN || lambda > 0, DZO_ERR_INVALID, "the chained quadratic needs lambda > 0 (it is what makes it strictly convex)");
     DZO_REQUIRE(n >= 1, DZO_ERR_INVALID, "n must be >= 1");
     DZO_REQUIRE(kind != DZO_PROBLEM_ROSENBROCK2D || n == 2, DZO_ERR_INVALID, "2-D Rosenbrock needs n == 2");

@@ -25,7 +25,10 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        RosenbrockChain, Rosenbrock2D, DenseQuadratic, LogSumExp, QuadraticChain, BuiltinProblem,
        BatchedBFGSOptimizer, count_active, LineSearchEvaluator, compute_lbfgs_step_direction!,
        update_inverse_hessian!, reset_inverse_hessian!, synchronize,
-       norm2, inv_norm, negate!, scale!, HipBackend, install_state!, ShardComm, all_done, read_field
+       norm2, inv_norm, negate!, scale!, HipBackend, install_state!, ShardComm, all_done, read_field,
+       lj_energy, lj_first_derivative, lj_second_derivative, PairwiseLennardJones,
+       accelerated_pairwise_radial_energy, accelerated_pairwise_radial_gradient!, accelerated_pairwise_radial_hvp!,
+       pairwise_radial_energy_delta
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -208,6 +211,8 @@ LogSumExp(c::HipVector{T}, lambda) where {T} = _problem(3, length(c), T; c=c, la
 # sum 1/2 (x[i+1]-x[i])^2 + lambda/2 (x[i]-1)^2: the large-n convex quadratic (tridiagonal Hessian); like RosenbrockChain it runs on
 # the L-BFGS point pass (DZO_PROBLEM_QUADRATIC_CHAIN)
 QuadraticChain(n::Integer, lambda, ::Type{T}=Float64) where {T} = _problem(4, n, T; lambda=lambda)
+# the pairwise Lennard-Jones objective of src/ExampleFunctions.jl on the point [x | y | z], n = 3N (DZO_PROBLEM_PAIRWISE_LJ)
+PairwiseLennardJones(n_particles::Integer, ::Type{T}=Float64) where {T} = _problem(5, 3 * n_particles, T)
 function (p::BuiltinProblem{T})(x::HipVector{T}) where {T}                           # objective_function(x)
     f = Ref{Cdouble}(0)
     check(ccall((:dzo_problem_eval, libdzo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cdouble}), p.handle, x.ptr, f))
@@ -216,6 +221,60 @@ end
 function gradient!(p::BuiltinProblem{T}, g::HipVector{T}, x::HipVector{T}) where {T}
     check(ccall((:dzo_problem_grad, libdzo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), p.handle, g.ptr, x.ptr))
     return g
+end
+
+################################################################################ pairwise radial functions (src/ExampleFunctions.jl)
+
+@inline _twice(x) = x + x
+@inline _square(x) = x * x
+# The radial functions as host functions, operation by operation what the reference defines (:16-72); on HipVector
+# arguments the accelerated_* methods below dispatch on their TYPES to the device kernels that evaluate the same arithmetic.
+@inline function lj_energy(r2::T) where {T}
+    inv_r2 = inv(r2); inv_r4 = _square(inv_r2); inv_r6 = inv_r4 * inv_r2
+    return T(4) * muladd(inv_r6, inv_r6, -inv_r6)
+end
+@inline function lj_first_derivative(r2::T) where {T}
+    inv_r2 = inv(r2); inv_r4 = _square(inv_r2); inv_r6 = inv_r4 * inv_r2; inv_r8 = _square(inv_r4)
+    return T(-12) * muladd(inv_r8, _twice(inv_r6), -inv_r8)
+end
+@inline function lj_second_derivative(r2::T) where {T}
+    inv_r2 = inv(r2); inv_r4 = _square(inv_r2); inv_r8 = _square(inv_r4); inv_r10 = inv_r8 * inv_r2
+    return T(48) * muladd(T(7) / T(2), _square(inv_r8), -inv_r10)
+end
+const DZO_RADIAL_LENNARD_JONES = Cint(0)
+
+"""`accelerated_pairwise_radial_energy(lj_energy, x, y, z)` on device vectors (src/ExampleFunctions.jl:152-173)."""
+function accelerated_pairwise_radial_energy(::typeof(lj_energy), x::HipVector{T}, y::HipVector{T}, z::HipVector{T}) where {T}
+    e = Ref{Cdouble}(0)
+    check(ccall((:dzo_pairwise_energy, libdzo), Cint, (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cdouble}),
+                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, e))
+    return T(e[])
+end
+"""`accelerated_pairwise_radial_gradient!(gx, gy, gz, lj_first_derivative, x, y, z)` (src/ExampleFunctions.jl:265-294)."""
+function accelerated_pairwise_radial_gradient!(gx::HipVector{T}, gy::HipVector{T}, gz::HipVector{T}, ::typeof(lj_first_derivative),
+                                               x::HipVector{T}, y::HipVector{T}, z::HipVector{T}) where {T}
+    check(ccall((:dzo_pairwise_gradient, libdzo), Cint,
+                (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), gx.ptr, gy.ptr, gz.ptr, x.ptr, y.ptr, z.ptr))
+    return nothing
+end
+"""`accelerated_pairwise_radial_hvp!(px, py, pz, lj_first_derivative, lj_second_derivative, x, y, z, u, v, w)` (:427-468)."""
+function accelerated_pairwise_radial_hvp!(px::HipVector{T}, py::HipVector{T}, pz::HipVector{T}, ::typeof(lj_first_derivative),
+                                          ::typeof(lj_second_derivative), x::HipVector{T}, y::HipVector{T}, z::HipVector{T},
+                                          u::HipVector{T}, v::HipVector{T}, w::HipVector{T}) where {T}
+    check(ccall((:dzo_pairwise_hvp, libdzo), Cint,
+                (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), px.ptr, py.ptr, pz.ptr, x.ptr, y.ptr, z.ptr, u.ptr, v.ptr, w.ptr))
+    return nothing
+end
+"""`pairwise_radial_energy_delta(lj_energy, x, y, z, i, x_new, y_new, z_new)` (:477-534); `i` is 1-based like the reference's."""
+function pairwise_radial_energy_delta(::typeof(lj_energy), x::HipVector{T}, y::HipVector{T}, z::HipVector{T}, i::Integer,
+                                      x_new::Real, y_new::Real, z_new::Real) where {T}
+    d = Ref{Cdouble}(0)
+    check(ccall((:dzo_pairwise_energy_delta, libdzo), Cint,
+                (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cdouble, Ref{Cdouble}),
+                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, i - 1, Float64(x_new), Float64(y_new), Float64(z_new), d))
+    return T(d[])
 end
 
 # decorators of legacy/DZOptimization.jl:219-296, applied on the device

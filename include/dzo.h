@@ -58,6 +58,11 @@ extern "C" {
 #define DZO_PROBLEM_QUADRATIC 2         /* 1/2 x'Ax, dense symmetric A */
 #define DZO_PROBLEM_LSE 3               /* log sum exp(x) + lambda/2 |x-c|^2 */
 #define DZO_PROBLEM_QUADRATIC_CHAIN 4   /* sum 1/2 (x[i+1]-x[i])^2 + lambda/2 (x[i]-1)^2: the large-n convex quadratic (tridiagonal Hessian) */
+#define DZO_PROBLEM_PAIRWISE_LJ 5       /* n = 3N, point = [x(0..N) | y | z]: sum over pairs of lj_energy(r2), src/ExampleFunctions.jl (one
+                                         * replicas[:, :, k] of scripts/MonteCarlo.jl:198) */
+
+/* radial functions of the pairwise objective (the reference is generic over energy_function::F) */
+#define DZO_RADIAL_LENNARD_JONES 0      /* lj_energy / lj_first_derivative / lj_second_derivative, src/ExampleFunctions.jl:16-72 */
 
 /* how compute_lbfgs_step_direction! is executed on the device */
 #define DZO_TWOLOOP_CHAIN 0 /* 2k+1 fused axpy+dot links in the reference's op order */
@@ -129,6 +134,9 @@ int32_t dzo_selftest_fast_div(uint64_t seed, int64_t pairs, int32_t mode, int64_
 int32_t dzo_calibrate_read_bandwidth(int64_t bytes, int32_t repeats, double *gbps);
 /* the same reader over a device buffer of the caller's, whatever it holds */
 int32_t dzo_calibrate_read_bandwidth_of(const void *buf_dev, int64_t bytes, int32_t repeats, double *gbps);
+/* GFLOP/s (2 per fma) of a register-only loop of `iters` x 16 independent fma chains per lane on every CU: the vector-ALU
+ * ceiling the pairwise kernels below are measured against */
+int32_t dzo_calibrate_fma_rate(int32_t dtype, int64_t iters, double *gflops);
 
 /* ---------------------------------------------------------------------------------------
  * device memory (what `similar` / `copy` / `Array(x)` do for a GPU array type A)
@@ -207,6 +215,34 @@ int32_t dzo_problem_grad(dzo_problem_t p, void *g_dev, const void *x_dev);
 double dzo_problem_objective_cb(void *problem, const void *x_dev);
 void dzo_problem_gradient_cb(void *problem, void *g_dev, const void *x_dev);
 int32_t dzo_problem_constraint_cb(void *problem, void *x_dev);
+
+/* ---------------------------------------------------------------------------------------
+ * pairwise radial N-body functions (src/ExampleFunctions.jl): the reference's own GPU kernels.
+ * SoA coordinates x, y, z of n_particles particles, e = the radial function of r2 = |r_i - r_j|^2 selected by `radial`
+ * (DZO_RADIAL_LENNARD_JONES).  Per pair the arithmetic is the reference's, operation by operation; the self term is removed
+ * by a select.  Sums over j run in a fixed order (no floating-point atomics): the same input gives the same bits on every
+ * call.  Blocking.  The pointers need no alignment beyond the element's.  Unknown radial, null pointers, i outside
+ * 0 .. N-1: DZO_ERR_INVALID; a host pointer where the reference asserts get_backend equality: DZO_ERR_ASSERT.
+ * DZO_PROBLEM_PAIRWISE_LJ is the same objective as a problem handle for the optimizers.
+ * ------------------------------------------------------------------------------------- */
+/* E = sum_i 1/2 sum_{j != i} e(r2_ij)      accelerated_pairwise_radial_energy + its kernel, :117-173 */
+int32_t dzo_pairwise_energy(int32_t radial, int64_t n_particles, int32_t dtype,
+                            const void *x_dev, const void *y_dev, const void *z_dev, double *energy);
+/* g_i = 2 sum_{j != i} e'(r2_ij) (r_i - r_j)   accelerated_pairwise_radial_gradient! + its kernel, :224-294 */
+int32_t dzo_pairwise_gradient(int32_t radial, int64_t n_particles, int32_t dtype,
+                              void *gx_dev, void *gy_dev, void *gz_dev,
+                              const void *x_dev, const void *y_dev, const void *z_dev);
+/* p_i = 2 sum_{j != i} [ e' (u_i - u_j) + 2 (overlap e'') (r_i - r_j) ], overlap = (r_i - r_j).(u_i - u_j): the Hessian
+ * applied to (u, v, w)                      accelerated_pairwise_radial_hvp! + its kernel, :367-468 */
+int32_t dzo_pairwise_hvp(int32_t radial, int64_t n_particles, int32_t dtype,
+                         void *px_dev, void *py_dev, void *pz_dev,
+                         const void *x_dev, const void *y_dev, const void *z_dev,
+                         const void *u_dev, const void *v_dev, const void *w_dev);
+/* sum_{j != i} e(r2_new) - sum_{j != i} e(r2_old) for particle i (0-based) moved to (x_new, y_new, z_new): O(N), one
+ * launch                                    pairwise_radial_energy_delta, :477-534 */
+int32_t dzo_pairwise_energy_delta(int32_t radial, int64_t n_particles, int32_t dtype,
+                                  const void *x_dev, const void *y_dev, const void *z_dev,
+                                  int64_t i, double x_new, double y_new, double z_new, double *delta);
 
 /* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
