@@ -183,6 +183,11 @@ ABI = {
     "dzo_pairwise_gradient": [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "dzo_pairwise_hvp": [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dzo_pairwise_energy_delta": [_i32, _i64, _i32, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _P(_dbl)],
+    "dzo_tempering_create": [_i32, _i64, _i64, _i32, _vp, _P(_dbl), _P(_dbl), _dbl, C.c_uint64, _P(_vp)],
+    "dzo_tempering_destroy": [_vp], "dzo_tempering_temper": [_vp, _i64, _vp, _i64], "dzo_tempering_swap": [_vp, _i32],
+    "dzo_tempering_run": [_vp, _i64, _i64, _vp, _i64],
+    "dzo_tempering_analyze": [_vp, _i64, _vp, _i64, _P(_dbl), _P(_dbl), _P(_dbl)], "dzo_tempering_set_record": [_vp, _i64],
+    "dzo_tempering_get_ptr": [_vp, _i32, _P(_vp)], "dzo_tempering_read": [_vp, _i32, _vp], "dzo_tempering_set": [_vp, _i32, _vp],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -458,6 +463,117 @@ def pairwise_radial_energy_delta(x, y, z, i, x_new, y_new, z_new, radial=RADIAL_
 
 
 # ------------------------------------------------------------------------------ profiling
+# ------------------------------------------------------------------------------ parallel tempering (scripts/MonteCarlo.jl)
+TEMPERING_MAX_PARTICLES = 1024
+(TEMPERING_REPLICAS, TEMPERING_RADII, TEMPERING_INV_TEMPS, TEMPERING_NUM_ACCEPT, TEMPERING_NUM_REJECT, TEMPERING_RNG_STATES,
+ TEMPERING_REC_INDEX, TEMPERING_REC_NORMALS, TEMPERING_REC_UNIFORM, TEMPERING_REC_CODE, TEMPERING_REC_SWAP,
+ TEMPERING_REC_SWAP_LOGP) = range(12)
+
+
+class ParallelTempering:
+    """``parallel_temper!`` / ``parallel_swap!`` / ``analyze`` of scripts/MonteCarlo.jl with the loop over the moves on the
+    device.  ``replicas`` is a DeviceArray of ``3 * n_particles * n_replicas`` elements, per replica ``[x | y | z]`` (the
+    reference's ``Array{T,3}(particles, 3, replicas)``); it is aliased and mutated, as the reference mutates its argument.
+    ``inverse_temperatures`` and ``perturbation_radii`` are host sequences.  The random-number rule is in include/dzo.h.
+
+    ``temper``, ``swap`` and ``run`` do not block; every property that reads device state does."""
+
+    def __init__(self, replicas, n_particles, inverse_temperatures, perturbation_radii, constraining_radius, base_seed=0,
+                 radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.replicas = replicas
+        self.dtype = replicas.dtype
+        self.n_particles = int(n_particles)
+        beta = np.ascontiguousarray(inverse_temperatures, dtype=np.float64)
+        rad = np.ascontiguousarray(perturbation_radii, dtype=np.float64)
+        assert beta.ndim == 1 and beta.shape == rad.shape
+        self.n_replicas = int(beta.size)
+        assert replicas.size == 3 * self.n_particles * self.n_replicas, "replicas must hold 3 * n_particles * n_replicas elements"
+        self.constraining_radius = float(constraining_radius)
+        self.record_capacity = 0
+        h = C.c_void_p()
+        _check(lib().dzo_tempering_create(radial, self.n_particles, self.n_replicas, _dt(self.dtype), replicas.ptr,
+                                          beta.ctypes.data_as(_P(_dbl)), rad.ctypes.data_as(_P(_dbl)), self.constraining_radius,
+                                          int(base_seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and _lib is not None:
+                lib().dzo_tempering_destroy(self.h)
+            self.h = None
+        except Exception:
+            pass
+
+    @staticmethod
+    def _trace(energies, ld, rows):
+        if energies is None:
+            return None, 0
+        return energies.ptr, int(ld if ld is not None else (energies.shape[0] if len(energies.shape) == 2 else rows))
+
+    def temper(self, num_steps, energies=None, ld=None):
+        """``parallel_temper!``: ``energies[i + ld * k]`` is the energy of replica k after move i (``ld`` defaults to
+        ``num_steps``)."""
+        p, ld = self._trace(energies, ld, num_steps)
+        _check(lib().dzo_tempering_temper(self.h, int(num_steps), p, ld))
+
+    def swap(self, odd):
+        _check(lib().dzo_tempering_swap(self.h, int(bool(odd))))
+
+    def run(self, num_steps, num_batches, energies=None, ld=None):
+        """The body of ``main``'s loop: per batch temper, swap(false), temper, swap(true); ``energies`` holds
+        ``2 * num_steps * num_batches`` rows per replica."""
+        p, ld = self._trace(energies, ld, 2 * num_steps * num_batches)
+        _check(lib().dzo_tempering_run(self.h, int(num_steps), int(num_batches), p, ld))
+
+    def analyze(self, energies, n_iterations, ld=None):
+        """``analyze``: (cv, cv_prime, moments) with moments[k] = (V1, V2, V3), as float64 arrays holding values of T."""
+        p, ld = self._trace(energies, ld, n_iterations)
+        r = self.n_replicas
+        cv, cvp, mom = np.empty(r), np.empty(r), np.empty((r, 3))
+        _check(lib().dzo_tempering_analyze(self.h, int(n_iterations), p, ld, cv.ctypes.data_as(_P(_dbl)), cvp.ctypes.data_as(_P(_dbl)),
+                                           mom.ctypes.data_as(_P(_dbl))))
+        return cv, cvp, mom
+
+    def set_record(self, capacity_steps):
+        _check(lib().dzo_tempering_set_record(self.h, int(capacity_steps)))
+        self.record_capacity = int(capacity_steps)
+
+    def _shape(self, what):
+        r, cap = self.n_replicas, self.record_capacity
+        return {TEMPERING_REPLICAS: ((r, 3, self.n_particles), self.dtype), TEMPERING_RADII: ((r,), self.dtype),
+                TEMPERING_INV_TEMPS: ((r,), self.dtype), TEMPERING_NUM_ACCEPT: ((r,), np.int64), TEMPERING_NUM_REJECT: ((r,), np.int64),
+                TEMPERING_RNG_STATES: ((r,), np.uint64), TEMPERING_REC_INDEX: ((r, cap), np.int32),
+                TEMPERING_REC_NORMALS: ((r, cap, 3), self.dtype), TEMPERING_REC_UNIFORM: ((r, cap), self.dtype),
+                TEMPERING_REC_CODE: ((r, cap), np.int8), TEMPERING_REC_SWAP: ((r,), np.int8),
+                TEMPERING_REC_SWAP_LOGP: ((r,), self.dtype)}[what]
+
+    def read(self, what):
+        """A blocking host copy of one of the TEMPERING_* arrays; replica-major (row k = replica k)."""
+        shape, dtype = self._shape(what)
+        out = np.empty(shape, dtype=dtype)
+        _check(lib().dzo_tempering_read(self.h, int(what), out.ctypes.data))
+        return out
+
+    def ptr(self, what):
+        p = C.c_void_p()
+        _check(lib().dzo_tempering_get_ptr(self.h, int(what), C.byref(p)))
+        return p.value
+
+    def _set(self, what, values):
+        shape, dtype = self._shape(what)
+        a = np.ascontiguousarray(values, dtype=dtype)
+        assert a.shape == shape
+        _check(lib().dzo_tempering_set(self.h, int(what), a.ctypes.data))
+
+    coordinates = property(lambda self: self.read(TEMPERING_REPLICAS))
+    inverse_temperatures = property(lambda self: self.read(TEMPERING_INV_TEMPS))
+    perturbation_radii = property(lambda self: self.read(TEMPERING_RADII), lambda self, v: self._set(TEMPERING_RADII, v))
+    rng_states = property(lambda self: self.read(TEMPERING_RNG_STATES), lambda self, v: self._set(TEMPERING_RNG_STATES, v))
+    num_accept = property(lambda self: self.read(TEMPERING_NUM_ACCEPT))
+    num_reject = property(lambda self: self.read(TEMPERING_NUM_REJECT))
+
+
 def profile_enable(level=2):
     """0/False off, 1 = the roofline kernels only (cheap), 2/True = every kernel."""
     _check(lib().dzo_profile_enable(2 if level is True else int(level)))

@@ -22,47 +22,7 @@
 
 namespace dzo {
 
-// ------------------------------------------------------------------------------ radial functions (:16-72)
-template <typename T> __device__ __forceinline__ T pw_twice(T a) { return a + a; }
-template <typename T> __device__ __forceinline__ T pw_square(T a) { return a * a; }
-
-template <typename T> struct LJRadial {
-    // lj_energy :16-27
-    static __device__ __forceinline__ T energy(T r2) {
-        const T inv_r2 = T(1) / r2;                          // inv, :22 (IEEE division)
-        const T inv_r4 = pw_square(inv_r2);
-        const T inv_r6 = inv_r4 * inv_r2;
-        return T(4) * dfma<T>(inv_r6, inv_r6, -inv_r6);
-    }
-    // lj_first_derivative :30-47
-    static __device__ __forceinline__ T first(T r2) {
-        const T inv_r2 = T(1) / r2;
-        const T inv_r4 = pw_square(inv_r2);
-        const T inv_r6 = inv_r4 * inv_r2;
-        const T inv_r8 = pw_square(inv_r4);
-        return T(-12) * dfma<T>(inv_r8, pw_twice(inv_r6), -inv_r8);
-    }
-    // lj_second_derivative :50-72
-    static __device__ __forceinline__ T second(T r2) {
-        const T inv_r2 = T(1) / r2;
-        const T inv_r4 = pw_square(inv_r2);
-        const T inv_r8 = pw_square(inv_r4);
-        const T inv_r10 = inv_r8 * inv_r2;
-        return T(48) * dfma<T>(T(3.5), pw_square(inv_r8), -inv_r10);
-    }
-};
-
 enum { kPwEnergy = 0, kPwGradient = 1, kPwHvp = 2 };
-
-// `self ? 0 : e(r2)` as a select of two computed values: the term is evaluated in every lane and then dropped (ifelse, :145),
-// never branched around -- a conditional EXPRESSION is a branch in the source, and the compiler keeps a branch around a
-// division sequence ("skip the expensive operand"): an exec-mask save / restore per pair that is never taken and that keeps
-// the independent chains of the four unrolled pairs from being interleaved.  pw_pin makes the value opaque so that the select
-// is not turned back into that branch late in code generation.
-template <typename T> __device__ __forceinline__ T pw_pin(T v) {
-    asm("" : "+v"(v));
-    return v;
-}
 
 template <typename T> struct PwPoint { T x, y, z, u, v, w; };
 

@@ -28,7 +28,8 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        norm2, inv_norm, negate!, scale!, HipBackend, install_state!, ShardComm, all_done, read_field,
        lj_energy, lj_first_derivative, lj_second_derivative, PairwiseLennardJones,
        accelerated_pairwise_radial_energy, accelerated_pairwise_radial_gradient!, accelerated_pairwise_radial_hvp!,
-       pairwise_radial_energy_delta
+       pairwise_radial_energy_delta,
+       ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -275,6 +276,78 @@ function pairwise_radial_energy_delta(::typeof(lj_energy), x::HipVector{T}, y::H
                 (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cdouble, Ref{Cdouble}),
                 DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, i - 1, Float64(x_new), Float64(y_new), Float64(z_new), d))
     return T(d[])
+end
+
+################################################################################ parallel tempering (scripts/MonteCarlo.jl)
+# NOT EXERCISED IN THE BUILD CONTAINER (no Julia there), like the rest of this file; tests/test_abi.py checks every ccall
+# below against include/dzo.h, and the Python class ParallelTempering binds the same ten entry points and IS tested.
+#
+# The reference's functions take everything per call; what outlives a call here (the device copies of the inverse
+# temperatures and perturbation radii, the random streams of include/dzo.h's rule) lives in the handle.  `replicas` is the
+# reference's Array{T,3}(particles, 3, replicas) as one device vector, aliased and mutated.  Julia's rand / randn streams are
+# not reproduced: a run agrees with the script's in distribution only.
+
+mutable struct ParallelTempering{T}
+    handle::Ptr{Cvoid}
+    replicas::HipVector{T}
+    n_particles::Int
+    n_replicas::Int
+end
+
+"""`ParallelTempering(lj_energy, replicas, n_particles, inverse_temperatures, perturbation_radii, constraining_radius; seed)`:
+the arguments of `parallel_temper!` (scripts/MonteCarlo.jl:8-15)."""
+function ParallelTempering(::typeof(lj_energy), replicas::HipVector{T}, n_particles::Integer, inverse_temperatures::AbstractVector,
+                           perturbation_radii::AbstractVector, constraining_radius::Real; seed::Integer=0) where {T}
+    ensure_init()
+    n_replicas = length(inverse_temperatures)
+    @assert length(perturbation_radii) == n_replicas                       # :33
+    @assert length(replicas) == 3 * n_particles * n_replicas               # :31
+    beta = Vector{Cdouble}(inverse_temperatures); radii = Vector{Cdouble}(perturbation_radii)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_tempering_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, UInt64, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, n_replicas, dtype_code(T), replicas.ptr, beta, radii, Float64(constraining_radius), UInt64(seed), h))
+    pt = ParallelTempering{T}(h[], replicas, n_particles, n_replicas)
+    finalizer(pt) do w
+        w.handle != C_NULL && ccall((:dzo_tempering_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return pt
+end
+
+"""`parallel_temper!(pt, energies, num_steps; ld)` (scripts/MonteCarlo.jl:8-86): `energies[i + ld * k]`, 0-based, is the energy
+of replica k after move i.  Does not block."""
+function parallel_temper!(pt::ParallelTempering{T}, energies::HipVector{T}, num_steps::Integer; ld::Integer=num_steps) where {T}
+    check(ccall((:dzo_tempering_temper, libdzo), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64), pt.handle, num_steps, energies.ptr, ld))
+    return nothing
+end
+
+"""`parallel_swap!(pt, odd)` (scripts/MonteCarlo.jl:89-136).  Does not block."""
+function parallel_swap!(pt::ParallelTempering, odd::Bool)
+    check(ccall((:dzo_tempering_swap, libdzo), Cint, (Ptr{Cvoid}, Cint), pt.handle, odd ? 1 : 0))
+    return nothing
+end
+
+"""`run_batches!(pt, energies, num_steps, num_batches; ld)`: the loop body of `main` (scripts/MonteCarlo.jl:222-231)."""
+function run_batches!(pt::ParallelTempering{T}, energies::HipVector{T}, num_steps::Integer, num_batches::Integer;
+                      ld::Integer=2 * num_steps * num_batches) where {T}
+    check(ccall((:dzo_tempering_run, libdzo), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64), pt.handle, num_steps, num_batches, energies.ptr, ld))
+    return nothing
+end
+
+"""`analyze(pt, energies, n_iterations; ld)` (scripts/MonteCarlo.jl:139-180): `(cv, cv_prime)` as host vectors of T."""
+function analyze(pt::ParallelTempering{T}, energies::HipVector{T}, n_iterations::Integer; ld::Integer=n_iterations) where {T}
+    cv = Vector{Cdouble}(undef, pt.n_replicas); cv_prime = Vector{Cdouble}(undef, pt.n_replicas)
+    check(ccall((:dzo_tempering_analyze, libdzo), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                pt.handle, n_iterations, energies.ptr, ld, cv, cv_prime, C_NULL))
+    return Vector{T}(cv), Vector{T}(cv_prime)
+end
+
+"""The perturbation radii after the adaptation of the last `parallel_temper!` (scripts/MonteCarlo.jl:77-81); blocks."""
+function perturbation_radii(pt::ParallelTempering{T}) where {T}
+    r = Vector{T}(undef, pt.n_replicas)
+    check(ccall((:dzo_tempering_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), pt.handle, 1, r))
+    return r
 end
 
 # decorators of legacy/DZOptimization.jl:219-296, applied on the device

@@ -245,6 +245,89 @@ int32_t dzo_pairwise_energy_delta(int32_t radial, int64_t n_particles, int32_t d
                                   int64_t i, double x_new, double y_new, double z_new, double *delta);
 
 /* ---------------------------------------------------------------------------------------
+ * Parallel-tempering Monte Carlo over replicas of one cluster (scripts/MonteCarlo.jl): the program pairwise_radial_energy_delta
+ * was written for, with the loop over the moves on the device.  One launch runs num_steps Metropolis moves of every replica;
+ * nothing crosses the host between moves.
+ *
+ * Layout.  replicas_dev is the reference's Array{T,3}(particles, 3, replicas) (:198): per replica [x(0..N) | y | z], 3N elements,
+ * replica k at element 3N k -- one point of DZO_PROBLEM_PAIRWISE_LJ, so a replica can be handed to an optimizer.  The handle
+ * ALIASES it (the reference mutates the caller's array).  energies_dev is (iterations, replicas) column-major with leading
+ * dimension ld >= num_steps: energies[i + ld k].  A view of rows of a larger matrix (:223-224) is its first element + the ld
+ * of the larger matrix.
+ *
+ * Launch shapes.  n_particles <= 64: one wave per replica, lane j holds particle j in registers.  65 .. 1024
+ * (DZO_TEMPERING_MAX_PARTICLES): one 256-thread block per replica, coordinates in LDS.  More: DZO_ERR_UNSUPPORTED.
+ *
+ * Random numbers -- THE SPECIFICATION of what a temper / swap call computes.  Replica k owns one PCG32 (XSH-RR) stream, the
+ * generator of legacy/PCG.jl:7-22:   advance(s) = 0x5851F42D4C957F2D s + 0x14057B7EF767814F (mod 2^64),
+ *                                     extract(s) = rotr32(((s >> 18) ^ s) >> 27, s >> 59),
+ * state after create = advance(0x14057B7EF767814F + base_seed + k); a draw is extract(state), then state = advance(state).
+ * The 64-bit states live in device memory between calls (DZO_TEMPERING_RNG_STATES).
+ * A Monte Carlo step consumes exactly SIX draws d0 .. d5, whatever branch it takes:
+ *     j        = (d0 * N) >> 32                                   the particle, 0-based              (:49)
+ *     u_i      = (d_i + 1/2) 2^-32 in fp64, i = 1 .. 4            (exact; never 0 or 1)
+ *     n_x, n_y = sqrt(-2 log u_1) (cos, sin)(2 pi u_2), n_z = sqrt(-2 log u_3) cos(2 pi u_4) in fp64, each rounded to T
+ *                (Box-Muller; the fourth normal is not used)                                          (:53-55)
+ *     u        = d5 2^-32 in fp64 (exact), rounded to T: the acceptance uniform, in [0, 1]            (:63)
+ * A swap decision consumes exactly ONE draw of the LOWER replica's stream (u as above), accepted or not   (:127)
+ * Julia's own rand / randn streams cannot be reproduced and nothing here pretends to: a run is comparable with a Julia run
+ * in distribution only.
+ *
+ * Arithmetic.  Proposal x_old + radius * n_x: a product and a sum, two roundings in T.  Sphere test x^2 + y^2 + z^2 < R^2 in T,
+ * left to right.  Energy difference: per pair the operations of pairwise_radial_energy_delta; the sums over j in a fixed
+ * order (lane sums in T, across lanes in fp64, one rounding back), no floating-point atomics: the same seed gives the same
+ * bits.  Accept when delta <= 0 || u <= exp(-inv_temp * delta) (exp in T).
+ *
+ * Errors follow the pairwise functions: unknown radial, sizes < 1, null pointers DZO_ERR_INVALID; a host pointer where the
+ * reference asserts that the axes / backends agree DZO_ERR_ASSERT.  temper, swap and run do NOT block (they enqueue on the
+ * library's stream of the calling thread's device); read, analyze, dzo_synchronize and dzo_memcpy_* do.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_TEMPERING_MAX_PARTICLES 1024
+/* `what` of get_ptr / read / set: element type and count */
+#define DZO_TEMPERING_REPLICAS 0        /* T, 3 N R: the caller's array */
+#define DZO_TEMPERING_RADII 1           /* T, R: perturbation_radii (:13), adapted by every temper call; settable */
+#define DZO_TEMPERING_INV_TEMPS 2       /* T, R: inverse_temperatures (:12) */
+#define DZO_TEMPERING_NUM_ACCEPT 3      /* int64, R: num_accept of the last temper call (:46) */
+#define DZO_TEMPERING_NUM_REJECT 4      /* int64, R: num_reject of the last temper call (:47) */
+#define DZO_TEMPERING_RNG_STATES 5      /* uint64, R: the PCG32 states; settable (checkpoint / resume) */
+#define DZO_TEMPERING_REC_INDEX 6       /* int32, (capacity, R): particle of step i of replica k at [i + capacity k] */
+#define DZO_TEMPERING_REC_NORMALS 7     /* T, (3, capacity, R): n_x, n_y, n_z at [3 (i + capacity k) + c] */
+#define DZO_TEMPERING_REC_UNIFORM 8     /* T, (capacity, R): the acceptance uniform */
+#define DZO_TEMPERING_REC_CODE 9        /* int8, (capacity, R): 0 rejected by the Metropolis test, 1 accepted, 2 outside the sphere */
+#define DZO_TEMPERING_REC_SWAP 10       /* int8, R: last swap call; slot a of a pair (a, a + 1): 1 exchanged, 0 not; other slots -1 */
+#define DZO_TEMPERING_REC_SWAP_LOGP 11  /* T, R: log_prob of that pair (:126) in slot a; other slots 0 */
+typedef struct dzo_tempering_s *dzo_tempering_t;
+/* The arguments of parallel_temper! that outlive a call (:8-15).  inverse_temperatures and perturbation_radii are HOST arrays
+ * of n_replicas doubles, rounded to T and kept on the device. */
+int32_t dzo_tempering_create(int32_t radial, int64_t n_particles, int64_t n_replicas, int32_t dtype, void *replicas_dev,
+                             const double *inverse_temperatures, const double *perturbation_radii, double constraining_radius,
+                             uint64_t base_seed, dzo_tempering_t *out);
+int32_t dzo_tempering_destroy(dzo_tempering_t h);
+/* parallel_temper!, :8-86: the full energy of every replica, num_steps moves, energies[i, k] after every move, then the
+ * radius adaptation of :77-81 (_fac = ten successive square roots of 2 in T).  energies_dev may be NULL (no trace). */
+int32_t dzo_tempering_temper(dzo_tempering_t h, int64_t num_steps, void *energies_dev, int64_t ld);
+/* parallel_swap!, :89-136: the pairs (a, a + 1), a = 0, 2, ... (odd = 0) or a = 1, 3, ... (odd != 0); both energies recomputed,
+ * log_prob = (E_a - E_b)(beta_a - beta_b), exchanged when log_prob >= 0 || u <= exp(log_prob).  Coordinates move;
+ * temperatures, radii and random streams stay with the slot. */
+int32_t dzo_tempering_swap(dzo_tempering_t h, int32_t odd);
+/* the body of main's loop, :222-231: per batch temper (rows 2 b S ..), swap(false), temper (rows (2 b + 1) S ..), swap(true),
+ * S = num_steps; energies_dev holds 2 S num_batches rows.  Enqueued with no host wait in between. */
+int32_t dzo_tempering_run(dzo_tempering_t h, int64_t num_steps, int64_t num_batches, void *energies_dev, int64_t ld);
+/* analyze, :139-180: per replica the means V1, V2, V3 of E, E^2, E^3 over n_iterations rows (terms and sums in fp64, a fixed
+ * order, one rounding to T), then cv and cv_prime by :173-176 in T.  Results to HOST arrays of doubles: cv[R], cv_prime[R],
+ * moments[3 R] = (V1, V2, V3) per replica (moments may be NULL).  Blocking. */
+int32_t dzo_tempering_analyze(dzo_tempering_t h, int64_t n_iterations, const void *energies_dev, int64_t ld, double *cv,
+                              double *cv_prime, double *moments);
+/* Record the draws and decisions of the temper calls that follow (up to capacity_steps steps per call; longer calls are
+ * DZO_ERR_INVALID while recording) and of the swap calls; 0 switches recording off.  Every call overwrites the record. */
+int32_t dzo_tempering_set_record(dzo_tempering_t h, int64_t capacity_steps);
+/* device address of an array above (no wait) / a blocking copy of it to host memory / host memory copied into it (blocking;
+ * DZO_TEMPERING_RADII and DZO_TEMPERING_RNG_STATES only).  Host arrays are in the array's own element type. */
+int32_t dzo_tempering_get_ptr(dzo_tempering_t h, int32_t what, void **ptr_dev);
+int32_t dzo_tempering_read(dzo_tempering_t h, int32_t what, void *out_host);
+int32_t dzo_tempering_set(dzo_tempering_t h, int32_t what, const void *in_host);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
