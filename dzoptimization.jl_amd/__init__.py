@@ -188,6 +188,10 @@ ABI = {
     "dzo_tempering_run": [_vp, _i64, _i64, _vp, _i64],
     "dzo_tempering_analyze": [_vp, _i64, _vp, _i64, _P(_dbl), _P(_dbl), _P(_dbl)], "dzo_tempering_set_record": [_vp, _i64],
     "dzo_tempering_get_ptr": [_vp, _i32, _P(_vp)], "dzo_tempering_read": [_vp, _i32, _vp], "dzo_tempering_set": [_vp, _i32, _vp],
+    "dzo_lbfgs_batch_create": [_i32, _i64, _i64, _i32, _vp, _dbl, _i32, _P(_vp)], "dzo_lbfgs_batch_destroy": [_vp],
+    "dzo_lbfgs_batch_set_max_halvings": [_vp, _i64], "dzo_lbfgs_batch_step": [_vp, _i32, _P(_i32)],
+    "dzo_lbfgs_batch_count_active": [_vp, _P(_i64)], "dzo_lbfgs_batch_get_ptr": [_vp, _i32, _P(_vp)],
+    "dzo_lbfgs_batch_read": [_vp, _i32, _vp], "dzo_pairwise_batch_energy_gradient": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -572,6 +576,126 @@ class ParallelTempering:
     rng_states = property(lambda self: self.read(TEMPERING_RNG_STATES), lambda self, v: self._set(TEMPERING_RNG_STATES, v))
     num_accept = property(lambda self: self.read(TEMPERING_NUM_ACCEPT))
     num_reject = property(lambda self: self.read(TEMPERING_NUM_REJECT))
+
+    def quench(self, history_length=10, initial_step_length=0.01, steps_per_launch=50, max_steps=2000):
+        """The inherent structures of the replicas: a device-to-device COPY of the replica array is quenched by a
+        ``BatchedLBFGS`` (``steps_per_launch`` calls of ``step!()`` per launch until every instance is stuck, at most
+        ``max_steps`` per instance).  Returns ``(energies, copy, optimizer)``: the minima's energies (host array), the
+        DeviceArray that holds them, and the handle (its ``is_stuck`` tells which instances finished).  The Markov chain's
+        own array is not touched."""
+        minima = self.replicas.copy()
+        opt = BatchedLBFGS(minima, self.n_particles, initial_step_length, history_length)
+        done, taken = opt.count_active() == 0, 0
+        while not done and taken < max_steps:
+            k = min(int(steps_per_launch), int(max_steps) - taken)
+            done = opt.step(k)
+            taken += k
+        return opt.current_objective_values, minima, opt
+
+
+# ------------------------------------------------------------------------------ batched L-BFGS over Lennard-Jones clusters
+LBFGS_BATCH_MAX_PARTICLES = 1024
+LBFGS_BATCH_MAX_HISTORY = 32
+(LBFGS_BATCH_POINTS, LBFGS_BATCH_GRADIENTS, LBFGS_BATCH_DIRECTIONS, LBFGS_BATCH_DELTA_POINTS, LBFGS_BATCH_DELTA_GRADIENTS,
+ LBFGS_BATCH_OBJECTIVES, LBFGS_BATCH_DELTA_OBJECTIVES, LBFGS_BATCH_IS_STUCK, LBFGS_BATCH_ITERATION_COUNTS,
+ LBFGS_BATCH_HISTORY_COUNTS, LBFGS_BATCH_S, LBFGS_BATCH_Y, LBFGS_BATCH_RHO, LBFGS_BATCH_LAST_HALVINGS) = range(14)
+
+
+def pairwise_batch_energy_gradient(points, n_particles, gradients=None, radial=RADIAL_LENNARD_JONES):
+    """Energy (host array, one per instance) of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b
+    ``[x | y | z]`` at ``3 * n_particles * b``) and, into ``gradients`` when given, its gradient: the device routine and the
+    summation order of ``BatchedLBFGS``."""
+    n = int(n_particles)
+    batch = points.size // (3 * n)
+    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    e = DeviceArray(batch, points.dtype)
+    _check(lib().dzo_pairwise_batch_energy_gradient(radial, n, batch, _dt(points.dtype), points.ptr, e.ptr,
+                                                    gradients.ptr if gradients is not None else None))
+    return e.to_host()
+
+
+class BatchedLBFGS:
+    """``LBFGSOptimizer`` (src/DZOptimization.jl:321-509, no constraint) of many small Lennard-Jones clusters at once:
+    ``step(k)`` runs k calls of ``step!()`` of every instance in ONE launch.  ``points`` is a DeviceArray of
+    ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
+    ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
+
+    def __init__(self, points, n_particles, initial_step_length, history_length, radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.points = points
+        self.dtype = points.dtype
+        self.n_particles = int(n_particles)
+        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
+        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        self.history_length = int(history_length)
+        h = C.c_void_p()
+        _check(lib().dzo_lbfgs_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, float(initial_step_length),
+                                            self.history_length, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            lib().dzo_lbfgs_batch_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_max_halvings(self, v):
+        _check(lib().dzo_lbfgs_batch_set_max_halvings(self.h, int(v)))
+
+    def step(self, steps=1, wait=True):
+        """``steps`` calls of ``step!()`` of every instance that is not stuck.  ``wait=True``: blocks and returns whether all
+        instances are stuck; ``wait=False``: enqueues only and returns None."""
+        if not wait:
+            _check(lib().dzo_lbfgs_batch_step(self.h, int(steps), None))
+            return None
+        flag = C.c_int32(0)
+        _check(lib().dzo_lbfgs_batch_step(self.h, int(steps), C.byref(flag)))
+        return bool(flag.value)
+
+    def count_active(self):
+        n = C.c_int64(0)
+        _check(lib().dzo_lbfgs_batch_count_active(self.h, C.byref(n)))
+        return int(n.value)
+
+    def _shape(self, what):
+        b, n3, m = self.batch, 3 * self.n_particles, self.history_length
+        vec, sc = ((b, n3), self.dtype), ((b,), self.dtype)
+        return {LBFGS_BATCH_POINTS: vec, LBFGS_BATCH_GRADIENTS: vec, LBFGS_BATCH_DIRECTIONS: vec, LBFGS_BATCH_DELTA_POINTS: vec,
+                LBFGS_BATCH_DELTA_GRADIENTS: vec, LBFGS_BATCH_OBJECTIVES: sc, LBFGS_BATCH_DELTA_OBJECTIVES: sc,
+                LBFGS_BATCH_IS_STUCK: ((b,), np.int32), LBFGS_BATCH_ITERATION_COUNTS: ((b,), np.int64),
+                LBFGS_BATCH_HISTORY_COUNTS: ((b,), np.int32), LBFGS_BATCH_S: ((b, m, n3), self.dtype),
+                LBFGS_BATCH_Y: ((b, m, n3), self.dtype), LBFGS_BATCH_RHO: ((b, m), np.float64),
+                LBFGS_BATCH_LAST_HALVINGS: ((b,), np.int32)}[what]
+
+    def read(self, what):
+        """A blocking host copy of one of the LBFGS_BATCH_* arrays."""
+        shape, dtype = self._shape(what)
+        out = np.empty(shape, dtype=dtype)
+        _check(lib().dzo_lbfgs_batch_read(self.h, int(what), out.ctypes.data))
+        return out
+
+    def ptr(self, what):
+        p = C.c_void_p()
+        _check(lib().dzo_lbfgs_batch_get_ptr(self.h, int(what), C.byref(p)))
+        return p.value
+
+    current_points = property(lambda self: self.read(LBFGS_BATCH_POINTS))
+    current_gradients = property(lambda self: self.read(LBFGS_BATCH_GRADIENTS))
+    current_objective_values = property(lambda self: self.read(LBFGS_BATCH_OBJECTIVES))
+    step_directions = property(lambda self: self.read(LBFGS_BATCH_DIRECTIONS))
+    delta_points = property(lambda self: self.read(LBFGS_BATCH_DELTA_POINTS))
+    delta_gradients = property(lambda self: self.read(LBFGS_BATCH_DELTA_GRADIENTS))
+    delta_objective_values = property(lambda self: self.read(LBFGS_BATCH_DELTA_OBJECTIVES))
+    is_stuck = property(lambda self: self.read(LBFGS_BATCH_IS_STUCK).astype(bool))
+    iteration_counts = property(lambda self: self.read(LBFGS_BATCH_ITERATION_COUNTS))
+    history_counts = property(lambda self: self.read(LBFGS_BATCH_HISTORY_COUNTS))
+    last_halvings = property(lambda self: self.read(LBFGS_BATCH_LAST_HALVINGS))
+
 
 
 def profile_enable(level=2):

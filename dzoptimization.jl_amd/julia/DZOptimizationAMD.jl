@@ -29,7 +29,8 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        lj_energy, lj_first_derivative, lj_second_derivative, PairwiseLennardJones,
        accelerated_pairwise_radial_energy, accelerated_pairwise_radial_gradient!, accelerated_pairwise_radial_hvp!,
        pairwise_radial_energy_delta,
-       ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii
+       ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
+       BatchedLBFGSOptimizer, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -348,6 +349,113 @@ function perturbation_radii(pt::ParallelTempering{T}) where {T}
     r = Vector{T}(undef, pt.n_replicas)
     check(ccall((:dzo_tempering_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), pt.handle, 1, r))
     return r
+end
+
+################################################################################ batched L-BFGS over Lennard-Jones clusters
+# (not exercised in the build container either; the Python class BatchedLBFGS binds the same entry points and IS tested)
+#
+# The live LBFGSOptimizer (src/DZOptimization.jl:321-509, constraint_function! = nothing) of `batch` clusters of
+# `n_particles` particles at once: `step!(opt, k)` runs k calls of the reference's step!() of every instance in ONE launch.
+# `points` holds instance b as [x | y | z] at 3 n_particles b (the tempering replica layout); it is aliased (:393).
+
+mutable struct BatchedLBFGSOptimizer{T}
+    handle::Ptr{Cvoid}
+    points::HipVector{T}
+    n_particles::Int
+    batch::Int
+    history_length::Int
+end
+
+"""`BatchedLBFGSOptimizer(lj_energy, points, n_particles, initial_step_length, history_length)` (:400-427 per instance)."""
+function BatchedLBFGSOptimizer(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, initial_step_length::Real,
+                               history_length::Integer) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_lbfgs_batch_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cdouble, Cint, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), history_length, h))
+    opt = BatchedLBFGSOptimizer{T}(h[], points, n_particles, batch, history_length)
+    finalizer(opt) do w
+        w.handle != C_NULL && ccall((:dzo_lbfgs_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return opt
+end
+
+"""`step!(opt, steps; wait=true)`: `steps` calls of step!() (:454-509) of every instance that is not stuck, one launch.
+Returns whether every instance is stuck (`wait=true`, blocking) or `nothing` (enqueued only)."""
+function step!(opt::BatchedLBFGSOptimizer, steps::Integer=1; wait::Bool=true)
+    if !wait
+        check(ccall((:dzo_lbfgs_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), opt.handle, steps, C_NULL))
+        return nothing
+    end
+    flag = Ref{Cint}(0)
+    check(ccall((:dzo_lbfgs_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), opt.handle, steps, flag))
+    return flag[] != 0
+end
+
+"""The bound on the halvings of one step (the project's escape from the loop of :121-153; default 4096)."""
+set_max_halvings!(opt::BatchedLBFGSOptimizer, v::Integer) =
+    (check(ccall((:dzo_lbfgs_batch_set_max_halvings, libdzo), Cint, (Ptr{Cvoid}, Int64), opt.handle, v)); opt)
+
+function count_active(opt::BatchedLBFGSOptimizer)
+    n = Ref{Int64}(0)
+    check(ccall((:dzo_lbfgs_batch_count_active, libdzo), Cint, (Ptr{Cvoid}, Ref{Int64}), opt.handle, n))
+    return Int(n[])
+end
+
+"""current_objective_value of every instance (DZO_LBFGS_BATCH_OBJECTIVES); blocks."""
+function objective_values(opt::BatchedLBFGSOptimizer{T}) where {T}
+    r = Vector{T}(undef, opt.batch)
+    check(ccall((:dzo_lbfgs_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, 5, r))
+    return r
+end
+
+"""iteration_count of every instance (DZO_LBFGS_BATCH_ITERATION_COUNTS); blocks."""
+function iteration_counts(opt::BatchedLBFGSOptimizer)
+    r = Vector{Int64}(undef, opt.batch)
+    check(ccall((:dzo_lbfgs_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, 8, r))
+    return r
+end
+
+"""is_stuck of every instance (DZO_LBFGS_BATCH_IS_STUCK); blocks."""
+function stuck_flags(opt::BatchedLBFGSOptimizer)
+    r = Vector{Int32}(undef, opt.batch)
+    check(ccall((:dzo_lbfgs_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, 7, r))
+    return r .!= 0
+end
+
+"""Device address of one of the DZO_LBFGS_BATCH_* arrays of include/dzo.h (no wait)."""
+function array_pointer(opt::BatchedLBFGSOptimizer, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_lbfgs_batch_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), opt.handle, what, p))
+    return p[]
+end
+
+"""`pairwise_batch_energy_gradient!(energies, gradients, points, n_particles)`: energy and gradient of every instance by the
+optimizer's own device routine (the objective_function / gradient_function! of :416-421); blocks."""
+function pairwise_batch_energy_gradient!(energies::HipVector{T}, gradients::HipVector{T}, points::HipVector{T}, n_particles::Integer) where {T}
+    batch = div(length(points), 3 * n_particles)
+    check(ccall((:dzo_pairwise_batch_energy_gradient, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, energies.ptr, gradients.ptr))
+    return energies
+end
+
+"""`quench(lj_energy, points, n_particles; ...)`: run the batched optimizer on `points` (in place) until every instance is
+stuck or `max_steps`; returns the optimizer."""
+function quench(f::typeof(lj_energy), points::HipVector{T}, n_particles::Integer; history_length::Integer=10,
+                initial_step_length::Real=0.01, steps_per_launch::Integer=50, max_steps::Integer=2000) where {T}
+    opt = BatchedLBFGSOptimizer(f, points, n_particles, initial_step_length, history_length)
+    taken = 0
+    done = count_active(opt) == 0
+    while !done && taken < max_steps
+        k = min(steps_per_launch, max_steps - taken)
+        done = step!(opt, k)
+        taken += k
+    end
+    return opt
 end
 
 # decorators of legacy/DZOptimization.jl:219-296, applied on the device

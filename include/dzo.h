@@ -328,6 +328,75 @@ int32_t dzo_tempering_read(dzo_tempering_t h, int32_t what, void *out_host);
 int32_t dzo_tempering_set(dzo_tempering_t h, int32_t what, const void *in_host);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched LBFGSOptimizer over many small Lennard-Jones clusters (src/DZOptimization.jl:321-509 with constraint_function! =
+ * nothing, objective = the pairwise radial energy above): the quench of the replicas that tempering leaves behind.  One
+ * launch runs `steps` calls of step!() (:454-509) of EVERY instance; nothing crosses the host between steps or trials.
+ *
+ * Layout.  points_dev is (3N, batch): instance b at element 3N b, [x(0..N) | y | z] -- the tempering replica layout and one
+ * point of DZO_PROBLEM_PAIRWISE_LJ.  The handle ALIASES it, like the live constructor aliases initial_point (:393): after a
+ * step the caller's array holds the new points.
+ *
+ * Launch shapes.  n_particles <= 64: one wave per instance, lane i holds particle i, vectors in registers, the history in
+ * LDS.  65 .. 1024 (DZO_LBFGS_BATCH_MAX_PARTICLES): one 256-thread block per instance, vectors in LDS; the history in LDS
+ * where (2 history_length + 5) 3N elements fit the 160 KiB, else in device memory.  More: DZO_ERR_UNSUPPORTED.
+ *
+ * Arithmetic, per instance.  Constructor: f0, g0, first direction -initial_step_length g / |g|, is_stuck = iszero(|g0|)
+ * (:381-387).  step!(): the two-loop recursion in its chain form over at most history_length pairs, newest first (:430-451;
+ * rho holds s.y itself); take_backtracking_step! from t = 1 (:107-154): trial = fma(t, direction, old point), stuck when the
+ * trial isequal the old point, accepted on strict decrease, halved otherwise; then delta_point = new - old, delta_gradient =
+ * new - old by subtraction, the pair pushed first.  Energy and gradient of a trial come from one pair loop with the per-pair
+ * operations of dzo_pairwise_* (a pair's value has the same bits); row sums over j = 0 .. N-1 in T, rows added in fp64 in a
+ * fixed tree, one rounding to T; dots in fp64, fixed order, alpha / beta / the scale rounded to T.  The orders depend on N,
+ * history_length and the element type only: an instance computes the same bits alone or anywhere in any batch.  No
+ * floating-point atomics.  Deviation (as dzo_lbfgs_set_max_halvings): after max_halvings rejected trials (default 4096) the
+ * instance is stuck.  A stuck instance does nothing more; on the step that finds it stuck delta_point keeps the copy of the
+ * point made at :118 and delta_gradient is not touched, as in the reference.
+ *
+ * Errors follow the pairwise and tempering entries: unknown radial or dtype, sizes < 1, steps < 0, history_length < 1, null
+ * pointers DZO_ERR_INVALID; n_particles > 1024 or history_length > 32 DZO_ERR_UNSUPPORTED; a host pointer where the reference
+ * asserts backend equality (:363-364) DZO_ERR_ASSERT.  step enqueues on the library's stream and blocks only for all_stuck;
+ * read and count_active block.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_LBFGS_BATCH_MAX_PARTICLES 1024
+#define DZO_LBFGS_BATCH_MAX_HISTORY   32
+/* `what` of get_ptr / read: element type and shape (T = the handle's element type, m = history_length) */
+#define DZO_LBFGS_BATCH_POINTS 0            /* T, 3N batch: the caller's array, current_point (:393) */
+#define DZO_LBFGS_BATCH_GRADIENTS 1         /* T, 3N batch: current_gradient */
+#define DZO_LBFGS_BATCH_DIRECTIONS 2        /* T, 3N batch: step_direction of the last step */
+#define DZO_LBFGS_BATCH_DELTA_POINTS 3      /* T, 3N batch: delta_point */
+#define DZO_LBFGS_BATCH_DELTA_GRADIENTS 4   /* T, 3N batch: delta_gradient */
+#define DZO_LBFGS_BATCH_OBJECTIVES 5        /* T, batch: current_objective_value */
+#define DZO_LBFGS_BATCH_DELTA_OBJECTIVES 6  /* T, batch: delta_objective_value */
+#define DZO_LBFGS_BATCH_IS_STUCK 7          /* int32, batch */
+#define DZO_LBFGS_BATCH_ITERATION_COUNTS 8  /* int64, batch */
+#define DZO_LBFGS_BATCH_HISTORY_COUNTS 9    /* int32, batch: pairs held, <= m */
+#define DZO_LBFGS_BATCH_S 10                /* T, (3N, m, batch): delta_point_history, newest first; pair k of instance b at 3N (k + m b) */
+#define DZO_LBFGS_BATCH_Y 11                /* T, (3N, m, batch): delta_gradient_history, newest first */
+#define DZO_LBFGS_BATCH_RHO 12              /* fp64, (m, batch): rho_history = s.y, newest first */
+#define DZO_LBFGS_BATCH_LAST_HALVINGS 13    /* int32, batch: h of the last accepted step (t = 2^-h); on a stuck step the halvings tried */
+typedef struct dzo_lbfgs_batch_s *dzo_lbfgs_batch_t;
+/* LBFGSOptimizer(nothing, f, g!, initial_point, initial_step_length, history_length) of every instance, :400-427 and :347-397.
+ * points_dev: (3N, batch), instance b at element 3N b, [x | y | z] -- the tempering replica layout; ALIASED like the live
+ * constructor aliases initial_point (:393).  initial_step_length <= 0: DZO_ERR_ASSERT (:380).  Blocking. */
+int32_t dzo_lbfgs_batch_create(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                               double initial_step_length, int32_t history_length, dzo_lbfgs_batch_t *out);
+int32_t dzo_lbfgs_batch_destroy(dzo_lbfgs_batch_t h);
+/* the bound on the halvings of one step (the loop of :121-153 has none); at least 1 */
+int32_t dzo_lbfgs_batch_set_max_halvings(dzo_lbfgs_batch_t h, int64_t max_halvings);
+/* `steps` step!() calls (:454-509) of every instance that is not stuck, one launch; all_stuck may be NULL (then no host wait) */
+int32_t dzo_lbfgs_batch_step(dzo_lbfgs_batch_t h, int32_t steps, int32_t *all_stuck);
+/* instances with is_stuck == false (:456).  Blocking. */
+int32_t dzo_lbfgs_batch_count_active(dzo_lbfgs_batch_t h, int64_t *active);
+/* device address of an array above (no wait) / a blocking copy of it to host memory, in the array's own element type */
+int32_t dzo_lbfgs_batch_get_ptr(dzo_lbfgs_batch_t h, int32_t what, void **ptr_dev);
+int32_t dzo_lbfgs_batch_read(dzo_lbfgs_batch_t h, int32_t what, void *out_host);
+/* objective_function and gradient_function! (:416-421) of every instance: energy (T, batch) and, unless NULL, gradient
+ * (T, 3N batch) of every instance of points_dev, by the SAME device routine and summation order the optimizer uses.
+ * Blocking. */
+int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype,
+                                           const void *points_dev, void *energies_dev, void *gradients_dev);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient

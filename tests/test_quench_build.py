@@ -1,0 +1,112 @@
+"""CPU-side checks of the batched L-BFGS entry points: the library exports them, the Python table binds them, the constants
+match the header, the kernels exist for gfx950 without scratch memory or spills (the method of
+tests/test_tempering_build.py), and the plain-C example compiles and links against the library alone.  No compute here."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+from dzo_loader import dzo
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
+SYMBOLS = ["dzo_lbfgs_batch_create", "dzo_lbfgs_batch_destroy", "dzo_lbfgs_batch_set_max_halvings", "dzo_lbfgs_batch_step",
+           "dzo_lbfgs_batch_count_active", "dzo_lbfgs_batch_get_ptr", "dzo_lbfgs_batch_read", "dzo_pairwise_batch_energy_gradient"]
+WHAT = ["POINTS", "GRADIENTS", "DIRECTIONS", "DELTA_POINTS", "DELTA_GRADIENTS", "OBJECTIVES", "DELTA_OBJECTIVES", "IS_STUCK",
+        "ITERATION_COUNTS", "HISTORY_COUNTS", "S", "Y", "RHO", "LAST_HALVINGS"]
+
+
+def test_library_exports_the_batched_lbfgs_entry_points():
+    lib = ctypes.CDLL(dzo.build())
+    missing = [n for n in SYMBOLS if not hasattr(lib, n)]
+    assert not missing, missing
+    assert [n for n in SYMBOLS if n not in dzo.ABI] == []
+
+
+def test_python_constants_match_the_header():
+    header = open(os.path.join(ROOT, "include", "dzo.h")).read()
+    values = []
+    for name in WHAT + ["MAX_PARTICLES", "MAX_HISTORY"]:
+        m = re.search(r"#define\s+DZO_LBFGS_BATCH_%s\s+(\d+)\b" % name, header)
+        assert m, name
+        assert getattr(dzo, "LBFGS_BATCH_" + name) == int(m.group(1)), name
+        values.append(int(m.group(1)))
+    assert sorted(values[:len(WHAT)]) == list(range(len(WHAT)))
+    assert dzo.LBFGS_BATCH_MAX_PARTICLES == 1024 and dzo.LBFGS_BATCH_MAX_HISTORY == 32
+    assert callable(dzo.BatchedLBFGS) and callable(dzo.pairwise_batch_energy_gradient) and callable(dzo.ParallelTempering.quench)
+    for f in ("step", "count_active", "read", "set_max_halvings"):
+        assert callable(getattr(dzo.BatchedLBFGS, f))
+    for p in ("current_points", "current_gradients", "current_objective_values", "is_stuck", "iteration_counts"):
+        assert isinstance(getattr(dzo.BatchedLBFGS, p), property), p
+
+
+def test_header_cites_the_reference_for_every_entry():
+    header = open(os.path.join(ROOT, "include", "dzo.h")).read()
+    block = header[header.index("Batched LBFGSOptimizer"):]
+    for needle in (":454-509", ":107-154", ":430-451", ":381-387", ":393", "max_halvings", "newest first"):
+        assert needle in block, needle
+
+
+def test_quench_kernels_exist_for_gfx950_without_scratch():
+    """Both launch shapes of the step kernel (the BLOCK shape with the history in LDS and in device memory) and of the
+    evaluation kernel, two element types each: no private segment, no VGPR or SGPR spill."""
+    llvm = "/opt/rocm/lib/llvm/bin"
+    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
+        pytest.skip("no ROCm llvm tools")
+    with tempfile.TemporaryDirectory() as tmp:
+        shutil.copy(dzo.build(), os.path.join(tmp, "lib.so"))
+        subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp, check=True,
+                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        meta = {}
+        for f in os.listdir(tmp):
+            if "gfx950" not in f:
+                continue
+            notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", f], cwd=tmp, check=True,
+                                   capture_output=True, text=True).stdout
+            name = None
+            for line in notes.splitlines():
+                m = re.match(r"\s+\.name:\s+(\S+)", line)
+                if m:
+                    name = m.group(1)
+                m = re.match(r"\s+\.(vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|vgpr_count|sgpr_count):\s+(\d+)", line)
+                if m and name:
+                    meta.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    kernels = sorted(n for n in meta if re.search(r"quench_(wave|block)_(step|eval)_kernel|quench_count_active_kernel", n))
+    assert len(kernels) >= 11, kernels
+    for shape in ("quench_wave_step_kernel", "quench_block_step_kernel", "quench_wave_eval_kernel", "quench_block_eval_kernel"):
+        for t in ("If", "Id"):
+            assert any(shape + t in n for n in kernels), (shape, t, kernels)
+    for t in ("If", "Id"):
+        for hist in ("Lb1E", "Lb0E"):
+            assert any("quench_block_step_kernel" + t in n and hist in n for n in kernels), (t, hist, kernels)
+    for n in kernels:
+        print(n, meta[n])
+        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
+        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
+        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+
+
+def test_source_uses_the_shared_pair_arithmetic():
+    src = open(os.path.join(PKG, "csrc", "dzo_lbfgs_batch.hip")).read()
+    assert '#include "dzo_pairwise.h"' in src and "LJRadial<T>" in src and "pw_pin(" in src
+    assert "atomicAdd(&total" in src and src.count("atomic") <= 4      # the one integer count; no floating-point atomic
+    assert "csrc/dzo_lbfgs_batch.hip" in open(os.path.join(PKG, "Makefile")).read()
+
+
+def test_lj_quench_example_compiles_and_links(tmp_path):
+    dzo.build()
+    exe = str(tmp_path / "lj_quench")
+    cmd = ["gcc", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "lj_quench.c"),
+           "-L" + PKG, "-ldzo_hip", "-Wl,-rpath," + PKG, "-lm", "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run(["nm", "-u", exe], check=True, capture_output=True, text=True).stdout
+    wanted = {l.split()[-1].split("@")[0] for l in out.splitlines() if " dzo_" in l}
+    exported = subprocess.run(["nm", "-D", "--defined-only", os.path.join(PKG, "libdzo_hip.so")], check=True, capture_output=True,
+                              text=True).stdout
+    have = {l.split()[-1] for l in exported.splitlines()}
+    assert {"dzo_lbfgs_batch_create", "dzo_lbfgs_batch_step", "dzo_lbfgs_batch_read", "dzo_tempering_run"} <= wanted and wanted <= have, wanted - have
