@@ -466,7 +466,6 @@ def pairwise_radial_energy_delta(x, y, z, i, x_new, y_new, z_new, radial=RADIAL_
     return r.value
 
 
-# ------------------------------------------------------------------------------ profiling
 # ------------------------------------------------------------------------------ parallel tempering (scripts/MonteCarlo.jl)
 TEMPERING_MAX_PARTICLES = 1024
 (TEMPERING_REPLICAS, TEMPERING_RADII, TEMPERING_INV_TEMPS, TEMPERING_NUM_ACCEPT, TEMPERING_NUM_REJECT, TEMPERING_RNG_STATES,
@@ -474,13 +473,32 @@ TEMPERING_MAX_PARTICLES = 1024
  TEMPERING_REC_SWAP_LOGP) = range(12)
 
 
-class ParallelTempering:
+class _HandleArrays:
+    """``read`` / ``ptr`` of a handle whose device arrays are numbered by a ``what`` constant.  A subclass names the library's
+    two entry points and has ``_shape(what)`` -> (shape, dtype)."""
+    _read_fn = _ptr_fn = None
+
+    def read(self, what):
+        """A blocking host copy of one of the handle's arrays; row k = replica / instance k."""
+        shape, dtype = self._shape(what)
+        out = np.empty(shape, dtype=dtype)
+        _check(getattr(lib(), self._read_fn)(self.h, int(what), out.ctypes.data))
+        return out
+
+    def ptr(self, what):
+        p = C.c_void_p()
+        _check(getattr(lib(), self._ptr_fn)(self.h, int(what), C.byref(p)))
+        return p.value
+
+
+class ParallelTempering(_HandleArrays):
     """``parallel_temper!`` / ``parallel_swap!`` / ``analyze`` of scripts/MonteCarlo.jl with the loop over the moves on the
     device.  ``replicas`` is a DeviceArray of ``3 * n_particles * n_replicas`` elements, per replica ``[x | y | z]`` (the
     reference's ``Array{T,3}(particles, 3, replicas)``); it is aliased and mutated, as the reference mutates its argument.
     ``inverse_temperatures`` and ``perturbation_radii`` are host sequences.  The random-number rule is in include/dzo.h.
 
     ``temper``, ``swap`` and ``run`` do not block; every property that reads device state does."""
+    _read_fn, _ptr_fn = "dzo_tempering_read", "dzo_tempering_get_ptr"
 
     def __init__(self, replicas, n_particles, inverse_temperatures, perturbation_radii, constraining_radius, base_seed=0,
                  radial=RADIAL_LENNARD_JONES):
@@ -552,18 +570,6 @@ class ParallelTempering:
                 TEMPERING_REC_CODE: ((r, cap), np.int8), TEMPERING_REC_SWAP: ((r,), np.int8),
                 TEMPERING_REC_SWAP_LOGP: ((r,), self.dtype)}[what]
 
-    def read(self, what):
-        """A blocking host copy of one of the TEMPERING_* arrays; replica-major (row k = replica k)."""
-        shape, dtype = self._shape(what)
-        out = np.empty(shape, dtype=dtype)
-        _check(lib().dzo_tempering_read(self.h, int(what), out.ctypes.data))
-        return out
-
-    def ptr(self, what):
-        p = C.c_void_p()
-        _check(lib().dzo_tempering_get_ptr(self.h, int(what), C.byref(p)))
-        return p.value
-
     def _set(self, what, values):
         shape, dtype = self._shape(what)
         a = np.ascontiguousarray(values, dtype=dtype)
@@ -614,11 +620,12 @@ def pairwise_batch_energy_gradient(points, n_particles, gradients=None, radial=R
     return e.to_host()
 
 
-class BatchedLBFGS:
+class BatchedLBFGS(_HandleArrays):
     """``LBFGSOptimizer`` (src/DZOptimization.jl:321-509, no constraint) of many small Lennard-Jones clusters at once:
     ``step(k)`` runs k calls of ``step!()`` of every instance in ONE launch.  ``points`` is a DeviceArray of
     ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
     ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
+    _read_fn, _ptr_fn = "dzo_lbfgs_batch_read", "dzo_lbfgs_batch_get_ptr"
 
     def __init__(self, points, n_particles, initial_step_length, history_length, radial=RADIAL_LENNARD_JONES):
         _need_init()
@@ -672,18 +679,6 @@ class BatchedLBFGS:
                 LBFGS_BATCH_Y: ((b, m, n3), self.dtype), LBFGS_BATCH_RHO: ((b, m), np.float64),
                 LBFGS_BATCH_LAST_HALVINGS: ((b,), np.int32)}[what]
 
-    def read(self, what):
-        """A blocking host copy of one of the LBFGS_BATCH_* arrays."""
-        shape, dtype = self._shape(what)
-        out = np.empty(shape, dtype=dtype)
-        _check(lib().dzo_lbfgs_batch_read(self.h, int(what), out.ctypes.data))
-        return out
-
-    def ptr(self, what):
-        p = C.c_void_p()
-        _check(lib().dzo_lbfgs_batch_get_ptr(self.h, int(what), C.byref(p)))
-        return p.value
-
     current_points = property(lambda self: self.read(LBFGS_BATCH_POINTS))
     current_gradients = property(lambda self: self.read(LBFGS_BATCH_GRADIENTS))
     current_objective_values = property(lambda self: self.read(LBFGS_BATCH_OBJECTIVES))
@@ -697,7 +692,7 @@ class BatchedLBFGS:
     last_halvings = property(lambda self: self.read(LBFGS_BATCH_LAST_HALVINGS))
 
 
-
+# ------------------------------------------------------------------------------ profiling
 def profile_enable(level=2):
     """0/False off, 1 = the roofline kernels only (cheap), 2/True = every kernel."""
     _check(lib().dzo_profile_enable(2 if level is True else int(level)))

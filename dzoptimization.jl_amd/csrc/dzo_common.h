@@ -209,6 +209,12 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane) {
     hi = __builtin_amdgcn_readlane(hi, src_lane);
     return __hiloint2double(hi, lo);
 }
+// the value of lane `src_lane` (wave-uniform) in every lane: v_readlane
+template <typename T> __device__ __forceinline__ T lane_read(T v, int src_lane);
+template <> __device__ __forceinline__ double lane_read<double>(double v, int src_lane) { return readlane_f64(v, src_lane); }
+template <> __device__ __forceinline__ float lane_read<float>(float v, int src_lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
+}
 
 // Wave-wide sums of FIVE values with 9 cross-lane exchanges instead of 5 x 6: a transposed
 // ("reduce-scatter") butterfly -- at the first three steps a lane keeps only part of the values

@@ -13,7 +13,7 @@
 //     broadcast), the trial gradient in registers.  The history ring is in LDS where it fits the 160 KiB, else in a
 //     handle-owned global slab.
 //
-// Per pair the arithmetic is dzo_pairwise.hip's (dzo_pairwise.h: same operations, same order, the self term removed by a select);
+// Per pair the arithmetic is dzo_pairwise.hip's: pw_pair of dzo_pairwise.h (the self term removed by a select);
 // energy and gradient of a trial come out of ONE pair loop (they share the reciprocal).  Row sums over j run j = 0 .. N-1 in T,
 // rows are added in fp64 by the fixed trees of dzo_common.h, one rounding back to T; dots accumulate in fp64 in a fixed order
 // that depends on N only.  No floating-point atomic.  The recursion is the chain form of :430-451.
@@ -43,19 +43,6 @@ template <typename T> struct QuenchArgs {
     T *slab;                   // BLOCK shape without room in LDS: 2 m 3N elements per instance
 };
 
-template <typename T> __device__ __forceinline__ T q_lane_read(T v, int src_lane);
-template <> __device__ __forceinline__ double q_lane_read<double>(double v, int src_lane) { return readlane_f64(v, src_lane); }
-template <> __device__ __forceinline__ float q_lane_read<float>(float v, int src_lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
-}
-
-// Addresses used again when the launch ends are kept in VECTOR registers: as kernel arguments they would sit in scalar
-// registers through the whole step loop, and the allocator then spills scalars (the same measure as in dzo_tempering.hip).
-template <typename P> __device__ __forceinline__ P *q_pin_ptr(P *p) {
-    asm("" : "+v"(p));
-    return p;
-}
-
 // a lane's / thread's share of a dot over one particle, in fp64
 template <typename T> __device__ __forceinline__ double q_dot3(T ax, T ay, T az, T bx, T by, T bz) {
     double p = (double)ax * (double)bx;
@@ -63,18 +50,10 @@ template <typename T> __device__ __forceinline__ double q_dot3(T ax, T ay, T az,
     return __builtin_fma((double)az, (double)bz, p);
 }
 
-// one (i, j) term: energy (:137-146) and gradient (:245-257) from the same r2; `drop` = self term or padding
+// one (i, j) term: energy (:137-146) and gradient (:245-257) from the same r2 (dzo_pairwise.h); `drop` = self term or padding
 template <typename T, typename F>
 __device__ __forceinline__ void q_pair(bool drop, T xi, T yi, T zi, T xj, T yj, T zj, T &row, T &ax, T &ay, T &az) {
-    const T dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    const T r2 = pw_square(dx) + pw_square(dy) + pw_square(dz);
-    const T e = pw_pin(F::energy(r2));
-    const T f1 = pw_pin(F::first(r2));
-    row += drop ? T(0) : e;
-    const T f = drop ? T(0) : f1;
-    ax += f * dx;
-    ay += f * dy;
-    az += f * dz;
+    pw_pair<T, F, kPwEnergyGradient>(drop, PwPoint<T>{xi, yi, zi}, PwPoint<T>{xj, yj, zj}, ax, ay, az, &row);
 }
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
@@ -87,7 +66,7 @@ __device__ __forceinline__ void q_wave_eval(int N, int lane, T x, T y, T z, T &E
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int j = j4 + k;
-            q_pair<T, F>(j == lane || j >= N, x, y, z, q_lane_read(x, j), q_lane_read(y, j), q_lane_read(z, j), row, ax, ay, az);
+            q_pair<T, F>(j == lane || j >= N, x, y, z, lane_read(x, j), lane_read(y, j), lane_read(z, j), row, ax, ay, az);
         }
     }
     const bool live = lane < N;
@@ -315,12 +294,12 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
     T *hS, *hY;
     if constexpr (HL) { hS = DG + n3; hY = hS + (size_t)m * n3; }
     else { hS = a.slab + 2 * hbase; hY = hS + (size_t)m * n3; }
-    T *const gx_ = q_pin_ptr(a.x + base), *const gg_ = q_pin_ptr(a.g + base), *const gd_ = q_pin_ptr(a.d + base);
-    T *const gdx_ = q_pin_ptr(a.dx + base), *const gdg_ = q_pin_ptr(a.dg + base);
-    T *const gS_ = q_pin_ptr(a.S + hbase), *const gY_ = q_pin_ptr(a.Y + hbase), *const gf_ = q_pin_ptr(a.f + b), *const gdf_ = q_pin_ptr(a.df + b);
-    double *const grho_ = q_pin_ptr(a.rho + (int64_t)m * b);
-    int32_t *const gstuck_ = q_pin_ptr(a.stuck + b), *const ghc_ = q_pin_ptr(a.hcount + b), *const ghalv_ = q_pin_ptr(a.halv + b);
-    int64_t *const git_ = q_pin_ptr(a.iters + b);
+    T *const gx_ = pw_pin_ptr(a.x + base), *const gg_ = pw_pin_ptr(a.g + base), *const gd_ = pw_pin_ptr(a.d + base);
+    T *const gdx_ = pw_pin_ptr(a.dx + base), *const gdg_ = pw_pin_ptr(a.dg + base);
+    T *const gS_ = pw_pin_ptr(a.S + hbase), *const gY_ = pw_pin_ptr(a.Y + hbase), *const gf_ = pw_pin_ptr(a.f + b), *const gdf_ = pw_pin_ptr(a.df + b);
+    double *const grho_ = pw_pin_ptr(a.rho + (int64_t)m * b);
+    int32_t *const gstuck_ = pw_pin_ptr(a.stuck + b), *const ghc_ = pw_pin_ptr(a.hcount + b), *const ghalv_ = pw_pin_ptr(a.halv + b);
+    int64_t *const git_ = pw_pin_ptr(a.iters + b);
     int hc = *ghc_, halv = *ghalv_, head = 0, par = 0;
     int64_t it = *git_;
     T E = *gf_, dE = *gdf_;
@@ -475,26 +454,10 @@ static void qb_free(dzo_lbfgs_batch_s *h) {
     delete h;
 }
 
-static int32_t qb_alloc(void **p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        set_error("out of device memory for the batched L-BFGS state (%zu bytes)", bytes);
-        return DZO_ERR_NOMEM;
-    }
-    return DZO_OK;
-}
+static int32_t qb_alloc(void **p, size_t bytes) { return device_alloc(p, bytes, "the batched L-BFGS state", true); }
 
 static int32_t qb_check_common(int32_t radial, int64_t N, int64_t batch, int32_t dtype) {
-    DZO_REQUIRE(radial == DZO_RADIAL_LENNARD_JONES, DZO_ERR_INVALID, "unknown radial function %d (DZO_RADIAL_LENNARD_JONES = 0 is the one built in)", radial);
-    DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
-    DZO_REQUIRE(N >= 1, DZO_ERR_INVALID, "n_particles must be at least 1 (got %lld)", (long long)N);
-    DZO_REQUIRE(batch >= 1 && batch <= ((int64_t)1 << 30), DZO_ERR_INVALID, "batch must be in 1 .. 2^30 (got %lld)", (long long)batch);
-    DZO_REQUIRE(N <= kQuenchMaxN, DZO_ERR_UNSUPPORTED, "n_particles = %lld: the batched kernels hold an instance in one block, up to %d particles",
-                (long long)N, kQuenchMaxN);
-    return DZO_OK;
+    return pw_check_args(radial, dtype, N, batch, "batch", kQuenchMaxN, DZO_ERR_UNSUPPORTED, "the batched kernels hold an instance in one block");
 }
 
 template <typename T> static QuenchArgs<T> qb_args(const dzo_lbfgs_batch_s *h, int steps, int init, double step_length) {
@@ -675,10 +638,7 @@ int32_t dzo_lbfgs_batch_read(dzo_lbfgs_batch_t h, int32_t what, void *out_host) 
     void *p = nullptr;
     size_t bytes = 0;
     DZO_TRY(qb_array(h, what, &p, &bytes));
-    hipStream_t s = ctx().stream;
-    DZO_HIP(hipMemcpyAsync(out_host, p, bytes, hipMemcpyDeviceToHost, s));
-    DZO_HIP(hipStreamSynchronize(s));
-    return DZO_OK;
+    return copy_blocking(out_host, p, bytes, hipMemcpyDeviceToHost);
 }
 
 // objective_function and gradient_function! of every instance (:416-421), by the optimizer's own device routine

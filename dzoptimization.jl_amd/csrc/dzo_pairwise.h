@@ -13,7 +13,19 @@ int32_t pairwise_energy_async(hipStream_t s, int32_t radial, int64_t n_particles
 int32_t pairwise_gradient_async(hipStream_t s, int32_t radial, int64_t n_particles, int32_t dtype, void *gx, void *gy, void *gz,
                                 const void *x, const void *y, const void *z, double *ws);
 
-// The device pieces below are shared by dzo_pairwise.hip and dzo_tempering.hip (one definition, the same bits in both).
+// ------------------------------------------------------------------------------ host helpers of the three units
+// hipMalloc (at least 16 bytes) of a piece of `what_for`, cleared when `zero_fill`; DZO_ERR_NOMEM with `what_for` in the message
+int32_t device_alloc(void **p, size_t bytes, const char *what_for, bool zero_fill);
+// The argument checks of every entry point that takes `count` sets of n_particles particles, in this order: radial, dtype,
+// n_particles >= 1, count in 1 .. 2^30 (DZO_ERR_INVALID, `count_name` in the message), n_particles <= max_particles (`over_max`;
+// `holder` says what holds that many).
+int32_t pw_check_args(int32_t radial, int32_t dtype, int64_t n_particles, int64_t count, const char *count_name, int64_t max_particles,
+                      int32_t over_max, const char *holder);
+// `bytes` of a handle's array to or from the host on the current context's stream; returns when they have arrived
+int32_t copy_blocking(void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+
+// The device pieces below are shared by dzo_pairwise.hip, dzo_tempering.hip and dzo_lbfgs_batch.hip (one definition, the same
+// bits in all three).
 // ------------------------------------------------------------------------------ radial functions (:16-72)
 template <typename T> __device__ __forceinline__ T pw_twice(T a) { return a + a; }
 template <typename T> __device__ __forceinline__ T pw_square(T a) { return a * a; }
@@ -52,5 +64,70 @@ template <typename T> struct LJRadial {
 template <typename T> __device__ __forceinline__ T pw_pin(T v) {
     asm("" : "+v"(v));
     return v;
+}
+// The same for an address.  Pointers that a kernel uses again when its loop ends are kept in VECTOR registers: as kernel
+// arguments they would sit in scalar registers through the whole loop next to the scalarised integer arithmetic, and the
+// allocator then spills scalars.
+template <typename P> __device__ __forceinline__ P *pw_pin_ptr(P *p) {
+    asm("" : "+v"(p));
+    return p;
+}
+
+// ------------------------------------------------------------------------------ the pair term
+// what pw_pair adds up: e (into ax), e' (r_i - r_j), the hvp's row, or e (into *row) and e' (r_i - r_j) from one r2
+enum { kPwEnergy = 0, kPwGradient = 1, kPwHvp = 2, kPwEnergyGradient = 3 };
+
+template <typename T> struct PwPoint { T x, y, z, u, v, w; };   // u, v, w: the hvp's direction (zero elsewhere)
+
+// the squared distance, summed in this order everywhere
+template <typename T> __device__ __forceinline__ T pw_r2(T dx, T dy, T dz) {
+    const T r2 = pw_square(dx) + pw_square(dy) + pw_square(dz);
+    return r2;
+}
+
+// e(r2) of the pair (px, py, pz) - (xj, yj, zj), pinned and RETURNED; the caller drops the self term with a select.  Kept apart
+// from pw_pair<T, F, kPwEnergy> on a zero accumulator: that form compiles to other code in the delta and tempering kernels.
+template <typename T, typename F> __device__ __forceinline__ T pw_pair_energy(T px, T py, T pz, T xj, T yj, T zj) {
+    return pw_pin(F::energy(pw_r2(px - xj, py - yj, pz - zj)));
+}
+
+// one (i, j) term of :137-146 / :245-257 / :395-419 added to the accumulators (`row`: kPwEnergyGradient only); `self` = (i == j) or padding
+template <typename T, typename F, int MODE>
+__device__ __forceinline__ void pw_pair(bool self, const PwPoint<T> &pi, const PwPoint<T> &pj, T &ax, T &ay, T &az, T *row = nullptr) {
+    const T dx = pi.x - pj.x;
+    const T dy = pi.y - pj.y;
+    const T dz = pi.z - pj.z;
+    const T r2 = pw_r2(dx, dy, dz);
+    if constexpr (MODE == kPwEnergy) {
+        const T e = pw_pin(F::energy(r2));
+        ax += self ? T(0) : e;
+    } else if constexpr (MODE == kPwGradient) {
+        const T f1 = pw_pin(F::first(r2));
+        const T f = self ? T(0) : f1;
+        ax += f * dx;
+        ay += f * dy;
+        az += f * dz;
+    } else if constexpr (MODE == kPwEnergyGradient) {
+        const T e = pw_pin(F::energy(r2));
+        const T f1 = pw_pin(F::first(r2));
+        *row += self ? T(0) : e;
+        const T f = self ? T(0) : f1;
+        ax += f * dx;
+        ay += f * dy;
+        az += f * dz;
+    } else {
+        const T du = pi.u - pj.u;
+        const T dv = pi.v - pj.v;
+        const T dw = pi.w - pj.w;
+        const T f1 = pw_pin(F::first(r2));
+        const T f = self ? T(0) : f1;
+        const T s2 = pw_pin(F::second(r2));
+        const T s = self ? T(0) : s2;
+        const T overlap = dx * du + dy * dv + dz * dw;
+        const T g = pw_twice(overlap * s);
+        ax += f * du + g * dx;
+        ay += f * dv + g * dy;
+        az += f * dw + g * dz;
+    }
 }
 }  // namespace dzo

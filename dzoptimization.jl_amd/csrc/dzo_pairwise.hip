@@ -22,42 +22,6 @@
 
 namespace dzo {
 
-enum { kPwEnergy = 0, kPwGradient = 1, kPwHvp = 2 };
-
-template <typename T> struct PwPoint { T x, y, z, u, v, w; };
-
-// one (i, j) term of :137-146 / :245-257 / :395-419 added to the accumulators; `self` = (i == j)
-template <typename T, typename F, int MODE>
-__device__ __forceinline__ void pw_pair(bool self, const PwPoint<T> &pi, const PwPoint<T> &pj, T &ax, T &ay, T &az) {
-    const T dx = pi.x - pj.x;
-    const T dy = pi.y - pj.y;
-    const T dz = pi.z - pj.z;
-    const T r2 = pw_square(dx) + pw_square(dy) + pw_square(dz);
-    if constexpr (MODE == kPwEnergy) {
-        const T e = pw_pin(F::energy(r2));
-        ax += self ? T(0) : e;
-    } else if constexpr (MODE == kPwGradient) {
-        const T f1 = pw_pin(F::first(r2));
-        const T f = self ? T(0) : f1;
-        ax += f * dx;
-        ay += f * dy;
-        az += f * dz;
-    } else {
-        const T du = pi.u - pj.u;
-        const T dv = pi.v - pj.v;
-        const T dw = pi.w - pj.w;
-        const T f1 = pw_pin(F::first(r2));
-        const T f = self ? T(0) : f1;
-        const T s2 = pw_pin(F::second(r2));
-        const T s = self ? T(0) : s2;
-        const T overlap = dx * du + dy * dv + dz * dw;
-        const T g = pw_twice(overlap * s);
-        ax += f * du + g * dx;
-        ay += f * dv + g * dy;
-        az += f * dw + g * dz;
-    }
-}
-
 // ------------------------------------------------------------------------------ TILE shape
 // grid (ceil(N / 256), js).  Block (bx, by) owns rows 256 bx ... and the j tiles [tiles by / js, tiles (by + 1) / js).
 // js == 1: the rows' results go straight to o0..o2 (twice(a), :258-260); js > 1: to part[(by * 3 + c) * N + i].
@@ -195,13 +159,9 @@ __global__ __launch_bounds__(kBlock) void pairwise_energy_delta_kernel(int64_t N
     for (int64_t j = threadIdx.x; j < N; j += kBlock) {
         const T xj = x[j], yj = y[j], zj = z[j];
         const bool self = j == i;
-        const T dxo = x_old - xj, dyo = y_old - yj, dzo = z_old - zj;
-        const T r2o = pw_square(dxo) + pw_square(dyo) + pw_square(dzo);
-        const T eo = pw_pin(F::energy(r2o));
+        const T eo = pw_pair_energy<T, F>(x_old, y_old, z_old, xj, yj, zj);
         e_old += self ? T(0) : eo;
-        const T dxn = x_new - xj, dyn = y_new - yj, dzn = z_new - zj;
-        const T r2n = pw_square(dxn) + pw_square(dyn) + pw_square(dzn);
-        const T en = pw_pin(F::energy(r2n));
+        const T en = pw_pair_energy<T, F>(x_new, y_new, z_new, xj, yj, zj);
         e_new += self ? T(0) : en;
     }
     const double in[2] = {(double)e_old, (double)e_new};
@@ -313,28 +273,59 @@ static int32_t pw_rows_t(hipStream_t s, int64_t N, T *o0, T *o1, T *o2, const T 
     return DZO_OK;
 }
 
-static int32_t pw_check_radial(int32_t radial) {
-    DZO_REQUIRE(radial == DZO_RADIAL_LENNARD_JONES, DZO_ERR_INVALID, "unknown radial function %d (DZO_RADIAL_LENNARD_JONES = 0 is the one built in)", radial);
+// ------------------------------------------------------------------------------ host helpers (dzo_pairwise.h)
+int32_t device_alloc(void **p, size_t bytes, const char *what_for, bool zero_fill) {
+    const size_t size = bytes ? bytes : 16;
+    hipError_t e = hipMalloc(p, size);
+    if (e == hipSuccess && zero_fill) e = hipMemset(*p, 0, size);
+    if (e != hipSuccess) {
+        *p = nullptr;
+        (void)hipGetLastError();
+        set_error("out of device memory for %s (%zu bytes)", what_for, bytes);
+        return DZO_ERR_NOMEM;
+    }
     return DZO_OK;
+}
+
+int32_t pw_check_args(int32_t radial, int32_t dtype, int64_t N, int64_t count, const char *count_name, int64_t max_particles, int32_t over_max,
+                      const char *holder) {
+    DZO_REQUIRE(radial == DZO_RADIAL_LENNARD_JONES, DZO_ERR_INVALID, "unknown radial function %d (DZO_RADIAL_LENNARD_JONES = 0 is the one built in)", radial);
+    DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
+    DZO_REQUIRE(N >= 1, DZO_ERR_INVALID, "n_particles must be at least 1 (got %lld)", (long long)N);
+    DZO_REQUIRE(count >= 1 && count <= ((int64_t)1 << 30), DZO_ERR_INVALID, "%s must be in 1 .. 2^30 (got %lld)", count_name, (long long)count);
+    DZO_REQUIRE(N <= max_particles, over_max, "n_particles = %lld: %s, up to %lld particles", (long long)N, holder, (long long)max_particles);
+    return DZO_OK;
+}
+
+int32_t copy_blocking(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+    hipStream_t s = ctx().stream;
+    DZO_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
+    DZO_HIP(hipStreamSynchronize(s));
+    return DZO_OK;
+}
+
+constexpr int64_t kPwMaxParticles = (int64_t)1 << 28;       // tiles and grids stay far inside int / the grid limits
+
+// one set of particles: the entry points below and the launchers the problem kind calls
+static int32_t pw_check_common(int32_t radial, int64_t N, int32_t dtype) {
+    return pw_check_args(radial, dtype, N, 1, "the number of particle sets", kPwMaxParticles, DZO_ERR_INVALID, "the launchers index tiles and grids with int");
 }
 
 int32_t pairwise_energy_async(hipStream_t s, int32_t radial, int64_t N, int32_t dtype, const void *x, const void *y, const void *z,
                               double *ws, double *result_dev) {
-    DZO_TRY(pw_check_radial(radial));
+    DZO_TRY(pw_check_common(radial, N, dtype));
     DZO_DISPATCH(dtype, return (pw_energy_t<T, LJRadial<T>>(s, N, (const T *)x, (const T *)y, (const T *)z, ws, result_dev)));
     return DZO_OK;
 }
 
 int32_t pairwise_gradient_async(hipStream_t s, int32_t radial, int64_t N, int32_t dtype, void *gx, void *gy, void *gz, const void *x,
                                 const void *y, const void *z, double *ws) {
-    DZO_TRY(pw_check_radial(radial));
+    DZO_TRY(pw_check_common(radial, N, dtype));
     DZO_DISPATCH(dtype, return (pw_rows_t<T, LJRadial<T>, kPwGradient>(s, N, (T *)gx, (T *)gy, (T *)gz, (const T *)x, (const T *)y,
                                                                          (const T *)z, (const T *)nullptr, (const T *)nullptr,
                                                                          (const T *)nullptr, ws)));
     return DZO_OK;
 }
-
-constexpr int64_t kPwMaxParticles = (int64_t)1 << 28;       // tiles and grids stay far inside int / the grid limits
 
 // workspace of the handle-less entry points: grown on demand, kept in the device's context, freed by dzo_shutdown
 static int32_t pw_ctx_workspace(int64_t N, double **ws) {
@@ -342,18 +333,10 @@ static int32_t pw_ctx_workspace(int64_t N, double **ws) {
     const int64_t need = pairwise_workspace_doubles(N);
     if (c.pair_ws_doubles < need) {
         if (c.pair_ws) { DZO_HIP(hipStreamSynchronize(c.stream)); (void)hipFree(c.pair_ws); c.pair_ws = nullptr; c.pair_ws_doubles = 0; }
-        hipError_t e = hipMalloc((void **)&c.pair_ws, sizeof(double) * (size_t)need);
-        if (e != hipSuccess) { c.pair_ws = nullptr; (void)hipGetLastError(); set_error("out of device memory for the pairwise workspace (%lld doubles)", (long long)need); return DZO_ERR_NOMEM; }
+        DZO_TRY(device_alloc((void **)&c.pair_ws, sizeof(double) * (size_t)need, "the pairwise workspace", false));
         c.pair_ws_doubles = need;
     }
     *ws = c.pair_ws;
-    return DZO_OK;
-}
-
-static int32_t pw_check_common(int32_t radial, int64_t N, int32_t dtype) {
-    DZO_TRY(pw_check_radial(radial));
-    DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
-    DZO_REQUIRE(N >= 1 && N <= kPwMaxParticles, DZO_ERR_INVALID, "n_particles must be in 1 .. 2^28 (got %lld)", (long long)N);
     return DZO_OK;
 }
 
@@ -378,8 +361,7 @@ int32_t dzo_pairwise_energy(int32_t radial, int64_t n_particles, int32_t dtype, 
         DZO_TIMED("pairwise_energy", c.stream);
         DZO_TRY(pairwise_energy_async(c.stream, radial, n_particles, dtype, x_dev, y_dev, z_dev, ws, c.scratch));
     }
-    DZO_HIP(hipMemcpyAsync(c.host_scalar, c.scratch, sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    DZO_HIP(hipStreamSynchronize(c.stream));
+    DZO_TRY(copy_blocking(c.host_scalar, c.scratch, sizeof(double), hipMemcpyDeviceToHost));
     *energy = c.host_scalar[0];
     return DZO_OK;
 }
@@ -452,8 +434,7 @@ int32_t dzo_pairwise_energy_delta(int32_t radial, int64_t n_particles, int32_t d
                                                (const T *)x_dev, (const T *)y_dev, (const T *)z_dev, i, (T)x_new, (T)y_new, (T)z_new, c.scratch));
         DZO_HIP(hipGetLastError());
     }
-    DZO_HIP(hipMemcpyAsync(c.host_scalar, c.scratch, sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    DZO_HIP(hipStreamSynchronize(c.stream));
+    DZO_TRY(copy_blocking(c.host_scalar, c.scratch, sizeof(double), hipMemcpyDeviceToHost));
     *delta = c.host_scalar[0];
     return DZO_OK;
 }

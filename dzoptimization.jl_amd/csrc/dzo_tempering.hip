@@ -12,7 +12,7 @@
 //   * BLOCK shape (N <= 1024): one 256-thread block per replica, coordinates in LDS (every lane reads the same address in
 //     the pair loops: a broadcast), thread t takes j = t, t + 256, ...; two barriers per move (sums, coordinate update).
 //
-// The per-pair arithmetic is pairwise_energy_delta_kernel's (same operations, same order, the self term removed by a select);
+// The per-pair arithmetic is pairwise_energy_delta_kernel's: both call pw_pair_energy of dzo_pairwise.h (the self term removed by a select);
 // lane sums are in T, sums across lanes / waves in fp64 in a fixed order, one rounding back to T.  No floating-point atomic.
 // The random-number rule is stated in include/dzo.h; it is the specification and tests/tempering_twin.py replays it.
 #include "dzo_pairwise.h"
@@ -62,12 +62,6 @@ template <typename T> __device__ __forceinline__ McDraws<T> mc_draw(uint64_t &s,
     return d;
 }
 
-template <typename T> __device__ __forceinline__ T lane_read(T v, int src_lane);
-template <> __device__ __forceinline__ double lane_read<double>(double v, int src_lane) { return readlane_f64(v, src_lane); }
-template <> __device__ __forceinline__ float lane_read<float>(float v, int src_lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
-}
-
 template <typename T> struct TemperArgs {
     int N;
     int64_t num_steps;
@@ -85,26 +79,20 @@ template <typename T> struct TemperArgs {
     int8_t *rec_code;
 };
 
-// Where lane / thread 0 of replica k stores after every step (:75).  The addresses are kept in VECTOR registers (mc_pin_ptr):
-// as kernel arguments they would sit in scalar registers for the whole loop next to the scalarised random-number arithmetic,
-// and the allocator then spills scalars.
-template <typename P> __device__ __forceinline__ P *mc_pin_ptr(P *p) {
-    asm("" : "+v"(p));
-    return p;
-}
+// Where lane / thread 0 of replica k stores after every step (:75); the addresses are pinned to vector registers (pw_pin_ptr).
 template <typename T> struct McOut {
     T *energies;            // null: no trace
     int32_t *rec_index;     // null: no record
     T *rec_normals, *rec_uniform;
     int8_t *rec_code;
     __device__ __forceinline__ McOut(const TemperArgs<T> &a, int64_t k) {
-        energies = mc_pin_ptr(a.energies ? a.energies + a.ld * k : nullptr);
+        energies = pw_pin_ptr(a.energies ? a.energies + a.ld * k : nullptr);
         const bool rec = a.rec_cap > 0;
         const int64_t r = a.rec_cap * k;
-        rec_index = mc_pin_ptr(rec ? a.rec_index + r : nullptr);
-        rec_normals = mc_pin_ptr(rec ? a.rec_normals + 3 * r : nullptr);
-        rec_uniform = mc_pin_ptr(rec ? a.rec_uniform + r : nullptr);
-        rec_code = mc_pin_ptr(rec ? a.rec_code + r : nullptr);
+        rec_index = pw_pin_ptr(rec ? a.rec_index + r : nullptr);
+        rec_normals = pw_pin_ptr(rec ? a.rec_normals + 3 * r : nullptr);
+        rec_uniform = pw_pin_ptr(rec ? a.rec_uniform + r : nullptr);
+        rec_code = pw_pin_ptr(rec ? a.rec_code + r : nullptr);
     }
     __device__ __forceinline__ void step(int64_t i, T energy, const McDraws<T> &d, int code) const {
         if (energies) energies[i] = energy;
@@ -125,10 +113,10 @@ template <typename T> struct McEnd {
     int64_t *acc_out, *rej_out;
     T fac;
     __device__ __forceinline__ McEnd(const TemperArgs<T> &a, int64_t k) {
-        radius_out = mc_pin_ptr(a.radii + k);
-        rng_out = mc_pin_ptr(a.rng + k);
-        acc_out = mc_pin_ptr(a.num_accept + k);
-        rej_out = mc_pin_ptr(a.num_reject + k);
+        radius_out = pw_pin_ptr(a.radii + k);
+        rng_out = pw_pin_ptr(a.rng + k);
+        acc_out = pw_pin_ptr(a.num_accept + k);
+        rej_out = pw_pin_ptr(a.num_reject + k);
         fac = pw_pin(a.fac);
     }
     __device__ __forceinline__ void store(T radius, int64_t acc, int64_t rej, uint64_t s) const {
@@ -142,13 +130,6 @@ template <typename T> struct McEnd {
     }
 };
 
-// one pair of the energy difference: particle (px, py, pz) against (xj, yj, zj), the arithmetic of pairwise_energy_delta_kernel
-template <typename T, typename F> __device__ __forceinline__ T mc_pair(T px, T py, T pz, T xj, T yj, T zj) {
-    const T dx = px - xj, dy = py - yj, dz = pz - zj;
-    const T r2 = pw_square(dx) + pw_square(dy) + pw_square(dz);
-    return pw_pin(F::energy(r2));
-}
-
 // ------------------------------------------------------------------------------ WAVE shape: grid R, block 64
 template <typename T, typename F> __global__ __launch_bounds__(64) void temper_wave_kernel(TemperArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
@@ -159,7 +140,7 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void temper_w
     // the full energy, :39-43: lane i adds row i over j in T, the rows are added in fp64, halved once
     T row = T(0);
     for (int j = 0; j < N; ++j) {
-        const T e = mc_pair<T, F>(x, y, z, lane_read(x, j), lane_read(y, j), lane_read(z, j));
+        const T e = pw_pair_energy<T, F>(x, y, z, lane_read(x, j), lane_read(y, j), lane_read(z, j));
         row += j == lane ? T(0) : e;
     }
     T energy = (T)(0.5 * wave_sum_all(live ? (double)row : 0.0));
@@ -177,7 +158,7 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void temper_w
         int code = 2;
         if (pw_square(xn) + pw_square(yn) + pw_square(zn) < R2) {
             const bool drop = lane == j || !live;
-            const T eo = mc_pair<T, F>(xo, yo, zo, x, y, z), en = mc_pair<T, F>(xn, yn, zn, x, y, z);
+            const T eo = pw_pair_energy<T, F>(xo, yo, zo, x, y, z), en = pw_pair_energy<T, F>(xn, yn, zn, x, y, z);
             const double so = wave_sum_all(drop ? 0.0 : (double)eo), sn = wave_sum_all(drop ? 0.0 : (double)en);
             const T delta = (T)sn - (T)so;
             const bool accept = delta <= T(0) || d.u <= mc_exp<T>(-beta * delta);
@@ -214,7 +195,7 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
     __shared__ double red[2 * kWaves];
     const int tid = threadIdx.x, N = a.N;
     const int64_t k = blockIdx.x;
-    T *rep = mc_pin_ptr(a.replicas + (int64_t)3 * N * k);
+    T *rep = pw_pin_ptr(a.replicas + (int64_t)3 * N * k);
     for (int j = tid; j < N; j += kBlock) { cx[j] = rep[j]; cy[j] = rep[N + j]; cz[j] = rep[2 * N + j]; }
     __syncthreads();
     double rows = 0, unused = 0;
@@ -222,7 +203,7 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
         const T xi = cx[i], yi = cy[i], zi = cz[i];
         T row = T(0);
         for (int j = 0; j < N; ++j) {
-            const T e = mc_pair<T, F>(xi, yi, zi, cx[j], cy[j], cz[j]);
+            const T e = pw_pair_energy<T, F>(xi, yi, zi, cx[j], cy[j], cz[j]);
             row += j == i ? T(0) : e;
         }
         rows += (double)row;
@@ -231,7 +212,7 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
     __syncthreads();
     T energy = (T)(0.5 * rows);
     uint64_t s = a.rng[k];
-    // (loop invariants pinned to vector registers: see mc_pin_ptr)
+    // (loop invariants pinned to vector registers: see pw_pin_ptr)
     const T beta = pw_pin(a.inv_temps[k]), radius = pw_pin(a.radii[k]);
     const T R2 = pw_pin(pw_square(a.constraining_radius));
     const McOut<T> out(a, k);
@@ -249,7 +230,7 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
         if (inside) {
             for (int jj = tid; jj < N; jj += kBlock) {
                 const T xj = cx[jj], yj = cy[jj], zj = cz[jj];
-                const T eo = mc_pair<T, F>(xo, yo, zo, xj, yj, zj), en = mc_pair<T, F>(xn, yn, zn, xj, yj, zj);
+                const T eo = pw_pair_energy<T, F>(xo, yo, zo, xj, yj, zj), en = pw_pair_energy<T, F>(xn, yn, zn, xj, yj, zj);
                 e_old += jj == j ? T(0) : eo;
                 e_new += jj == j ? T(0) : en;
             }
@@ -304,8 +285,8 @@ __global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd,
         const T xb = c[n3 + i], yb = c[n3 + N + i], zb = c[n3 + 2 * N + i];
         T row_a = T(0), row_b = T(0);
         for (int j = 0; j < N; ++j) {
-            const T ea = mc_pair<T, F>(xa, ya, za, c[j], c[N + j], c[2 * N + j]);
-            const T eb = mc_pair<T, F>(xb, yb, zb, c[n3 + j], c[n3 + N + j], c[n3 + 2 * N + j]);
+            const T ea = pw_pair_energy<T, F>(xa, ya, za, c[j], c[N + j], c[2 * N + j]);
+            const T eb = pw_pair_energy<T, F>(xb, yb, zb, c[n3 + j], c[n3 + N + j], c[n3 + 2 * N + j]);
             row_a += j == i ? T(0) : ea;
             row_b += j == i ? T(0) : eb;
         }
@@ -397,15 +378,7 @@ static void tp_free(dzo_tempering_s *h) {
     delete h;
 }
 
-static int32_t tp_alloc(void **p, size_t bytes) {
-    if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        set_error("out of device memory for the tempering state (%zu bytes)", bytes);
-        return DZO_ERR_NOMEM;
-    }
-    return DZO_OK;
-}
+static int32_t tp_alloc(void **p, size_t bytes) { return device_alloc(p, bytes, "the tempering state", false); }
 
 // _fac = ten successive square roots of two in T (:21-24); the host's sqrt is correctly rounded
 template <typename T> static double tp_fac() {
@@ -500,12 +473,8 @@ int32_t dzo_tempering_create(int32_t radial, int64_t n_particles, int64_t n_repl
     DZO_REQUIRE(out, DZO_ERR_INVALID, "null argument");
     *out = nullptr;
     DZO_REQUIRE(replicas_dev && inverse_temperatures && perturbation_radii, DZO_ERR_INVALID, "null argument");
-    DZO_REQUIRE(radial == DZO_RADIAL_LENNARD_JONES, DZO_ERR_INVALID, "unknown radial function %d (DZO_RADIAL_LENNARD_JONES = 0 is the one built in)", radial);
-    DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
-    DZO_REQUIRE(n_particles >= 1, DZO_ERR_INVALID, "n_particles must be at least 1 (got %lld)", (long long)n_particles);
-    DZO_REQUIRE(n_replicas >= 1 && n_replicas <= ((int64_t)1 << 30), DZO_ERR_INVALID, "n_replicas must be in 1 .. 2^30 (got %lld)", (long long)n_replicas);
-    DZO_REQUIRE(n_particles <= kTemperMaxN, DZO_ERR_UNSUPPORTED, "n_particles = %lld: the tempering kernels hold a replica in LDS, up to %d particles",
-                (long long)n_particles, kTemperMaxN);
+    DZO_TRY(pw_check_args(radial, dtype, n_particles, n_replicas, "n_replicas", kTemperMaxN, DZO_ERR_UNSUPPORTED,
+                          "the tempering kernels hold a replica in LDS"));
     DZO_TRY(require_same_backend("parallel_temper!", "scripts/MonteCarlo.jl:31", replicas_dev, "replicas", nullptr, ""));
     Context &c = ctx();
     dzo_tempering_s *h = new (std::nothrow) dzo_tempering_s();
@@ -660,10 +629,7 @@ int32_t dzo_tempering_read(dzo_tempering_t h, int32_t what, void *out_host) {
     void *p = nullptr;
     size_t bytes = 0;
     DZO_TRY(tp_array(h, what, &p, &bytes));
-    hipStream_t s = ctx().stream;
-    DZO_HIP(hipMemcpyAsync(out_host, p, bytes, hipMemcpyDeviceToHost, s));
-    DZO_HIP(hipStreamSynchronize(s));
-    return DZO_OK;
+    return copy_blocking(out_host, p, bytes, hipMemcpyDeviceToHost);
 }
 
 int32_t dzo_tempering_set(dzo_tempering_t h, int32_t what, const void *in_host) {
@@ -675,10 +641,7 @@ int32_t dzo_tempering_set(dzo_tempering_t h, int32_t what, const void *in_host) 
     void *p = nullptr;
     size_t bytes = 0;
     DZO_TRY(tp_array(h, what, &p, &bytes));
-    hipStream_t s = ctx().stream;
-    DZO_HIP(hipMemcpyAsync(p, in_host, bytes, hipMemcpyHostToDevice, s));
-    DZO_HIP(hipStreamSynchronize(s));
-    return DZO_OK;
+    return copy_blocking(p, in_host, bytes, hipMemcpyHostToDevice);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ import re
 
 import pytest
 
+from build_checks import kernel_metadata
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,30 +132,7 @@ def test_streaming_kernels_keep_their_registers():
     prefetch.  Guard every instantiation, fp32 included (its K = 20 form used to spill the fp64 copies
     of the new pair), the two-pass streaming kernels and the batched step kernel against a compiler or
     source change that tips them over."""
-    import shutil
-    import subprocess
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
-        pytest.skip("no ROCm llvm tools")
-    with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(dzo.build(), os.path.join(tmp, "lib.so"))
-        subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        meta = {}
-        for f in os.listdir(tmp):
-            if "gfx950" not in f:
-                continue
-            notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", f], cwd=tmp, check=True,
-                                   capture_output=True, text=True).stdout
-            name = None
-            for line in notes.splitlines():
-                m = re.match(r"\s+\.name:\s+(\S+)", line)
-                if m:
-                    name = m.group(1)
-                m = re.match(r"\s+\.(vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-                if m and name:
-                    meta.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    meta = kernel_metadata()
     guarded = [n for n in meta if re.search(r"lbfgs_single_pass_kernelI[df]|lbfgs_point_pass_kernelI[df]|gram_pass_lanes_kernelI[df]|combine_kernelI[df]|batch_step_kernelI[df]Li[124]", n)]
     assert len(guarded) >= 12, sorted(meta)[:20]
     # (the DECORATED instantiations of the point pass -- last template argument true, "...ELb1EEEv" -- are the rarely used

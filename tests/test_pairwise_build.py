@@ -4,16 +4,11 @@ links against the library alone.  No compute here."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
-
+from build_checks import kernel_metadata, link_example
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = ["dzo_pairwise_energy", "dzo_pairwise_gradient", "dzo_pairwise_hvp", "dzo_pairwise_energy_delta", "dzo_calibrate_fma_rate"]
 
 
@@ -38,27 +33,7 @@ def test_python_constants_and_functions():
 def test_pairwise_kernels_exist_for_gfx950_without_scratch():
     """Four entries x two element types is the fewest there can be; every one of them keeps its accumulators in registers:
     no private segment, no VGPR or SGPR spill."""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
-        pytest.skip("no ROCm llvm tools")
-    with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(dzo.build(), os.path.join(tmp, "lib.so"))
-        subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        meta = {}
-        for f in os.listdir(tmp):
-            if "gfx950" not in f:
-                continue
-            notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", f], cwd=tmp, check=True,
-                                   capture_output=True, text=True).stdout
-            name = None
-            for line in notes.splitlines():
-                m = re.match(r"\s+\.name:\s+(\S+)", line)
-                if m:
-                    name = m.group(1)
-                m = re.match(r"\s+\.(vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-                if m and name:
-                    meta.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    meta = kernel_metadata()
     kernels = sorted(n for n in meta if "pairwise" in n)
     assert len(kernels) >= 8, kernels
     for shape in ("pairwise_tile_kernel", "pairwise_wave_kernel", "pairwise_energy_delta_kernel"):
@@ -71,15 +46,5 @@ def test_pairwise_kernels_exist_for_gfx950_without_scratch():
 
 
 def test_lj_cluster_example_compiles_and_links(tmp_path):
-    dzo.build()
-    exe = str(tmp_path / "lj_cluster")
-    cmd = ["gcc", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "lj_cluster.c"),
-           "-L" + PKG, "-ldzo_hip", "-Wl,-rpath," + PKG, "-lm", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run(["nm", "-u", exe], check=True, capture_output=True, text=True).stdout
-    wanted = {l.split()[-1].split("@")[0] for l in out.splitlines() if " dzo_" in l}
-    exported = subprocess.run(["nm", "-D", "--defined-only", os.path.join(PKG, "libdzo_hip.so")], check=True, capture_output=True,
-                              text=True).stdout
-    have = {l.split()[-1] for l in exported.splitlines()}
+    _, wanted, have = link_example(tmp_path, "lj_cluster")
     assert {"dzo_pairwise_energy", "dzo_problem_create", "dzo_lbfgs_step"} <= wanted and wanted <= have, wanted - have

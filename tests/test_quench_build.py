@@ -4,12 +4,8 @@ tests/test_tempering_build.py), and the plain-C example compiles and links again
 import ctypes
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
-
+from build_checks import kernel_metadata, link_example
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,27 +50,7 @@ def test_header_cites_the_reference_for_every_entry():
 def test_quench_kernels_exist_for_gfx950_without_scratch():
     """Both launch shapes of the step kernel (the BLOCK shape with the history in LDS and in device memory) and of the
     evaluation kernel, two element types each: no private segment, no VGPR or SGPR spill."""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
-        pytest.skip("no ROCm llvm tools")
-    with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(dzo.build(), os.path.join(tmp, "lib.so"))
-        subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        meta = {}
-        for f in os.listdir(tmp):
-            if "gfx950" not in f:
-                continue
-            notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", f], cwd=tmp, check=True,
-                                   capture_output=True, text=True).stdout
-            name = None
-            for line in notes.splitlines():
-                m = re.match(r"\s+\.name:\s+(\S+)", line)
-                if m:
-                    name = m.group(1)
-                m = re.match(r"\s+\.(vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|vgpr_count|sgpr_count):\s+(\d+)", line)
-                if m and name:
-                    meta.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    meta = kernel_metadata()
     kernels = sorted(n for n in meta if re.search(r"quench_(wave|block)_(step|eval)_kernel|quench_count_active_kernel", n))
     assert len(kernels) >= 11, kernels
     for shape in ("quench_wave_step_kernel", "quench_block_step_kernel", "quench_wave_eval_kernel", "quench_block_eval_kernel"):
@@ -92,21 +68,12 @@ def test_quench_kernels_exist_for_gfx950_without_scratch():
 
 def test_source_uses_the_shared_pair_arithmetic():
     src = open(os.path.join(PKG, "csrc", "dzo_lbfgs_batch.hip")).read()
-    assert '#include "dzo_pairwise.h"' in src and "LJRadial<T>" in src and "pw_pin(" in src
+    assert '#include "dzo_pairwise.h"' in src and "LJRadial<T>" in src and "pw_pair<" in src
+    assert "F::energy(" not in src and "F::first(" not in src
     assert "atomicAdd(&total" in src and src.count("atomic") <= 4      # the one integer count; no floating-point atomic
     assert "csrc/dzo_lbfgs_batch.hip" in open(os.path.join(PKG, "Makefile")).read()
 
 
 def test_lj_quench_example_compiles_and_links(tmp_path):
-    dzo.build()
-    exe = str(tmp_path / "lj_quench")
-    cmd = ["gcc", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "lj_quench.c"),
-           "-L" + PKG, "-ldzo_hip", "-Wl,-rpath," + PKG, "-lm", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run(["nm", "-u", exe], check=True, capture_output=True, text=True).stdout
-    wanted = {l.split()[-1].split("@")[0] for l in out.splitlines() if " dzo_" in l}
-    exported = subprocess.run(["nm", "-D", "--defined-only", os.path.join(PKG, "libdzo_hip.so")], check=True, capture_output=True,
-                              text=True).stdout
-    have = {l.split()[-1] for l in exported.splitlines()}
+    _, wanted, have = link_example(tmp_path, "lj_quench")
     assert {"dzo_lbfgs_batch_create", "dzo_lbfgs_batch_step", "dzo_lbfgs_batch_read", "dzo_tempering_run"} <= wanted and wanted <= have, wanted - have

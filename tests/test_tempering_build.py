@@ -4,12 +4,8 @@ example compiles and links against the library alone.  No compute here."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
-
+from build_checks import kernel_metadata, link_example
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,27 +44,7 @@ def test_header_states_the_random_number_rule():
 def test_tempering_kernels_exist_for_gfx950_without_scratch():
     """Both launch shapes of the temper kernel, the swap and the analyze kernel, two element types each; every one keeps its
     state in registers: no private segment, no VGPR or SGPR spill."""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
-        pytest.skip("no ROCm llvm tools")
-    with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(dzo.build(), os.path.join(tmp, "lib.so"))
-        subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        meta = {}
-        for f in os.listdir(tmp):
-            if "gfx950" not in f:
-                continue
-            notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", f], cwd=tmp, check=True,
-                                   capture_output=True, text=True).stdout
-            name = None
-            for line in notes.splitlines():
-                m = re.match(r"\s+\.name:\s+(\S+)", line)
-                if m:
-                    name = m.group(1)
-                m = re.match(r"\s+\.(vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-                if m and name:
-                    meta.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    meta = kernel_metadata()
     kernels = sorted(n for n in meta if re.search(r"temper_wave_kernel|temper_block_kernel|swap_kernel|analyze_kernel", n))
     assert len(kernels) >= 8, kernels
     for shape in ("temper_wave_kernel", "temper_block_kernel", "swap_kernel", "analyze_kernel"):
@@ -80,16 +56,12 @@ def test_tempering_kernels_exist_for_gfx950_without_scratch():
         assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
 
 
+def test_source_uses_the_shared_pair_arithmetic():
+    src = open(os.path.join(PKG, "csrc", "dzo_tempering.hip")).read()
+    assert '#include "dzo_pairwise.h"' in src and "pw_pair_energy<" in src
+    assert "F::energy(" not in src
+
+
 def test_lj_tempering_example_compiles_and_links(tmp_path):
-    dzo.build()
-    exe = str(tmp_path / "lj_tempering")
-    cmd = ["gcc", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "lj_tempering.c"),
-           "-L" + PKG, "-ldzo_hip", "-Wl,-rpath," + PKG, "-lm", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run(["nm", "-u", exe], check=True, capture_output=True, text=True).stdout
-    wanted = {l.split()[-1].split("@")[0] for l in out.splitlines() if " dzo_" in l}
-    exported = subprocess.run(["nm", "-D", "--defined-only", os.path.join(PKG, "libdzo_hip.so")], check=True, capture_output=True,
-                              text=True).stdout
-    have = {l.split()[-1] for l in exported.splitlines()}
+    _, wanted, have = link_example(tmp_path, "lj_tempering")
     assert {"dzo_tempering_create", "dzo_tempering_run", "dzo_tempering_analyze"} <= wanted and wanted <= have, wanted - have
