@@ -165,11 +165,12 @@ class Quench:
 
 
 # ------------------------------------------------------------------------------ decisions
-def decision_margin(x_old, x_new, dtype):
+def decision_margin(x_old, x_new, dtype, old=None):
     """(E_new - E_old, bound) in longdouble with bound = (N + 32) u (S_old + S_new): a trial whose |difference| is within the
-    bound is one an evaluation correct to the derived error bound may decide either way."""
+    bound is one an evaluation correct to the derived error bound may decide either way.  `old`: exact_energy(x_old), where the
+    caller has it from an earlier trial of the same step."""
     n = len(x_old) // 3
-    e0, s0 = exact_energy(x_old)
+    e0, s0 = exact_energy(x_old) if old is None else old
     e1, s1 = exact_energy(x_new)
     return e1 - e0, LD(n + 32) * U[np.dtype(dtype)] * (s0 + s1)
 

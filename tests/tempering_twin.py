@@ -238,7 +238,7 @@ def heat_capacity(V1, V2, V3, inv_tau, dtype):
 
 
 # ------------------------------------------------------------------------------ inputs of the trajectory tests
-TRAJECTORY_NS = [2, 13, 38, 64, 65, 200]
+TRAJECTORY_NS = [2, 13, 38, 64, 65, 200, 256, 257, 1024]      # from 257 on the block kernel's strided loops make a second trip
 TRAJECTORY_REPLICAS = 3
 TRAJECTORY_STEPS = 200
 TRAJECTORY_SEED = 4242

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import pairwise_twin as tw
+import quench_checks as qc
 import quench_twin as qt
 from dzo_loader import dzo
 from oracle import oracle as orc
@@ -31,10 +32,10 @@ LD = np.longdouble
 U = qt.U
 DTYPES = [np.float64, np.float32]
 NS = [13, 38, 200]                                # WAVE, WAVE, BLOCK
-TOL_DIRECTION = {np.dtype(np.float64): 1e-10, np.dtype(np.float32): 2e-6}
+TOL_DIRECTION = qc.TOL_DIRECTION                   # set at history_length 10
 WINDOW = {np.dtype(np.float64): 20, np.dtype(np.float32): 5}
-VECTORS = ["POINTS", "GRADIENTS", "DIRECTIONS", "DELTA_POINTS", "DELTA_GRADIENTS", "OBJECTIVES", "DELTA_OBJECTIVES", "IS_STUCK",
-           "ITERATION_COUNTS", "HISTORY_COUNTS", "S", "Y", "RHO", "LAST_HALVINGS"]
+VECTORS = qc.VECTORS
+_make, _same, _state, _assert_same_state, _consistent = qc.make, qc.same, qc.state, qc.assert_same_state, qc.consistent
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -52,41 +53,6 @@ def _start(n, seed, dtype):
 
 def _starts(n, seeds, dtype):
     return np.stack([_start(n, s, dtype) for s in seeds])
-
-
-def _make(points, n, m=10, step=0.01):
-    dev = dzo.DeviceArray.from_host(np.ascontiguousarray(points).ravel())
-    return dev, dzo.BatchedLBFGS(dev, n, step, m)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.int64, 4: np.int32}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _state(opt):
-    """Every array of the handle; of S, Y and RHO only the pairs that are held."""
-    st = {name: opt.read(getattr(dzo, "LBFGS_BATCH_" + name)) for name in VECTORS}
-    for b, hc in enumerate(st["HISTORY_COUNTS"]):
-        st["S"][b, hc:] = 0; st["Y"][b, hc:] = 0; st["RHO"][b, hc:] = 0
-    return st
-
-
-def _assert_same_state(a, b, what, rows_a=slice(None), rows_b=slice(None)):
-    for name in VECTORS:
-        assert _same(a[name][rows_a], b[name][rows_b]), (what, name)
-
-
-def _consistent(opt, n, st, what):
-    """The stored objective and gradient are those of the stored point, bit for bit."""
-    gdev = dzo.DeviceArray.zeros(opt.batch * 3 * n, opt.dtype)
-    e = dzo.pairwise_batch_energy_gradient(opt.points, n, gdev)
-    assert _same(e, st["OBJECTIVES"]), (what, "objective")
-    assert _same(gdev.to_host().reshape(opt.batch, 3 * n), st["GRADIENTS"]), (what, "gradient")
 
 
 # ------------------------------------------------------------------------------ 1. invariants
@@ -277,22 +243,35 @@ def test_single_particle_is_stuck_at_creation(dtype):
     _assert_same_state(_state(opt), st, "N = 1 after step")
 
 
-@pytest.mark.parametrize("n", [38, 200])
-def test_coincident_particles_do_not_disturb_the_neighbours(n):
-    starts = _starts(n, range(3), np.float64)
+@pytest.mark.parametrize("n,m,dtype,halvings", [
+    pytest.param(38, 10, np.float64, 64, id="38"), pytest.param(200, 10, np.float64, 64, id="200"),
+    pytest.param(64, 3, np.float64, 8, id="64-3"), pytest.param(257, 1, np.float64, 8, id="257-1"),
+    pytest.param(1024, 5, np.float32, 8, id="1024-5-float32")])
+def test_coincident_particles_do_not_disturb_the_neighbours(n, m, dtype, halvings):
+    """Two particles of instance 1 share a place: its energy is not finite, no trial is accepted, and it is stuck after
+    max_halvings trials of its first step, in the state the header documents; its neighbours in the batch do not notice."""
+    starts = _starts(n, range(3), dtype)
     clean = starts.copy()
     starts[1, 1] = starts[1, 0]; starts[1, n + 1] = starts[1, n]; starts[1, 2 * n + 1] = starts[1, 2 * n]   # particles 0 and 1 coincide
-    _, bad = _make(starts, n)
-    bad.set_max_halvings(64)
-    _, ref = _make(clean, n)
-    ref.set_max_halvings(64)
+    _, bad = _make(starts, n, m)
+    bad.set_max_halvings(halvings)
+    _, ref = _make(clean, n, m)
+    ref.set_max_halvings(halvings)
+    history = ("HISTORY_COUNTS", "S", "Y", "RHO")
+    first = {name: bad.read(getattr(dzo, "LBFGS_BATCH_" + name)) for name in VECTORS}        # S, Y and RHO as they are stored
     active = [bad.count_active()]
     for _ in range(4):
         bad.step(25); ref.step(25)
         active.append(bad.count_active())
-    assert bad.is_stuck[1] and bad.last_halvings[1] == 64 and bad.iteration_counts[1] == 0
+    assert bad.is_stuck[1] and bad.last_halvings[1] == halvings and bad.iteration_counts[1] == 0
     assert all(x >= y for x, y in zip(active, active[1:])), active
     _assert_same_state(_state(bad), _state(ref), "neighbours of a singular instance", [0, 2], [0, 2])
+    last = {name: bad.read(getattr(dzo, "LBFGS_BATCH_" + name)) for name in VECTORS}
+    assert _same(last["POINTS"][1], starts[1]) and _same(last["DELTA_POINTS"][1], starts[1]), "delta_point holds the old point"
+    assert _same(last["DELTA_GRADIENTS"][1], first["DELTA_GRADIENTS"][1]) and not last["DELTA_GRADIENTS"][1].any()
+    assert last["HISTORY_COUNTS"][1] == 0
+    for name in history + ("GRADIENTS", "OBJECTIVES", "DELTA_OBJECTIVES"):
+        assert _same(last[name][1], first[name][1]), (name, "changed in the step that got stuck")
 
 
 def test_count_active_falls_to_zero_and_the_handle_aliases_its_points():
@@ -358,10 +337,16 @@ def test_error_codes():
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_history_in_device_memory_matches_history_in_lds(dtype):
-    """N = 1024 keeps the history ring in the handle's global slab; N = 200 keeps it in LDS.  Both obey the invariants; the
-    large one is checked here for a few steps (consistency, deltas, decrease)."""
-    n = 1024
-    dev, opt = _make(_starts(n, range(2), dtype), n)
+    """N = 1024 keeps the history ring in the handle's global slab from history_length 5 (fp32) / 1 (fp64) on.  The path follows
+    from (N, m, T), so no instance runs on both; what the two have in common is the oracle and the single-step launches.  Over
+    m + 3 steps, which turn the ring past its end: the invariants (consistency, deltas, decrease), every direction against the
+    oracle and the twin on the state read before it with the ring shifting by one, and one launch of m + 3 steps against
+    m + 3 launches of one and against step(m) + step(3), bit for bit.  tests/test_gpu_quench_shapes.py holds the shapes on either
+    side of the LDS limit, (97, 32) | (98, 32) and others, to the same checks."""
+    n, m = 1024, {np.dtype(np.float64): 1, np.dtype(np.float32): 5}[np.dtype(dtype)]
+    assert qc.path(n, m, dtype) == qc.BLOCK_SLAB
+    points = _starts(n, range(2), dtype)
+    dev, opt = _make(points, n, m)
     prev = _state(opt)
     for k in range(1, 4):
         opt.step(1)
@@ -369,8 +354,12 @@ def test_history_in_device_memory_matches_history_in_lds(dtype):
         _consistent(opt, n, cur, (n, k))
         assert np.array_equal(cur["DELTA_POINTS"], cur["POINTS"] - prev["POINTS"]) and np.array_equal(cur["DELTA_GRADIENTS"], cur["GRADIENTS"] - prev["GRADIENTS"])
         assert np.all(cur["OBJECTIVES"] < prev["OBJECTIVES"]) and np.all(cur["ITERATION_COUNTS"] == k)
-        assert _same(cur["S"][:, 0], cur["DELTA_POINTS"]) and (k == 1 or _same(cur["S"][:, 1], prev["S"][:, 0]))
+        assert _same(cur["S"][:, 0], cur["DELTA_POINTS"]) and (k == 1 or m == 1 or _same(cur["S"][:, 1], prev["S"][:, 0]))
         prev = cur
+    _, opt = _make(points, n, m)
+    worst = qc.check_directions_and_ring(opt, n, m, dtype, m + 3)
+    print(f"N={n} m={m} {np.dtype(dtype).name}: worst direction error / tolerance {worst:.4f}")
+    qc.check_one_launch_against_many(points, n, m, m + 3)
 
 
 # ------------------------------------------------------------------------------ 8. tempering hand-over
