@@ -28,29 +28,18 @@
 #include <type_traits>
 #include <utility>
 
+#include "dzo_lbfgs_plan.h"
 #include "dzo_optcore.h"
 #include "dzo_rosen.h"
 
 namespace dzo {
 
-constexpr int kGramValues = 5;  // per pair: s.g, y.g, y.y_p, y.s_p, s.y_p  (p = pivot pair)
+static_assert(kPlanWaves == kWaves && kPlanMaxHistory == kMaxHistory && kPlanMaxPartialBlocks == kMaxPartialBlocks,
+              "dzo_lbfgs_plan.h restates these constants of dzo_common.h");
 
 struct SlotMap {
     uint8_t slot[kMaxHistory];
 };
-
-struct RingDecor {
-    double l2 = 0; bool bg_on = false; double bg_lo = 0, bg_hi = 0; bool cons_on = false; double cons_lo = 0, cons_hi = 0;
-    bool any() const { return l2 != 0.0 || bg_on || cons_on; }
-    bool operator==(const RingDecor &o) const {
-        return l2 == o.l2 && bg_on == o.bg_on && cons_on == o.cons_on && (!bg_on || (bg_lo == o.bg_lo && bg_hi == o.bg_hi)) &&
-               (!cons_on || (cons_lo == o.cons_lo && cons_hi == o.cons_hi));
-    }
-};
-
-constexpr int kRowOwn = 62;                     // wave-row geometry of the single-pass kernel (see there)
-constexpr int kRowLead = (64 - kRowOwn) / 2;
-constexpr int kTileBytes = 64 * 16;             // one stream's share of a wave-row in the blocked ring
 
 }  // namespace dzo
 
@@ -994,12 +983,7 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(CombineParams<T> p) {
 // each side.  62 uses the whole wave.  (56 owned vectors = seven whole 128-B lines per stream, so
 // that rows start on line boundaries, measured slower: 770 vs 757 us -- 11 % more rows and
 // redundant halo loads cost more than the partial first / last line of every row.)
-constexpr int kPairMaxK = 20;                  // pairs the single-pass step over a PAIR ring holds (its largest instantiation)
-// points the point pass holds: K = 20 is what fits two waves per SIMD (247 of 256 registers); fp64 has one more
-// instantiation, K = 24 on two register sets and one wave per SIMD (508 of 512), so that m = 21 .. 24 do not fall
-// back to the two-pass kernels (n = 1e7, m = 24: 683 step!()/s there)
-static inline int point_max_k(int32_t dtype) { return dtype == DZO_F64 ? 24 : 20; }
-constexpr int kFusedMaxK = 24;                 // two register sets of 2k history vectors: 2*2*20 x 16 B per lane
+// (kPairMaxK, point_max_k, kFusedMaxK: dzo_lbfgs_plan.h)
 
 // The decorators of legacy/DZOptimization.jl:219-296 as the point pass applies them (DEC instantiations), per element:
 //   L2GradientWrapper (:247)            g += (lambda + lambda) x          after the stencil, for every point of the ring and the trial point
@@ -2698,8 +2682,7 @@ static inline RingDecor ring_decor_of(const dzo_problem_s *p) {
 }
 // the chained objectives the point pass serves (ChainObj): -1 = none of them
 static inline int ring_obj_of(const dzo_problem_s *p) {
-    if (!p) return -1;
-    return p->kind == DZO_PROBLEM_ROSENBROCK_CHAIN ? 0 : (p->kind == DZO_PROBLEM_QUADRATIC_CHAIN ? 1 : (p->kind == DZO_PROBLEM_LSE ? 2 : -1));
+    return p ? ring_obj_of_kind(p->kind) : -1;
 }
 // vectors of 16 bytes a ring stream holds: the last one is padded with phantom elements when n is ragged (see load_vec_tail)
 template <typename T> static inline int64_t ring_nvec(const dzo_lbfgs_s *o) { return (o->core.n + Vec16<T>::N - 1) / Vec16<T>::N; }
@@ -3106,7 +3089,6 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
     return DZO_OK;
 }
 
-static inline bool al16v(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // the twin buffers of x and g (the pair-ring pass writes its trial point / gradient there; the general path's gradient
 // callback writes g_new there): one slab, allocated on first use; false when the allocation fails
@@ -3124,36 +3106,39 @@ static bool lbfgs_ensure_twins(dzo_lbfgs_s *o) {
     return true;
 }
 
+// what a step looks at to choose its path (the decisions themselves: dzo_lbfgs_plan.h)
+static LbfgsStepFacts step_facts(const dzo_lbfgs_s *o) {
+    const OptCore &c = o->core;
+    LbfgsStepFacts f;
+    f.points = o->points; f.single_pass = o->single_pass; f.blocked = o->blocked;
+    f.mode = o->mode; f.line_search = o->line_search;
+    f.descent_check = o->descent_check; f.sd_fallback = o->sd_fallback; f.speculate = o->speculate; f.fused_post = o->fused_post;
+    f.callbacks = c.objective || c.gradient || c.constraint;
+    f.box_on = c.box_on; f.has_problem = c.problem != nullptr;
+    f.iteration_count = c.iteration_count; f.n = c.n; f.k = o->k; f.m = o->m; f.dtype = c.dtype;
+    f.ring_obj = o->ring_obj; f.ring_decorated = o->ring_dec.any();
+    f.obj_agrees = ring_obj_of(c.problem) == o->ring_obj;
+    f.dec_agrees = ring_decor_of(c.problem) == o->ring_dec;
+    f.lambda_agrees = c.problem && c.problem->lambda == o->ring_obj_lambda;
+    f.lse_c_agrees = c.problem && c.problem->c == o->lse_c;
+    f.spec_scalars = o->spec_scalars; f.d_al16 = al16(o->d);
+    return f;
+}
+
 // can this step run as one pass over the history?  (built-in chained Rosenbrock, plain options)
 static bool single_pass_ok(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
-    if (!o->single_pass || !o->blocked || o->mode != DZO_TWOLOOP_GRAM || o->line_search != 0 || o->descent_check || o->sd_fallback) return false;
-    if (c.objective || c.gradient || c.constraint || c.box_on || !o->speculate || !o->fused_post) return false;
-    if (c.iteration_count == 0 || o->k < 1 || o->k > kPairMaxK || o->m > kPairMaxK) return false;   // (m: the pass also forms the dots of pair k + 1)
-    const int vecn = 16 / (int)dtype_size(c.dtype);
-    // (a ragged n never gets here: its tile ring exists as a POINT ring only -- lbfgs_leave_points hands it to the slabs)
-    if (c.n < 4 * vecn || (uint64_t)c.n * dtype_size(c.dtype) >= (1ull << 32)) return false;   // 32-bit byte offsets
+    const LbfgsStepFacts f = step_facts(o);
+    if (!single_pass_plan_ok(f)) return false;
     o->refresh_delta_ptrs();
-    if (!problem_has_fused_post(c.problem, c.x, c.dx, c.g, c.dg) || !al16v(o->d)) return false;
+    if (!problem_has_fused_post(c.problem, c.x, c.dx, c.g, c.dg) || !al16(o->d)) return false;
     // the twin buffers of x and g: allocated here, before the step touches anything; a failed allocation
     // only switches this optimizer to the two-pass kernels
     if (!lbfgs_ensure_twins(o)) { o->single_pass = false; return false; }
     return true;
 }
 
-// the point ring serves exactly the optimizers the single-pass step serves (and, unlike it, the first step)
-static bool points_ok(dzo_lbfgs_s *o) {
-    OptCore &c = o->core;
-    if (!o->points || !o->single_pass || !o->blocked || o->mode != DZO_TWOLOOP_GRAM || o->line_search != 0 || o->descent_check || o->sd_fallback) return false;
-    if (c.objective || c.gradient || c.constraint || !o->speculate || !o->fused_post || !c.problem) return false;
-    // (the decorators of legacy :219-296 ride on the pass: its DEC instantiations, under the set the ring was stored with)
-    if (ring_obj_of(c.problem) != o->ring_obj || !(ring_decor_of(c.problem) == o->ring_dec)) return false;
-    if (o->ring_obj >= 1 && (o->ring_dec.any() || c.problem->lambda != o->ring_obj_lambda)) return false;   // (no DEC instantiations of those objectives)
-    if (o->ring_obj == 2 && c.problem->c != o->lse_c) return false;
-    if (o->k > point_max_k(c.dtype) || o->m > point_max_k(c.dtype) || !al16v(o->d)) return false;
-    if (o->k > 0 && !o->spec_scalars) return false;       // (the scalars come from the previous pass; anything else goes through Gram passes)
-    return true;
-}
+static bool points_ok(dzo_lbfgs_s *o) { return points_plan_ok(step_facts(o)); }
 
 // ---- aliasing of the caller's arrays (:393, :395) with twin buffers
 static int32_t lbfgs_settle_entry(void *h);
@@ -3226,18 +3211,14 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     fp.changed = c.flag();
     fp.debug_skip = tune("DZO_TUNE_SP_DEBUG", 0);
     // register footprint follows the history length: pick the smallest instantiation that holds m pairs
-    void (*kern)(FusedParams<T>) = o->m <= 8 ? lbfgs_single_pass_kernel<T, 8>
-                                   : o->m <= 16 ? lbfgs_single_pass_kernel<T, 16>
+    const int pass_k = pair_pass_k(o->m);
+    void (*kern)(FusedParams<T>) = pass_k == 8 ? lbfgs_single_pass_kernel<T, 8>
+                                   : pass_k == 16 ? lbfgs_single_pass_kernel<T, 16>
                                    : lbfgs_single_pass_kernel<T, 20>;
     if constexpr (std::is_same<T, double>::value) {
         if ((fp.debug_skip & 256) && o->m > 16) kern = lbfgs_single_pass_kernel<double, 20, true>;
     }
-    int64_t blocks = (rows + kWaves - 1) / kWaves;
-    const int64_t res = (int64_t)ctx().cus * resident_blocks((const void *)kern);
-    if (blocks > res) blocks = res;
-    if (blocks > (int64_t)o->gram_grid * kWaves) blocks = (int64_t)o->gram_grid * kWaves;
-    if (blocks > kMaxPartialBlocks) blocks = kMaxPartialBlocks;              // two objective partials per block in the problem scratch
-    const int grid = (int)(blocks < 1 ? 1 : blocks);
+    const int grid = pass_grid(rows, (int64_t)ctx().cus * resident_blocks((const void *)kern), o->gram_grid, kPairPassGridCap);
     // The pass runs at t = 1 and, when that trial is rejected while the objective at t/2 (which rode along) is a
     // decrease, once more at t = 1/2 -- the loop of take_backtracking_step! (:121-152) on the same kernel, x and g
     // untouched in between.  Deeper halvings continue on the cheap trial kernels.
@@ -3324,86 +3305,45 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
 // x and g (= point 0) untouched until a trial is accepted, which makes the spare slot point 0.
 // grid of a point pass: the resident blocks, bounded by the partial-sum buffers
 template <typename T> static int points_grid(dzo_lbfgs_s *o, void (*kern)(FusedParams<T>), size_t dyn_lds = 0) {
-    const int64_t nvec = ring_nvec<T>(o);
-    const int64_t rows = (nvec + kRowOwn - 1) / kRowOwn;
-    int64_t blocks = (rows + kWaves - 1) / kWaves;
-    const int64_t res = (int64_t)ctx().cus * resident_blocks((const void *)kern, dyn_lds);
-    if (blocks > res) blocks = res;
-    if (blocks > (int64_t)o->gram_grid * kWaves) blocks = (int64_t)o->gram_grid * kWaves;
-    if (blocks > kMaxPartialBlocks / 2) blocks = kMaxPartialBlocks / 2;     // up to four partial sums per block in the problem scratch (2 kMaxPartialBlocks doubles)
-    return (int)(blocks < 1 ? 1 : blocks);
+    const int64_t rows = (ring_nvec<T>(o) + kRowOwn - 1) / kRowOwn;
+    return pass_grid(rows, (int64_t)ctx().cus * resident_blocks((const void *)kern, dyn_lds), o->gram_grid, kPointPassGridCap);
 }
 
-// one register set per wave (two waves per SIMD)?  DZO_TUNE_POINT_SETS=1 (the default), where the instantiation fits 256 registers
-template <typename T> static bool point_one_set(const dzo_lbfgs_s *o) { return o->point_sets == 1 && o->m <= 20 && (sizeof(T) == 8 || o->m <= 12); }
-
-// the instantiation of the point pass for this optimizer: the smallest K that holds m pairs; one or two register sets
-// (DZO_TUNE_POINT_SETS; see the kernel)
-template <typename T> static void (*point_pass_kernel_sel(dzo_lbfgs_s *o))(FusedParams<T>) {
-    if (o->ring_obj == 1) {
-        // the chained quadratic (ChainObj<T, 1>): the same ladder of history lengths as the decorated pass
-        if (point_one_set<T>(o)) {
-            if constexpr (sizeof(T) == 8) {
-                return o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 1, false, 1>
-                       : o->m <= 12 ? lbfgs_point_pass_kernel<T, 12, false, 1, false, 1>
-                       : o->m <= 16 ? lbfgs_point_pass_kernel<T, 16, false, 1, false, 1>
-                       : lbfgs_point_pass_kernel<T, 20, false, 1, false, 1>;
-            } else {
-                return o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 1, false, 1> : lbfgs_point_pass_kernel<T, 12, false, 1, false, 1>;
-            }
-        }
-        if constexpr (sizeof(T) == 8) { if (o->m > 20) return lbfgs_point_pass_kernel<T, 24, false, 2, false, 1>; }
-        return o->m <= 12 ? lbfgs_point_pass_kernel<T, 12, false, 2, false, 1>
-               : o->m <= 16 ? lbfgs_point_pass_kernel<T, 16, false, 2, false, 1>
-               : lbfgs_point_pass_kernel<T, 20, false, 2, false, 1>;
+// Variant (dzo_lbfgs_plan.h: point_pass_variant) -> kernel.  The instantiations of the point pass are named here and nowhere
+// else.  Per list: the first step's three kernels, then the chained quadratic (OBJ = 1), the decorated pass (DEC), the plain
+// pass -- one register set, then two.  tests/test_lbfgs_plan.py reads the two lists: no entry twice, and each list is exactly
+// the set of variants point_pass_variant can return for that element type, so the nullptr below (the callers report it as an
+// error before they enqueue anything) is never returned.
+// The ORDER of a list is the order in which the compiler emits the kernels into the code object, and nothing else: do not
+// sort a list, and add a new instantiation without moving the others.  The device-code comparison of DESIGN.md
+// ("What runs: the L-BFGS plan") pins it; fp64 and fp32 have a list each because their orders differ.
+template <typename T> static void (*point_pass_kernel_of(PassVariant v))(FusedParams<T>) {
+#define DZO_PP(K, FIRST, SETS, DEC, OBJ) \
+    if (v == PassVariant{K, SETS, DEC, OBJ, FIRST}) return lbfgs_point_pass_kernel<T, K, FIRST, SETS, DEC, OBJ>;
+    if constexpr (sizeof(T) == 8) {
+        DZO_PP(8, true, 2, true, 0) DZO_PP(8, true, 2, false, 0) DZO_PP(8, true, 2, false, 1)
+        DZO_PP(16, false, 1, false, 1) DZO_PP(20, false, 1, false, 1) DZO_PP(12, false, 1, false, 1) DZO_PP(8, false, 1, false, 1)
+        DZO_PP(24, false, 2, false, 1) DZO_PP(16, false, 2, false, 1) DZO_PP(20, false, 2, false, 1) DZO_PP(12, false, 2, false, 1)
+        DZO_PP(16, false, 1, true, 0) DZO_PP(20, false, 1, true, 0) DZO_PP(12, false, 1, true, 0) DZO_PP(8, false, 1, true, 0)
+        DZO_PP(24, false, 2, true, 0) DZO_PP(16, false, 2, true, 0) DZO_PP(20, false, 2, true, 0) DZO_PP(12, false, 2, true, 0)
+        DZO_PP(18, false, 1, false, 0) DZO_PP(20, false, 1, false, 0) DZO_PP(16, false, 1, false, 0) DZO_PP(14, false, 1, false, 0) DZO_PP(12, false, 1, false, 0) DZO_PP(10, false, 1, false, 0) DZO_PP(8, false, 1, false, 0) DZO_PP(6, false, 1, false, 0)
+        DZO_PP(22, false, 2, false, 0) DZO_PP(24, false, 2, false, 0) DZO_PP(16, false, 2, false, 0) DZO_PP(20, false, 2, false, 0) DZO_PP(12, false, 2, false, 0) DZO_PP(8, false, 2, false, 0)
+    } else {
+        DZO_PP(8, true, 2, true, 0) DZO_PP(8, true, 2, false, 0) DZO_PP(8, true, 2, false, 1)
+        DZO_PP(8, false, 1, false, 1) DZO_PP(12, false, 1, false, 1)
+        DZO_PP(16, false, 2, false, 1) DZO_PP(20, false, 2, false, 1) DZO_PP(12, false, 2, false, 1)
+        DZO_PP(8, false, 1, true, 0) DZO_PP(12, false, 1, true, 0)
+        DZO_PP(16, false, 2, true, 0) DZO_PP(20, false, 2, true, 0) DZO_PP(12, false, 2, true, 0)
+        DZO_PP(10, false, 1, false, 0) DZO_PP(12, false, 1, false, 0) DZO_PP(8, false, 1, false, 0) DZO_PP(6, false, 1, false, 0)
+        DZO_PP(16, false, 2, false, 0) DZO_PP(20, false, 2, false, 0) DZO_PP(12, false, 2, false, 0) DZO_PP(8, false, 2, false, 0)
     }
-    if (o->ring_dec.any()) {
-        // the decorated pass (DEC): fewer instantiations, the next larger K serves the history lengths in between
-        if (point_one_set<T>(o)) {
-            if constexpr (sizeof(T) == 8) {
-                return o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 1, true>
-                       : o->m <= 12 ? lbfgs_point_pass_kernel<T, 12, false, 1, true>
-                       : o->m <= 16 ? lbfgs_point_pass_kernel<T, 16, false, 1, true>
-                       : lbfgs_point_pass_kernel<T, 20, false, 1, true>;
-            } else {
-                return o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 1, true> : lbfgs_point_pass_kernel<T, 12, false, 1, true>;
-            }
-        }
-        if constexpr (sizeof(T) == 8) { if (o->m > 20) return lbfgs_point_pass_kernel<T, 24, false, 2, true>; }
-        return o->m <= 12 ? lbfgs_point_pass_kernel<T, 12, false, 2, true>
-               : o->m <= 16 ? lbfgs_point_pass_kernel<T, 16, false, 2, true>
-               : lbfgs_point_pass_kernel<T, 20, false, 2, true>;
-    }
-    if (point_one_set<T>(o)) {
-        if constexpr (sizeof(T) == 8) {
-            // (K = 10: m = 10 is the history length most L-BFGS users ask for; on the K = 12 instantiation it paid for two
-            // masked pairs -- 211 us per pass at n = 1e7 where m = 12 takes 218)
-            return o->m <= 6 ? lbfgs_point_pass_kernel<T, 6, false, 1>
-                   : o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 1>
-                   : o->m <= 10 ? lbfgs_point_pass_kernel<T, 10, false, 1>
-                   : o->m <= 12 ? lbfgs_point_pass_kernel<T, 12, false, 1>
-                   : o->m <= 14 ? lbfgs_point_pass_kernel<T, 14, false, 1>
-                   : o->m <= 16 ? lbfgs_point_pass_kernel<T, 16, false, 1>
-                   : o->m <= 18 ? lbfgs_point_pass_kernel<T, 18, false, 1>
-                   : lbfgs_point_pass_kernel<T, 20, false, 1>;
-        } else {                                             // (fp32, K > 12: the fp64 copies for the dots do not fit 256 registers)
-            return o->m <= 6 ? lbfgs_point_pass_kernel<T, 6, false, 1>
-                   : o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 1>
-                   : o->m <= 10 ? lbfgs_point_pass_kernel<T, 10, false, 1> : lbfgs_point_pass_kernel<T, 12, false, 1>;
-        }
-    }
-    // (m <= 24: point_max_k; K = 22 for m = 21, 22: on K = 24 they paid for two or three masked pairs)
-    if constexpr (sizeof(T) == 8) { if (o->m > 20) return o->m <= 22 ? lbfgs_point_pass_kernel<T, 22, false, 2> : lbfgs_point_pass_kernel<T, 24, false, 2>; }
-    return o->m <= 8 ? lbfgs_point_pass_kernel<T, 8, false, 2>
-           : o->m <= 12 ? lbfgs_point_pass_kernel<T, 12, false, 2>
-           : o->m <= 16 ? lbfgs_point_pass_kernel<T, 16, false, 2>
-           : lbfgs_point_pass_kernel<T, 20, false, 2>;
+#undef DZO_PP
+    return nullptr;
 }
 // first: the first step's kernel
 template <typename T> static void (*point_pass_kernel_for(dzo_lbfgs_s *o, bool first))(FusedParams<T>) {
-    if (first) return o->ring_obj == 1 ? lbfgs_point_pass_kernel<T, 8, true, 2, false, 1>
-                      : o->ring_dec.any() ? lbfgs_point_pass_kernel<T, 8, true, 2, true> : lbfgs_point_pass_kernel<T, 8, true>;
-    return point_pass_kernel_sel<T>(o);
+    return point_pass_kernel_of<T>(point_pass_variant(o->m, o->core.dtype, point_one_set(o->m, o->core.dtype, o->point_sets),
+                                                      o->ring_dec.any(), o->ring_obj, first));
 }
 
 // step_direction of the last step, on demand: the same pass once more over the view of the ring that step started
@@ -3430,6 +3370,7 @@ template <typename T> static int32_t lbfgs_materialize_d_t(dzo_lbfgs_s *o) {
     fp.obj_lambda = (T)o->ring_obj_lambda;
     fp.stage_rows = 1;
     void (*kern)(FusedParams<T>) = point_pass_kernel_for<T>(o, false);
+    DZO_REQUIRE(kern, DZO_ERR_STATE, "direction on demand: no point-pass kernel for history_length %d", o->m);
     const int grid = points_grid<T>(o, kern);
     DZO_REQUIRE(fused_params_ok<T>(fp, false), DZO_ERR_STATE, "direction on demand: a null operand (ring %p, d %p)", (void *)fp.ring, (void *)fp.d);
     {
@@ -3454,6 +3395,8 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
     hipStream_t s = c.stream;
     const int k = o->k;
+    void (*kern)(FusedParams<T>) = point_pass_kernel_for<T>(o, k == 0);
+    DZO_REQUIRE(kern, DZO_ERR_STATE, "point pass: no kernel for history_length %d", o->m);   // (before anything is enqueued)
     if (k > 0) {
         DZO_TRY(gram_scalars<T>(o));                      // alpha / coef / scale of THIS step (computed behind the last decision)
         o->scalars_ready = false;
@@ -3473,26 +3416,15 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
     fp.debug_skip = tune("DZO_TUNE_SP_DEBUG", 0);
     fp.dec = point_decor<T>(o->ring_dec);
     fp.obj_lambda = (T)o->ring_obj_lambda;
-    void (*kern)(FusedParams<T>) = point_pass_kernel_for<T>(o, k == 0);
     fp.store_d = o->lazy_d ? 0 : 1;
-    {
-        // tile-major ring: plain stores while the two streams fit the 256-MiB Infinity Cache (695 vs 735 us at
-        // n = 1e7); stream-major ring: non-temporal (655-672 vs 659-682 us over four interleaved rounds)
-        const int64_t cache_mb = tune("DZO_TUNE_POINT_PLAIN_MB", o->tile_stride == kTileBytes ? 200 : 0);
-        fp.nt_tiles = 2 * (int64_t)c.n * (int64_t)sizeof(T) > (cache_mb << 20) ? 1 : 0;
-    }
-    // rows of new tiles a wave collects in LDS before it writes them (2 KiB per row and wave; the whole 160-KiB LDS
-    // of a CU is this one block's)
-    // (two blocks per CU with one register set per wave: half the LDS each)
-    const bool one_set = point_one_set<T>(o) && k > 0;
-    fp.prio = one_set ? (tune("DZO_TUNE_POINT_PRIO", 1) != 0 ? 1 : 0) : 0;   // (two waves per SIMD only; see the kernel)
+    // the launch shape (dzo_lbfgs_plan.h); its knobs are read per step
+    const PointLaunch pl = point_pass_launch(c.n, c.dtype, o->m, k, o->point_sets, DZO_PP_REGRAD != 0, tune("DZO_TUNE_POINT_STAGE_ROWS", 16),
+                                             tune("DZO_TUNE_POINT_PRIO", 1), tune("DZO_TUNE_POINT_PLAIN_MB", point_plain_mb_default(o->tile_stride)));
+    fp.nt_tiles = pl.nt_tiles;
+    fp.prio = pl.prio;
     fp.leftover_even = tune("DZO_TUNE_POINT_LEFTOVER_EVEN", 1) != 0 ? 1 : 0;
-    const int stage_tiles = (k == 0 || DZO_PP_REGRAD == 0) ? 2 : 1;      // tiles staged per row: the point, and its gradient where the kernel writes it
-    const int stage_max = (one_set ? 72 : 144) / (4 * stage_tiles);        // KiB of LDS per block / (waves x KiB per staged row)
-    fp.stage_rows = tune("DZO_TUNE_POINT_STAGE_ROWS", 16);
-    if (fp.stage_rows < 1) fp.stage_rows = 1;
-    if (fp.stage_rows > stage_max) fp.stage_rows = stage_max;
-    size_t stage_bytes = (size_t)kWaves * fp.stage_rows * stage_tiles * kTileBytes;
+    fp.stage_rows = pl.stage_rows;
+    size_t stage_bytes = pl.stage_bytes;
     if (o->stage_kern != (const void *)kern || o->stage_bytes != stage_bytes) {   // (once per kernel and size)
         if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes) != hipSuccess) {
             (void)hipGetLastError();                      // a device that does not grant it: stay within the default 64 KiB
@@ -3500,9 +3432,9 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
         }
         o->stage_kern = (const void *)kern; o->stage_bytes = stage_bytes;
     }
-    if (o->stage_small && fp.stage_rows > 14 / stage_tiles) {
-        fp.stage_rows = 14 / stage_tiles;
-        stage_bytes = (size_t)kWaves * fp.stage_rows * stage_tiles * kTileBytes;
+    if (o->stage_small && fp.stage_rows > point_stage_small_rows(pl.stage_tiles)) {
+        fp.stage_rows = point_stage_small_rows(pl.stage_tiles);
+        stage_bytes = point_stage_bytes(fp.stage_rows, pl.stage_tiles);
     }
     // the blocks resident at once WITH the dynamic LDS of this launch: asked without it, the query answers 3 per CU for the
     // K = 8 instantiation (149 registers) while 64 KiB of staging let two in, and the third block of every CU ran as a
@@ -3640,17 +3572,12 @@ template <typename T> static void (*lse_trial_kernel_for(dzo_lbfgs_s *o, bool fi
     return first ? lse_trial_kernel<T, true> : lse_trial_kernel<T, false>;
 }
 template <typename T> static void (*lse_dots_kernel_for(dzo_lbfgs_s *o))(LseParams<T>) {
-    if constexpr (sizeof(T) == 8) { if (o->m > 20) return lse_dots_kernel<T, 24>; }
-    return o->m <= 8 ? lse_dots_kernel<T, 8> : o->m <= 12 ? lse_dots_kernel<T, 12> : lse_dots_kernel<T, 20>;
+    const int K = lse_dots_k(o->m, o->core.dtype);
+    if constexpr (sizeof(T) == 8) { if (K == 24) return lse_dots_kernel<T, 24>; }
+    return K == 8 ? lse_dots_kernel<T, 8> : K == 12 ? lse_dots_kernel<T, 12> : lse_dots_kernel<T, 20>;
 }
 template <typename T> static int lse_grid(dzo_lbfgs_s *o, const void *kern) {
-    const int64_t rows = o->ring_rows;
-    int64_t blocks = (rows + kWaves - 1) / kWaves;
-    const int64_t res = (int64_t)ctx().cus * resident_blocks(kern);
-    if (blocks > res) blocks = res;
-    if (blocks > (int64_t)o->gram_grid * kWaves) blocks = (int64_t)o->gram_grid * kWaves;
-    if (blocks > kMaxPartialBlocks / 2) blocks = kMaxPartialBlocks / 2;
-    return (int)(blocks < 1 ? 1 : blocks);
+    return pass_grid(o->ring_rows, (int64_t)ctx().cus * resident_blocks(kern), o->gram_grid, kPointPassGridCap);
 }
 
 // step_direction of the last step on demand (as lbfgs_materialize_d_t): the trial pass over the view that step started from,
@@ -3849,16 +3776,40 @@ static int32_t lbfgs_step(dzo_lbfgs_s *o) {
 
 using namespace dzo;
 
-static thread_local bool tl_want_blocked = false;       // dzo_lbfgs_create_problem -> dzo_lbfgs_create
-static thread_local RingDecor tl_ring_dec;              // ... and the decorators the start point's gradient was formed under
-static thread_local int tl_ring_obj = 0;                // ... and the chained objective (ChainObj) with its parameter
-static thread_local double tl_ring_obj_lambda = 0;
+// the construction-time DZO_TUNE_* knobs (dev only), read once per construction
+static LbfgsKnobs lbfgs_read_knobs() {
+    LbfgsKnobs k;
+    k.stride_skew = tune("DZO_TUNE_STRIDE_SKEW", 1);
+    k.blocked = tune("DZO_TUNE_BLOCKED", 1);
+    k.single_pass = tune("DZO_TUNE_SINGLE_PASS", 1);
+    k.point_ring = tune("DZO_TUNE_POINT_RING", 1);
+    k.interleave = tune("DZO_TUNE_INTERLEAVE", 1);
+    k.stream_major_set = getenv("DZO_TUNE_STREAM_MAJOR") != nullptr;
+    k.stream_major = tune("DZO_TUNE_STREAM_MAJOR", 0);
+    k.lse_points = tune("DZO_TUNE_LSE_POINTS", 1);
+    k.lazy_d = tune("DZO_TUNE_LAZY_D", 1);
+    k.point_sets = tune("DZO_TUNE_POINT_SETS", 1);
+    k.gram_u = tune("DZO_TUNE_GRAM_U", 4);
+    k.gram_bpc = tune("DZO_TUNE_GRAM_BPC", 0);
+    k.fused_finish = tune("DZO_TUNE_FUSED_FINISH", 0);
+    k.fused_finish_max = tune("DZO_TUNE_FUSED_FINISH_MAX", 65536);
+    k.speculate = tune("DZO_TUNE_SPECULATE", 1);
+    k.gram_variant = tune("DZO_TUNE_GRAM_VARIANT", 1);
+    k.gram_peel = tune("DZO_TUNE_GRAM_PEEL", 1);
+    k.gram_fresh_plain = tune("DZO_TUNE_GRAM_FRESH_PLAIN", 1);
+    k.gram_skip0 = tune("DZO_TUNE_GRAM_SKIP0", 1);
+    k.combine_fresh_plain = tune("DZO_TUNE_COMBINE_FRESH_PLAIN", 1);
+    k.combine_nts = tune("DZO_TUNE_COMBINE_NTS", 1);
+    k.combine_u = tune("DZO_TUNE_COMBINE_U", 4);
+    k.combine_bpc = tune("DZO_TUNE_COMBINE_BPC", 0);
+    k.fused_post = tune("DZO_TUNE_FUSED_POST", 1);
+    return k;
+}
 
-// ============================================================================ C ABI
-extern "C" {
-
-int32_t dzo_lbfgs_create(int64_t n, int32_t history_length, int32_t dtype, void *x_dev, void *g_dev,
-                         double initial_objective_value, double initial_step_length, dzo_lbfgs_t *out) {
+// The constructor behind dzo_lbfgs_create (empty `start`) and dzo_lbfgs_create_problem: check arguments, read the knobs,
+// plan (lbfgs_plan_layout), allocate, carve the scalar block by the plan's offsets, zero, finish.
+static int32_t lbfgs_construct(int64_t n, int32_t history_length, int32_t dtype, void *x_dev, void *g_dev, double initial_objective_value,
+                               double initial_step_length, const LbfgsStart &start, dzo_lbfgs_t *out) {
     DZO_TRY(require_init());
     DZO_REQUIRE(out, DZO_ERR_INVALID, "null out");
     DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
@@ -3868,137 +3819,81 @@ int32_t dzo_lbfgs_create(int64_t n, int32_t history_length, int32_t dtype, void 
     DZO_REQUIRE(initial_step_length > 0, DZO_ERR_ASSERT, "@assert initial_step_length > 0 (src/DZOptimization.jl:380)");
     // :363-364 (and :366-378: everything `similar` allocates below lands on the same device by construction)
     DZO_TRY(require_same_backend("LBFGSOptimizer", "src/DZOptimization.jl:363-364", x_dev, "initial_point", g_dev, "initial_gradient"));
+    const LbfgsKnobs kn = lbfgs_read_knobs();
+    const LbfgsLayout L = lbfgs_plan_layout(n, dtype, history_length, start, kn, ctx().cus);
     dzo_lbfgs_s *o = new dzo_lbfgs_s();
     OptCore &c = o->core;
     c.n = n; c.dtype = dtype; c.x = x_dev; c.g = g_dev;
     o->x_user = x_dev; o->g_user = g_dev; o->device = ctx().device;
-    o->ring_dec = tl_ring_dec; o->ring_obj = tl_ring_obj; o->ring_obj_lambda = tl_ring_obj_lambda;
+    o->ring_dec = start.dec; o->ring_obj = L.ring_obj; o->ring_obj_lambda = start.lambda;
     c.f = round_to_dtype(dtype, initial_objective_value);
     o->m = history_length;
-    const size_t es = dtype_size(dtype);
-    {
-        // slot stride: n rounded up to 1 KiB, and an ODD number of KiB, so that the 2(m+1) streams
-        // never sit a power-of-two distance apart (same HBM channel / bank for equal offsets)
-        size_t sb = ((size_t)n * es + 1023) / 1024 * 1024;
-        if ((sb / 1024) % 2 == 0 && tune("DZO_TUNE_STRIDE_SKEW", 1)) sb += 1024;
-        o->stride = (int64_t)(sb / es);
-    }
+    o->stride = L.stride;
     o->last_step_length = round_to_dtype(dtype, initial_step_length);   // as legacy BFGS :779
     int32_t rc = core_alloc(c);
     if (rc != DZO_OK) { delete o; return rc; }
-    {
-        // blocked (tile-major) ring: when the constructor knows that the single-pass step applies
-        const int vecn = 16 / (int)es;
-        o->blocked = tl_want_blocked && tune("DZO_TUNE_BLOCKED", 1) != 0 && tune("DZO_TUNE_SINGLE_PASS", 1) != 0 &&
-                     history_length <= point_max_k(dtype) && n >= 4 * vecn && (uint64_t)n * es < (1ull << 32) &&
-                     (n % vecn == 0 || tune("DZO_TUNE_POINT_RING", 1) != 0);   // (a ragged n: phantom padding, load_vec_tail -- on the POINT ring only)
-    }
-    o->nslots = o->m + (o->blocked ? 2 : 1);
-    const int m1 = o->nslots;
-    const size_t slab = (size_t)m1 * (size_t)o->stride * es;
-    hipError_t e;
-#define ALLOC(ptr, bytes)                                                                          \
-    e = hipMalloc((void **)&(ptr), (bytes));                                                       \
-    if (e != hipSuccess) { dzo_lbfgs_destroy(o); if (e == hipErrorOutOfMemory) { set_error("out of device memory allocating the L-BFGS state (%zu bytes)", (size_t)(bytes)); (void)hipGetLastError(); return DZO_ERR_NOMEM; } return hip_fail(e, "hipMalloc", __FILE__, __LINE__); }
-    o->interleaved = tune("DZO_TUNE_INTERLEAVE", 1) != 0;
-    if (o->blocked) {
-        const int64_t nvec = (n + 16 / (int64_t)es - 1) / (16 / (int64_t)es);
-        o->ring_rows = (nvec + kRowOwn - 1) / kRowOwn;
-        {
-            const int64_t stream_bytes = ((o->ring_rows * kTileBytes + 1023) / 1024 | 1) * 1024;   // an odd number of KiB (HBM channel skew)
-            const int ms = m1 + (o->ring_obj == 2 ? 1 : 0);      // (log-sum-exp: slot m1 holds the tiles of the centre vector c)
-            const uint64_t total = (uint64_t)2 * ms * (uint64_t)stream_bytes;
-            // (few streams: the whole wave-row of a tile-major ring sits in a handful of DRAM pages and its reads win --
-            // n = 1e7: m = 5 pass 234 us tile-major / 253 us stream-major, m = 10 398 / 383, m = 20 684 / 660)
-            if (tune("DZO_TUNE_STREAM_MAJOR", o->m >= 9 ? 1 : 0) != 0 && total + (1u << 20) < (1ull << 32)) {      // 32-bit byte offsets in the passes
-                o->tile_stride = stream_bytes; o->rowbytes = kTileBytes; o->ring_bytes = (size_t)total;
-            } else {
-                o->tile_stride = kTileBytes; o->rowbytes = (int64_t)2 * ms * kTileBytes;
-                o->ring_bytes = (size_t)o->ring_rows * (size_t)o->rowbytes;
-            }
-        }
-        ALLOC(o->S, o->ring_bytes);
-        o->Y = nullptr;
-        o->pair_stride = 0;
-        ALLOC(o->dx_lin, (size_t)o->stride * es);
-        ALLOC(o->dg_lin, (size_t)o->stride * es);
-    } else if (o->interleaved) {
-        ALLOC(o->S, 2 * slab);
-        o->Y = (char *)o->S + (size_t)o->stride * es;
-        o->pair_stride = 2 * o->stride;
+    o->blocked = L.blocked; o->nslots = L.nslots; o->interleaved = L.interleaved; o->pair_stride = L.pair_stride;
+    o->ring_rows = L.ring_rows; o->tile_stride = L.tile_stride; o->rowbytes = L.rowbytes; o->ring_bytes = L.ring_bytes;
+    o->gram_grid = L.gram_grid;
+    o->gram_u = kn.gram_u; o->gram_bpc = kn.gram_bpc;
+    o->fused_finish = kn.fused_finish != 0; o->fused_finish_max = kn.fused_finish_max;
+    o->speculate = kn.speculate != 0;
+    o->gram_variant = kn.gram_variant; o->gram_peel = kn.gram_peel; o->gram_fresh_plain = kn.gram_fresh_plain; o->gram_skip0 = kn.gram_skip0;
+    o->combine_fresh_plain = kn.combine_fresh_plain; o->combine_nts = kn.combine_nts != 0; o->combine_u = kn.combine_u;
+    o->combine_blocks_per_cu = kn.combine_bpc;
+    o->single_pass = kn.single_pass != 0; o->fused_post = kn.fused_post != 0;
+    // a failed allocation gives the state back: the ring alone is gigabytes
+    auto alloc = [&](void **ptr, size_t bytes) -> int32_t {
+        const hipError_t e = hipMalloc(ptr, bytes);
+        if (e == hipSuccess) return DZO_OK;
+        dzo_lbfgs_destroy(o);
+        if (e == hipErrorOutOfMemory) { set_error("out of device memory allocating the L-BFGS state (%zu bytes)", bytes); (void)hipGetLastError(); return DZO_ERR_NOMEM; }
+        return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+    };
+    const size_t ring_alloc = L.blocked ? L.ring_bytes : (L.interleaved ? 2 * L.slab_bytes : L.slab_bytes);
+    DZO_TRY(alloc(&o->S, ring_alloc));
+    if (L.blocked) {
+        DZO_TRY(alloc(&o->dx_lin, L.lin_bytes));
+        DZO_TRY(alloc(&o->dg_lin, L.lin_bytes));
+    } else if (L.interleaved) {
+        o->Y = (char *)o->S + L.lin_bytes;
     } else {
-        ALLOC(o->S, slab);
-        ALLOC(o->Y, slab);
-        o->pair_stride = o->stride;
+        DZO_TRY(alloc(&o->Y, L.slab_bytes));
     }
-    ALLOC(o->d_alloc, (size_t)o->stride * es + 4096);
-    o->d = (char *)o->d_alloc + 3 * 1024;             // off the allocator's alignment grid (see xbak / gbak)
-    o->gram_u = tune("DZO_TUNE_GRAM_U", 4);
-    o->fused_finish = tune("DZO_TUNE_FUSED_FINISH", 0) != 0;
-    o->fused_finish_max = tune("DZO_TUNE_FUSED_FINISH_MAX", 65536);
-    o->speculate = tune("DZO_TUNE_SPECULATE", 1) != 0;
-    o->gram_variant = tune("DZO_TUNE_GRAM_VARIANT", 1);
-    o->gram_peel = tune("DZO_TUNE_GRAM_PEEL", 1);
-    o->gram_fresh_plain = tune("DZO_TUNE_GRAM_FRESH_PLAIN", 1);
-    o->gram_skip0 = tune("DZO_TUNE_GRAM_SKIP0", 1);
-    o->combine_fresh_plain = tune("DZO_TUNE_COMBINE_FRESH_PLAIN", 1);
-    o->single_pass = tune("DZO_TUNE_SINGLE_PASS", 1) != 0;
-    o->fused_post = tune("DZO_TUNE_FUSED_POST", 1) != 0;
-    o->combine_nts = tune("DZO_TUNE_COMBINE_NTS", 1) != 0;
-    o->combine_u = tune("DZO_TUNE_COMBINE_U", 4);
-    o->combine_blocks_per_cu = tune("DZO_TUNE_COMBINE_BPC", 0);   // 0: resident blocks
-    o->gram_bpc = tune("DZO_TUNE_GRAM_BPC", 0);                 // 0: as many blocks as are resident at once
-    o->gram_grid = ctx().cus * (o->gram_bpc > 0 ? o->gram_bpc : 8);   // upper bound (sizes the partials)
-    if (o->gram_grid > kMaxPartialBlocks) o->gram_grid = kMaxPartialBlocks;
-    {
-        const int64_t tile_v = 64 * (int64_t)o->gram_u;
-        const int64_t tiles = (n / (16 / (int64_t)es) + tile_v - 1) / tile_v;
-        if (tiles < o->gram_grid) o->gram_grid = (int)(tiles > 0 ? tiles : 1);
-    }
-    const size_t nscal = 2 + 2 + 2 * ((size_t)m1 + 2) + (size_t)m1 + 3 * kMaxHistory + 8 + 2 * (size_t)m1 * m1 + 2 * kMaxHistory + (2 * kMaxHistory + 8) +
-                         (size_t)kGramValues * kMaxHistory * (o->gram_grid * kWaves + 1) + 4 * (size_t)kMaxPartialBlocks;
+    DZO_TRY(alloc(&o->d_alloc, L.d_bytes));
+    o->d = (char *)o->d_alloc + L.d_offset;             // off the allocator's alignment grid (see xbak / gbak)
     double *base = nullptr;
-    ALLOC(base, nscal * sizeof(double));
-#undef ALLOC
-    (void)hipMemset(base, 0, nscal * sizeof(double));
+    DZO_TRY(alloc((void **)&base, L.scal.total * sizeof(double)));
+    (void)hipMemset(base, 0, L.scal.total * sizeof(double));
     (void)hipDeviceSynchronize();
-    o->gram_ticket = reinterpret_cast<unsigned int *>(base); base += 2;   // (zeroed with the rest; re-armed by the kernel)
-    o->xg_differs = reinterpret_cast<int32_t *>(base); base += 2;
-    o->pscal = base; base += 2 * ((size_t)m1 + 2);
-    o->rho = base; base += m1;
-    o->alpha = base; base += kMaxHistory;
-    o->coef = base; base += kMaxHistory;
-    o->scale = base; base += 8;
-    o->alpha_sp = base; base += kMaxHistory;
-    o->coef_sp = base; base += kMaxHistory;
-    o->scale_sp = base; base += 8;
-    o->Gyy = base; base += (size_t)m1 * m1;
-    o->Gsy = base; base += (size_t)m1 * m1;
-    o->sg = base; base += kMaxHistory;
-    o->yg = base; base += kMaxHistory;
-    o->gram_partials = base; base += (size_t)kGramValues * kMaxHistory * (o->gram_grid * kWaves + 1);
-    o->link_partials = base;
+    o->gram_ticket = reinterpret_cast<unsigned int *>(base + L.scal.off[kScalGramTicket]);   // (the base of the block: destroy frees it)
+    o->xg_differs = reinterpret_cast<int32_t *>(base + L.scal.off[kScalXgDiffers]);
+    o->pscal = base + L.scal.off[kScalPscal];
+    o->rho = base + L.scal.off[kScalRho];
+    o->alpha = base + L.scal.off[kScalAlpha]; o->coef = base + L.scal.off[kScalCoef]; o->scale = base + L.scal.off[kScalScale];
+    o->alpha_sp = base + L.scal.off[kScalAlphaSp]; o->coef_sp = base + L.scal.off[kScalCoefSp]; o->scale_sp = base + L.scal.off[kScalScaleSp];
+    o->Gyy = base + L.scal.off[kScalGyy]; o->Gsy = base + L.scal.off[kScalGsy];
+    o->sg = base + L.scal.off[kScalSg]; o->yg = base + L.scal.off[kScalYg];
+    o->gram_partials = base + L.scal.off[kScalGramPartials];
+    o->link_partials = base + L.scal.off[kScalLinkPartials];
     // (from here on a failure must give the state back: the ring alone is gigabytes)
     auto finish = [&]() -> int32_t {
         // :366-374 zero-filled deltas: the whole ring starts zeroed
-        if (o->blocked) {
-            DZO_HIP(hipMemsetAsync(o->S, 0, o->ring_bytes, c.stream));
-            DZO_HIP(hipMemsetAsync(o->dx_lin, 0, (size_t)o->stride * es, c.stream));
-            DZO_HIP(hipMemsetAsync(o->dg_lin, 0, (size_t)o->stride * es, c.stream));
-        } else if (o->interleaved) {
-            DZO_HIP(hipMemsetAsync(o->S, 0, 2 * slab, c.stream));
-        } else {
-            DZO_HIP(hipMemsetAsync(o->S, 0, slab, c.stream));
-            DZO_HIP(hipMemsetAsync(o->Y, 0, slab, c.stream));
+        DZO_HIP(hipMemsetAsync(o->S, 0, ring_alloc, c.stream));
+        if (L.blocked) {
+            DZO_HIP(hipMemsetAsync(o->dx_lin, 0, L.lin_bytes, c.stream));
+            DZO_HIP(hipMemsetAsync(o->dg_lin, 0, L.lin_bytes, c.stream));
+        } else if (!L.interleaved) {
+            DZO_HIP(hipMemsetAsync(o->Y, 0, L.slab_bytes, c.stream));
         }
         o->k = 0; o->newest = o->nslots - 1;   // spare() == 0
         o->refresh_delta_ptrs();
-        DZO_HIP(hipMemsetAsync(o->d_alloc, 0, (size_t)o->stride * es + 4096, c.stream));   // (the padding behind element n: +0, the first pass reads whole vectors)
-        if (o->blocked && tune("DZO_TUNE_POINT_RING", 1) != 0) {
+        DZO_HIP(hipMemsetAsync(o->d_alloc, 0, L.d_bytes, c.stream));   // (the padding behind element n: +0, the first pass reads whole vectors)
+        if (L.points) {
             // point ring: the start point and its gradient are point 0
             o->points = true;
-            o->lazy_d = tune("DZO_TUNE_LAZY_D", 1) != 0;
-            o->point_sets = tune("DZO_TUNE_POINT_SETS", 1) == 1 ? 1 : 2;
+            o->lazy_d = L.lazy_d;
+            o->point_sets = L.point_sets;
             o->xg_host_may_write = true;                      // (the caller owns x0 / g0 and may change them before the first step)
             DZO_DISPATCH(dtype, (ring_scatter<T>(o, x_dev, o->s_slot_v(o->newest)), ring_scatter<T>(o, g_dev, o->y_slot_v(o->newest))));
             o->g_valid = 1u << o->newest;
@@ -4010,7 +3905,7 @@ int32_t dzo_lbfgs_create(int64_t n, int32_t history_length, int32_t dtype, void 
         gnorm = dtype == DZO_F32 ? (double)sqrtf((float)gnorm) : sqrt(gnorm);
         c.is_stuck = (gnorm == 0.0);                          // :382 iszero
         if (c.is_stuck) {
-            DZO_HIP(hipMemsetAsync(o->d, 0, (size_t)o->stride * es, c.stream));   // :384
+            DZO_HIP(hipMemsetAsync(o->d, 0, L.lin_bytes, c.stream));   // :384
         } else {
             const double sc = round_to_dtype(dtype, -initial_step_length / gnorm);
             DZO_DISPATCH(dtype, launch_scal_oop<T>(c.stream, n, (T *)o->d, (T)sc, (const T *)g_dev));  // :386-387
@@ -4022,6 +3917,14 @@ int32_t dzo_lbfgs_create(int64_t n, int32_t history_length, int32_t dtype, void 
     if (rc != DZO_OK) { o->x_user = nullptr; dzo_lbfgs_destroy(o); return rc; }   // (x_user cleared: nothing to settle)
     *out = o;
     return DZO_OK;
+}
+
+// ============================================================================ C ABI
+extern "C" {
+
+int32_t dzo_lbfgs_create(int64_t n, int32_t history_length, int32_t dtype, void *x_dev, void *g_dev,
+                         double initial_objective_value, double initial_step_length, dzo_lbfgs_t *out) {
+    return lbfgs_construct(n, history_length, dtype, x_dev, g_dev, initial_objective_value, initial_step_length, LbfgsStart(), out);
 }
 
 int32_t dzo_lbfgs_destroy(dzo_lbfgs_t o) {
@@ -4076,16 +3979,11 @@ int32_t dzo_lbfgs_create_problem(dzo_problem_t problem, int32_t history_length, 
     void *g = nullptr;
     DZO_HIP(hipMalloc(&g, (size_t)((problem->n + 63) / 64 * 64) * dtype_size(problem->dtype)));
     int32_t rc = dzo_problem_grad(problem, g, x_dev);     // :421
-    // the single-pass step will apply (built-in chained Rosenbrock, no decorators): tile-major history ring
-    const bool lse_points = problem->kind == DZO_PROBLEM_LSE && !ring_decor_of(problem).any() && ((uintptr_t)problem->c & 15u) == 0 &&
-                            tune("DZO_TUNE_LSE_POINTS", 1) != 0;
-    tl_want_blocked = (problem->kind == DZO_PROBLEM_ROSENBROCK_CHAIN ||
-                       (problem->kind == DZO_PROBLEM_QUADRATIC_CHAIN && !ring_decor_of(problem).any()) || lse_points) && (((uintptr_t)x_dev | (uintptr_t)g) & 15u) == 0;
-    tl_ring_dec = ring_decor_of(problem);
-    tl_ring_obj = ring_obj_of(problem) >= 1 ? ring_obj_of(problem) : 0; tl_ring_obj_lambda = problem->lambda;
-    if (rc == DZO_OK) rc = dzo_lbfgs_create(problem->n, history_length, problem->dtype, x_dev, g, f0, initial_step_length, out);
-    tl_want_blocked = false;
-    tl_ring_dec = RingDecor(); tl_ring_obj = 0; tl_ring_obj_lambda = 0;
+    // what the constructor needs to know of the problem (whether the pass will apply is lbfgs_plan_layout's decision)
+    LbfgsStart start;
+    start.kind = problem->kind; start.dec = ring_decor_of(problem); start.lambda = problem->lambda;
+    start.x_al16 = al16(x_dev); start.g_al16 = al16(g); start.c_al16 = al16(problem->c);
+    if (rc == DZO_OK) rc = lbfgs_construct(problem->n, history_length, problem->dtype, x_dev, g, f0, initial_step_length, start, out);
     if (rc != DZO_OK) { (void)hipFree(g); return rc; }
     (*out)->core.owns_g = true;
     if ((*out)->ring_obj == 2 && (*out)->points) {
@@ -4232,7 +4130,7 @@ int32_t dzo_lbfgs_get_i(dzo_lbfgs_t o, int32_t what, int64_t *value) {
     case 15: *value = o->blocked ? (o->tile_stride == kTileBytes ? 1 : 2) : 0; break;   // arrangement of the tiles: 1 tile-major, 2 stream-major
     case 16: *value = (o->points && DZO_PP_REGRAD != 0) ? 1 : 0; break;   // point pass: 1 = the points' gradients are recomputed from the point tiles, not streamed
     case 18: *value = o->host_write_checks; break;        // steps that first compared the aliased arrays with the point ring (after a pointer hand-out)
-    case 17: { int sets = 0; if (o->points) { DZO_DISPATCH(o->core.dtype, sets = point_one_set<T>(o) ? 1 : 2); } *value = sets; break; }   // register sets per wave of the point pass
+    case 17: { int sets = 0; if (o->points) { sets = point_one_set(o->m, o->core.dtype, o->point_sets) ? 1 : 2; } *value = sets; break; }   // register sets per wave of the point pass
     default: set_error("dzo_lbfgs_get_i: unknown field %d", what); return DZO_ERR_INVALID;
     }
     return DZO_OK;
