@@ -1175,6 +1175,7 @@ class BFGSOptimizer(_OptBase):
     objective_evaluations = property(lambda s: s._i(4))
     last_step_length = property(lambda s: s._s(1))
     next_step_direction = property(lambda s: s._p(4))
+    scratch = property(lambda s: s._p(6))                # legacy :748; after a BFGS step it holds t = H * delta_gradient (:875)
 
     @property
     def approximate_inverse_hessian(self):
