@@ -192,6 +192,10 @@ ABI = {
     "dzo_lbfgs_batch_set_max_halvings": [_vp, _i64], "dzo_lbfgs_batch_step": [_vp, _i32, _P(_i32)],
     "dzo_lbfgs_batch_count_active": [_vp, _P(_i64)], "dzo_lbfgs_batch_get_ptr": [_vp, _i32, _P(_vp)],
     "dzo_lbfgs_batch_read": [_vp, _i32, _vp], "dzo_pairwise_batch_energy_gradient": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
+    "dzo_adgd_batch_create": [_i32, _i64, _i64, _i32, _vp, _dbl, _P(_vp)], "dzo_adgd_batch_destroy": [_vp],
+    "dzo_adgd_batch_set_max_halvings": [_vp, _i64], "dzo_adgd_batch_step": [_vp, _i32, _P(_i32)],
+    "dzo_adgd_batch_count_active": [_vp, _P(_i64)], "dzo_adgd_batch_get_ptr": [_vp, _i32, _P(_vp)],
+    "dzo_adgd_batch_read": [_vp, _i32, _vp],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -583,14 +587,19 @@ class ParallelTempering(_HandleArrays):
     num_accept = property(lambda self: self.read(TEMPERING_NUM_ACCEPT))
     num_reject = property(lambda self: self.read(TEMPERING_NUM_REJECT))
 
-    def quench(self, history_length=10, initial_step_length=0.01, steps_per_launch=50, max_steps=2000):
+    def quench(self, history_length=10, initial_step_length=0.01, steps_per_launch=50, max_steps=2000, optimizer="lbfgs"):
         """The inherent structures of the replicas: a device-to-device COPY of the replica array is quenched by a
         ``BatchedLBFGS`` (``steps_per_launch`` calls of ``step!()`` per launch until every instance is stuck, at most
-        ``max_steps`` per instance).  Returns ``(energies, copy, optimizer)``: the minima's energies (host array), the
+        ``max_steps`` per instance).  ``optimizer="adgd"`` quenches the copy with a ``BatchedAdGD`` instead
+        (``history_length`` is ignored).  Returns ``(energies, copy, optimizer)``: the minima's energies (host array), the
         DeviceArray that holds them, and the handle (its ``is_stuck`` tells which instances finished).  The Markov chain's
         own array is not touched."""
+        assert optimizer in ("lbfgs", "adgd"), "optimizer must be 'lbfgs' or 'adgd'"
         minima = self.replicas.copy()
-        opt = BatchedLBFGS(minima, self.n_particles, initial_step_length, history_length)
+        if optimizer == "adgd":
+            opt = BatchedAdGD(minima, self.n_particles, initial_step_length)
+        else:
+            opt = BatchedLBFGS(minima, self.n_particles, initial_step_length, history_length)
         done, taken = opt.count_active() == 0, 0
         while not done and taken < max_steps:
             k = min(int(steps_per_launch), int(max_steps) - taken)
@@ -690,6 +699,82 @@ class BatchedLBFGS(_HandleArrays):
     iteration_counts = property(lambda self: self.read(LBFGS_BATCH_ITERATION_COUNTS))
     history_counts = property(lambda self: self.read(LBFGS_BATCH_HISTORY_COUNTS))
     last_halvings = property(lambda self: self.read(LBFGS_BATCH_LAST_HALVINGS))
+
+
+# ------------------------------------------------------------------------------ batched AdGD over Lennard-Jones clusters
+ADGD_BATCH_MAX_PARTICLES = 1024
+(ADGD_BATCH_POINTS, ADGD_BATCH_GRADIENTS, ADGD_BATCH_DELTA_POINTS, ADGD_BATCH_DELTA_GRADIENTS, ADGD_BATCH_OBJECTIVES,
+ ADGD_BATCH_DELTA_OBJECTIVES, ADGD_BATCH_IS_STUCK, ADGD_BATCH_ITERATION_COUNTS, ADGD_BATCH_CURRENT_STEP_SIZES,
+ ADGD_BATCH_PREVIOUS_STEP_SIZES, ADGD_BATCH_LAST_HALVINGS) = range(11)
+
+
+class BatchedAdGD(_HandleArrays):
+    """``AdGDOptimizer`` (src/DZOptimization.jl:179-312, no constraint) of many small Lennard-Jones clusters at once:
+    ``step(k)`` runs k calls of ``step!()`` of every instance in ONE launch.  ``points`` is a DeviceArray of
+    ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
+    ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
+    _read_fn, _ptr_fn = "dzo_adgd_batch_read", "dzo_adgd_batch_get_ptr"
+
+    def __init__(self, points, n_particles, initial_step_length, radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.points = points
+        self.dtype = points.dtype
+        self.n_particles = int(n_particles)
+        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
+        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        h = C.c_void_p()
+        _check(lib().dzo_adgd_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, float(initial_step_length),
+                                           C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            lib().dzo_adgd_batch_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_max_halvings(self, v):
+        _check(lib().dzo_adgd_batch_set_max_halvings(self.h, int(v)))
+
+    def step(self, steps=1, wait=True):
+        """``steps`` calls of ``step!()`` of every instance that is not stuck.  ``wait=True``: blocks and returns whether all
+        instances are stuck; ``wait=False``: enqueues only and returns None."""
+        if not wait:
+            _check(lib().dzo_adgd_batch_step(self.h, int(steps), None))
+            return None
+        flag = C.c_int32(0)
+        _check(lib().dzo_adgd_batch_step(self.h, int(steps), C.byref(flag)))
+        return bool(flag.value)
+
+    def count_active(self):
+        n = C.c_int64(0)
+        _check(lib().dzo_adgd_batch_count_active(self.h, C.byref(n)))
+        return int(n.value)
+
+    def _shape(self, what):
+        b, n3 = self.batch, 3 * self.n_particles
+        vec, sc = ((b, n3), self.dtype), ((b,), self.dtype)
+        return {ADGD_BATCH_POINTS: vec, ADGD_BATCH_GRADIENTS: vec, ADGD_BATCH_DELTA_POINTS: vec, ADGD_BATCH_DELTA_GRADIENTS: vec,
+                ADGD_BATCH_OBJECTIVES: sc, ADGD_BATCH_DELTA_OBJECTIVES: sc, ADGD_BATCH_IS_STUCK: ((b,), np.int32),
+                ADGD_BATCH_ITERATION_COUNTS: ((b,), np.int64), ADGD_BATCH_CURRENT_STEP_SIZES: sc,
+                ADGD_BATCH_PREVIOUS_STEP_SIZES: sc, ADGD_BATCH_LAST_HALVINGS: ((b,), np.int32)}[what]
+
+    current_points = property(lambda self: self.read(ADGD_BATCH_POINTS))
+    current_gradients = property(lambda self: self.read(ADGD_BATCH_GRADIENTS))
+    delta_points = property(lambda self: self.read(ADGD_BATCH_DELTA_POINTS))
+    delta_gradients = property(lambda self: self.read(ADGD_BATCH_DELTA_GRADIENTS))
+    current_objective_values = property(lambda self: self.read(ADGD_BATCH_OBJECTIVES))
+    delta_objective_values = property(lambda self: self.read(ADGD_BATCH_DELTA_OBJECTIVES))
+    is_stuck = property(lambda self: self.read(ADGD_BATCH_IS_STUCK).astype(bool))
+    iteration_counts = property(lambda self: self.read(ADGD_BATCH_ITERATION_COUNTS))
+    current_step_sizes = property(lambda self: self.read(ADGD_BATCH_CURRENT_STEP_SIZES))
+    previous_step_sizes = property(lambda self: self.read(ADGD_BATCH_PREVIOUS_STEP_SIZES))
+    last_halvings = property(lambda self: self.read(ADGD_BATCH_LAST_HALVINGS))
 
 
 # ------------------------------------------------------------------------------ profiling

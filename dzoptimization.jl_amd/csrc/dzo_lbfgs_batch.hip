@@ -282,6 +282,14 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void quen
     if (tid == 0) a.stuck[b] = stuck ? 1 : 0;
 }
 
+// the body for every particle i the thread owns (thread t owns the particles t + 256 q; `tid` and `N` are the caller's): every
+// element of a vector in LDS is touched by its owner only
+#define DZO_Q_OWN(i, ...)                                   \
+    _Pragma("unroll") for (int q = 0; q < kQuenchPer; ++q) { \
+        const int i = tid + kBlock * q;                     \
+        if (i < N) { __VA_ARGS__ }                          \
+    }
+
 // HL: the history ring is in LDS (else in a.slab)
 template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void quench_block_step_kernel(QuenchArgs<T> a) {
     const int64_t b = blockIdx.x;
@@ -303,12 +311,6 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
     int hc = *ghc_, halv = *ghalv_, head = 0, par = 0;
     int64_t it = *git_;
     T E = *gf_, dE = *gdf_;
-    // every element below is touched by its owner only: thread t owns the particles t + 256 q
-#define DZO_Q_OWN(i, ...)                                   \
-    _Pragma("unroll") for (int q = 0; q < kQuenchPer; ++q) { \
-        const int i = tid + kBlock * q;                     \
-        if (i < N) { __VA_ARGS__ }                          \
-    }
     DZO_Q_OWN(i, for (int c = 0; c < 3; ++c) {
         const int e = c * N + i;
         X[e] = gx_[e]; G[e] = gg_[e]; D[e] = gd_[e]; DX[e] = gdx_[e]; DG[e] = gdg_[e];
@@ -404,7 +406,6 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
             gY_[(int64_t)n3 * k + e] = hY[p * n3 + e];
         }
     })
-#undef DZO_Q_OWN
     if (tid < hc) grho_[tid] = rho[head + tid < m ? head + tid : head + tid - m];
     if (tid == 0) {
         *gf_ = E; *gdf_ = dE;
@@ -490,7 +491,8 @@ template <typename T> static void qb_launch_step(hipStream_t s, const dzo_lbfgs_
     else hipLaunchKernelGGL((quench_block_step_kernel<T, LJRadial<T>, false>), grid, dim3(kBlock), h->lds_bytes, s, a);
 }
 
-static int32_t qb_count(dzo_lbfgs_batch_s *h, hipStream_t s, int64_t *active) {
+// H: either batched handle (B, stuck, active_dev, active_host)
+template <typename H> static int32_t qb_count(H *h, hipStream_t s, int64_t *active) {
     hipLaunchKernelGGL(quench_count_active_kernel, dim3(1), dim3(kBlock), 0, s, h->B, (const int32_t *)h->stuck, h->active_dev);
     DZO_HIP(hipGetLastError());
     DZO_HIP(hipMemcpyAsync(h->active_host, h->active_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -661,6 +663,400 @@ int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, 
     }
     DZO_HIP(hipStreamSynchronize(c.stream));
     return DZO_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================================
+// Batched AdGDOptimizer (src/DZOptimization.jl:179-312, constraint_function! = nothing) over the same clusters: dzo_adgd_batch_*.
+//
+// The second live optimizer on the launch shapes above.  It keeps no history, so an instance is four vectors (point, gradient,
+// delta_point, delta_gradient), two step sizes and a few scalars.  The trial's energy and gradient come from q_wave_eval /
+// q_block_eval, the block sums from q_block_sum_all, the sums of squares from q_dot3: one definition with the quench, the same
+// bits.  The step-size rule (:285-299) is evaluated in T, operation by operation as adgd_next_state of dzo_adgd.hip does.
+//
+//   * WAVE (N <= 64): point, gradient, both deltas, the trial and its gradient are registers; no LDS beyond the sums'.
+//   * BLOCK (65 <= N <= 1024): dynamic LDS red[2 kWaves] | X | G | DX | DG | XT (the trial point, which the pair loop reads as
+//     a broadcast); the trial gradient in registers.  5 * 3N elements: 120 KiB at N = 1024 in fp64.
+// ================================================================================================================
+namespace dzo {
+
+constexpr int kAdgdBatchMaxN = DZO_ADGD_BATCH_MAX_PARTICLES;
+static_assert(kAdgdBatchMaxN == kQuenchMaxN, "the batched AdGD kernels use the quench's evaluation routines and their particle bound");
+
+template <typename T> struct AdgdBatchArgs {
+    int N, steps;
+    int64_t max_halvings;
+    T step_length;
+    T *x, *g, *dx, *dg;        // (3N, batch)
+    T *f, *df, *cur, *prev;    // batch
+    int32_t *stuck, *halv;
+    int64_t *iters;
+};
+
+__device__ __forceinline__ double ab_sqrt(double v) { return ::sqrt(v); }
+__device__ __forceinline__ float ab_sqrt(float v) { return ::sqrtf(v); }
+
+// next_step_size of :290-295 from the sums of squares of delta_point and delta_gradient (fp64); every operation in T
+template <typename T> __device__ __forceinline__ T ab_next_step_size(T current, T previous, double dx2, double dg2) {
+    const T theta = current / previous;                      // :290
+    T next = current * ab_sqrt(T(1) + theta);                // :291
+    const T dgn = ab_sqrt((T)dg2);                           // :292
+    if (dgn != T(0)) {                                       // :293
+        const T inv_L = ab_sqrt((T)dx2) / dgn;               // :294
+        const T cap = ab_sqrt(T(0.5)) * inv_L;
+        next = next < cap ? next : cap;                      // :295
+    }
+    return next;
+}
+
+// the rest of the constructor (:229-241) behind the evaluation kernel, which left f0 and g0: grid batch, block 256
+template <typename T> __global__ __launch_bounds__(kBlock) void adgd_batch_init_kernel(AdgdBatchArgs<T> a) {
+    __shared__ double red[2 * kWaves];
+    const int tid = threadIdx.x, N = a.N;
+    const int64_t b = blockIdx.x, base = (int64_t)3 * N * b;
+    double part = 0;
+    for (int i = tid; i < N; i += kBlock) {
+        const T gx = a.g[base + i], gy = a.g[base + N + i], gz = a.g[base + 2 * N + i];
+        part += q_dot3(gx, gy, gz, gx, gy, gz);
+    }
+    int par = 0;
+    const double ss = q_block_sum_all(part, red, par);       // :230
+    if (tid == 0) {
+        const bool stuck = ss == 0.0;                        // :231
+        const T s0 = stuck ? T(0) : a.step_length / (T)::sqrt(ss);   // :232-233
+        a.cur[b] = s0; a.prev[b] = s0;                       // :241
+        a.stuck[b] = stuck ? 1 : 0;
+    }
+}
+
+template <typename T, typename F> __global__ __launch_bounds__(64) void adgd_batch_wave_step_kernel(AdgdBatchArgs<T> a) {
+    const int64_t b = blockIdx.x;
+    if (a.stuck[b]) return;                                  // :276, the whole wave
+    const int lane = threadIdx.x, N = a.N;
+    const int64_t base = (int64_t)3 * N * b;
+    const bool live = lane < N;
+    auto ld = [&](const T *p, int c) { return live ? p[base + c * N + lane] : T(0); };
+    T x = ld(a.x, 0), y = ld(a.x, 1), z = ld(a.x, 2);
+    T gx = ld(a.g, 0), gy = ld(a.g, 1), gz = ld(a.g, 2);
+    T sx = ld(a.dx, 0), sy = ld(a.dx, 1), sz = ld(a.dx, 2);
+    T yx = ld(a.dg, 0), yy = ld(a.dg, 1), yz = ld(a.dg, 2);
+    T E = a.f[b], dE = a.df[b], cur = a.cur[b], prev = a.prev[b];
+    int64_t it = a.iters[b];
+    int halv = a.halv[b];
+    bool stuck = false;
+    for (int s = 0; s < a.steps && !stuck; ++s) {
+        T next = cur;                                        // :287
+        if (it > 0) {                                        // :288
+            const double dg2 = wave_sum_all(q_dot3(yx, yy, yz, yx, yy, yz));
+            const double dx2 = wave_sum_all(q_dot3(sx, sy, sz, sx, sy, sz));
+            next = ab_next_step_size<T>(cur, prev, dx2, dg2);
+        }
+        prev = cur; cur = next;                              // :298-299
+        // take_backtracking_step!(opt, -next, current_gradient), :107-154
+        const T x0 = x, y0 = y, z0 = z;                      // :118
+        T t = next;
+        int h = 0;
+        for (;;) {
+            const T xt = dfma<T>(-t, gx, x0), yt = dfma<T>(-t, gy, y0), zt = dfma<T>(-t, gz, z0);   // :124
+            if (__all(is_equal(xt, x0) && is_equal(yt, y0) && is_equal(zt, z0))) { stuck = true; break; }   // :128
+            T Et, tx, ty, tz;
+            q_wave_eval<T, F>(N, lane, xt, yt, zt, Et, tx, ty, tz);
+            if (Et < E) {                                    // :139
+                dE = Et - E; E = Et;                         // :142-144
+                sx = xt - x0; sy = yt - y0; sz = zt - z0;    // :145
+                yx = tx - gx; yy = ty - gy; yz = tz - gz;    // :306-308
+                x = xt; y = yt; z = zt;
+                gx = tx; gy = ty; gz = tz;
+                break;
+            }
+            t *= T(0.5);                                     // :152 (the point was never overwritten: :151)
+            if (++h >= a.max_halvings) { stuck = true; break; }
+        }
+        halv = h;
+        if (stuck) { sx = x0; sy = y0; sz = z0; break; }     // delta_point keeps the copy of :118
+        ++it;                                                // :310
+    }
+    if (live) {
+        auto st = [&](T *p, int c, T v) { p[base + c * N + lane] = v; };
+        st(a.x, 0, x); st(a.x, 1, y); st(a.x, 2, z);
+        st(a.g, 0, gx); st(a.g, 1, gy); st(a.g, 2, gz);
+        st(a.dx, 0, sx); st(a.dx, 1, sy); st(a.dx, 2, sz);
+        st(a.dg, 0, yx); st(a.dg, 1, yy); st(a.dg, 2, yz);
+    }
+    if (lane == 0) {
+        a.f[b] = E; a.df[b] = dE;
+        a.cur[b] = cur; a.prev[b] = prev;
+        a.stuck[b] = stuck ? 1 : 0;
+        a.iters[b] = it;
+        a.halv[b] = halv;
+    }
+}
+
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void adgd_batch_block_step_kernel(AdgdBatchArgs<T> a) {
+    const int64_t b = blockIdx.x;
+    if (a.stuck[b]) return;                                  // the whole block
+    const int tid = threadIdx.x, N = a.N, n3 = 3 * N;
+    const int64_t base = (int64_t)n3 * b;
+    // LDS: red[2 kWaves] | X | G | DX | DG | XT
+    double *red = quench_smem;
+    T *X = reinterpret_cast<T *>(red + 2 * kWaves), *G = X + n3, *DX = G + n3, *DG = DX + n3, *XT = DG + n3;
+    T *const gx_ = pw_pin_ptr(a.x + base), *const gg_ = pw_pin_ptr(a.g + base), *const gdx_ = pw_pin_ptr(a.dx + base);
+    T *const gdg_ = pw_pin_ptr(a.dg + base), *const gf_ = pw_pin_ptr(a.f + b), *const gdf_ = pw_pin_ptr(a.df + b);
+    T *const gcur_ = pw_pin_ptr(a.cur + b), *const gprev_ = pw_pin_ptr(a.prev + b);
+    int32_t *const gstuck_ = pw_pin_ptr(a.stuck + b), *const ghalv_ = pw_pin_ptr(a.halv + b);
+    int64_t *const git_ = pw_pin_ptr(a.iters + b);
+    int halv = *ghalv_, par = 0;
+    int64_t it = *git_;
+    T E = *gf_, dE = *gdf_, cur = *gcur_, prev = *gprev_;
+    DZO_Q_OWN(i, for (int c = 0; c < 3; ++c) {
+        const int e = c * N + i;
+        X[e] = gx_[e]; G[e] = gg_[e]; DX[e] = gdx_[e]; DG[e] = gdg_[e];
+    })
+    bool stuck = false;
+    for (int s = 0; s < a.steps && !stuck; ++s) {
+        T next = cur;                                        // :287
+        if (it > 0) {                                        // :288
+            double pg = 0, px = 0;
+            DZO_Q_OWN(i, pg += q_dot3(DG[i], DG[N + i], DG[2 * N + i], DG[i], DG[N + i], DG[2 * N + i]);
+                      px += q_dot3(DX[i], DX[N + i], DX[2 * N + i], DX[i], DX[N + i], DX[2 * N + i]);)
+            const double dg2 = q_block_sum_all(pg, red, par);
+            const double dx2 = q_block_sum_all(px, red, par);
+            next = ab_next_step_size<T>(cur, prev, dx2, dg2);
+        }
+        prev = cur; cur = next;                              // :298-299
+        // take_backtracking_step!(opt, -next, current_gradient), :107-154: X keeps the old point, XT is the trial (:124)
+        T t = next;
+        int h = 0;
+        bool accepted = false;
+        T tx[kQuenchPer], ty[kQuenchPer], tz[kQuenchPer];
+        for (;;) {
+            bool same = true;
+            DZO_Q_OWN(i, for (int c = 0; c < 3; ++c) {
+                const T v = dfma<T>(-t, G[c * N + i], X[c * N + i]);
+                XT[c * N + i] = v;
+                same = same && is_equal(v, X[c * N + i]);
+            })
+            if (__syncthreads_and(same ? 1 : 0)) { stuck = true; break; }   // :128; the barrier also publishes the trial point
+            T Et;
+            q_block_eval<T, F>(N, tid, XT, red, par, Et, tx, ty, tz);      // its barrier: every thread has read XT
+            if (Et < E) { dE = Et - E; E = Et; accepted = true; break; }   // :139-144
+            t *= T(0.5);                                                    // :152
+            if (++h >= a.max_halvings) { stuck = true; break; }
+        }
+        halv = h;
+        if (!accepted) {                                     // delta_point keeps the copy of :118
+            DZO_Q_OWN(i, for (int c = 0; c < 3; ++c) DX[c * N + i] = X[c * N + i];)
+            break;
+        }
+#pragma unroll
+        for (int q = 0; q < kQuenchPer; ++q) {
+            const int i = tid + kBlock * q;
+            if (i < N) {
+                const T tg[3] = {tx[q], ty[q], tz[q]};
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int e = c * N + i;
+                    DX[e] = XT[e] - X[e]; DG[e] = tg[c] - G[e];   // :145, :306-308
+                    X[e] = XT[e]; G[e] = tg[c];
+                }
+            }
+        }
+        ++it;                                                // :310
+    }
+    DZO_Q_OWN(i, for (int c = 0; c < 3; ++c) {
+        const int e = c * N + i;
+        gx_[e] = X[e]; gg_[e] = G[e]; gdx_[e] = DX[e]; gdg_[e] = DG[e];
+    })
+    if (tid == 0) {
+        *gf_ = E; *gdf_ = dE;
+        *gcur_ = cur; *gprev_ = prev;
+        *gstuck_ = stuck ? 1 : 0;
+        *git_ = it;
+        *ghalv_ = halv;
+    }
+}
+
+}  // namespace dzo
+
+#undef DZO_Q_OWN
+
+struct dzo_adgd_batch_s {
+    int device = -1;
+    int32_t dtype = DZO_F64;
+    int N = 0;
+    int64_t B = 0, max_halvings = 4096;
+    void *x = nullptr;               // the caller's
+    void *g = nullptr, *dx = nullptr, *dg = nullptr, *f = nullptr, *df = nullptr, *cur = nullptr, *prev = nullptr;
+    int32_t *stuck = nullptr, *halv = nullptr;
+    int64_t *iters = nullptr, *active_dev = nullptr, *active_host = nullptr;
+    size_t lds_bytes = 0;            // BLOCK shape
+};
+
+namespace dzo {
+
+static void ab_free(dzo_adgd_batch_s *h) {
+    void *p[] = {h->g, h->dx, h->dg, h->f, h->df, h->cur, h->prev, h->stuck, h->halv, h->iters, h->active_dev};
+    for (void *q : p)
+        if (q) (void)hipFree(q);
+    if (h->active_host) (void)hipHostFree(h->active_host);
+    delete h;
+}
+
+static int32_t ab_alloc(void **p, size_t bytes) { return device_alloc(p, bytes, "the batched AdGD state", true); }
+
+template <typename T> static AdgdBatchArgs<T> ab_args(const dzo_adgd_batch_s *h, int steps, double step_length) {
+    AdgdBatchArgs<T> a;
+    a.N = h->N; a.steps = steps;
+    a.max_halvings = h->max_halvings;
+    a.step_length = (T)step_length;
+    a.x = (T *)h->x; a.g = (T *)h->g; a.dx = (T *)h->dx; a.dg = (T *)h->dg;
+    a.f = (T *)h->f; a.df = (T *)h->df; a.cur = (T *)h->cur; a.prev = (T *)h->prev;
+    a.stuck = h->stuck; a.halv = h->halv; a.iters = h->iters;
+    return a;
+}
+
+// f0 and g0 by the evaluation kernels of dzo_pairwise_batch_energy_gradient, then the step sizes and is_stuck
+template <typename T> static void ab_launch_init(hipStream_t s, const dzo_adgd_batch_s *h, double step_length) {
+    dzo_lbfgs_batch_s tmp;
+    tmp.N = h->N; tmp.m = 1; tmp.B = h->B;
+    tmp.x = h->x; tmp.f = h->f; tmp.g = h->g;
+    qb_launch_eval<T>(s, h->B, qb_args<T>(&tmp, 0, 0, 0.0));
+    hipLaunchKernelGGL((adgd_batch_init_kernel<T>), dim3((unsigned)h->B), dim3(kBlock), 0, s, ab_args<T>(h, 0, step_length));
+}
+
+template <typename T> static void ab_launch_step(hipStream_t s, const dzo_adgd_batch_s *h, int steps) {
+    const AdgdBatchArgs<T> a = ab_args<T>(h, steps, 0.0);
+    const dim3 grid((unsigned)h->B);
+    if (h->N <= 64) hipLaunchKernelGGL((adgd_batch_wave_step_kernel<T, LJRadial<T>>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((adgd_batch_block_step_kernel<T, LJRadial<T>>), grid, dim3(kBlock), h->lds_bytes, s, a);
+}
+
+// `what` -> device address, bytes
+static int32_t ab_array(dzo_adgd_batch_s *h, int32_t what, void **p, size_t *bytes) {
+    const size_t es = dtype_size(h->dtype), B = (size_t)h->B, n3 = 3 * (size_t)h->N;
+    switch (what) {
+    case DZO_ADGD_BATCH_POINTS: *p = h->x; *bytes = es * n3 * B; break;
+    case DZO_ADGD_BATCH_GRADIENTS: *p = h->g; *bytes = es * n3 * B; break;
+    case DZO_ADGD_BATCH_DELTA_POINTS: *p = h->dx; *bytes = es * n3 * B; break;
+    case DZO_ADGD_BATCH_DELTA_GRADIENTS: *p = h->dg; *bytes = es * n3 * B; break;
+    case DZO_ADGD_BATCH_OBJECTIVES: *p = h->f; *bytes = es * B; break;
+    case DZO_ADGD_BATCH_DELTA_OBJECTIVES: *p = h->df; *bytes = es * B; break;
+    case DZO_ADGD_BATCH_IS_STUCK: *p = h->stuck; *bytes = 4 * B; break;
+    case DZO_ADGD_BATCH_ITERATION_COUNTS: *p = h->iters; *bytes = 8 * B; break;
+    case DZO_ADGD_BATCH_CURRENT_STEP_SIZES: *p = h->cur; *bytes = es * B; break;
+    case DZO_ADGD_BATCH_PREVIOUS_STEP_SIZES: *p = h->prev; *bytes = es * B; break;
+    case DZO_ADGD_BATCH_LAST_HALVINGS: *p = h->halv; *bytes = 4 * B; break;
+    default: set_error("unknown batched AdGD array %d", what); return DZO_ERR_INVALID;
+    }
+    return DZO_OK;
+}
+
+}  // namespace dzo
+
+extern "C" {
+
+// AdGDOptimizer(constraint_function! = nothing, ...), src/DZOptimization.jl:245-271 and :201-242, per instance
+int32_t dzo_adgd_batch_create(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev, double initial_step_length,
+                              dzo_adgd_batch_t *out) {
+    DZO_TRY(require_init());
+    DZO_REQUIRE(out, DZO_ERR_INVALID, "null argument");
+    *out = nullptr;
+    DZO_REQUIRE(points_dev, DZO_ERR_INVALID, "null argument");
+    DZO_TRY(qb_check_common(radial, n_particles, batch, dtype));
+    DZO_REQUIRE(initial_step_length > 0, DZO_ERR_ASSERT, "AssertionError: initial_step_length > _zero (src/DZOptimization.jl:229)");
+    DZO_TRY(require_same_backend("AdGDOptimizer", "src/DZOptimization.jl:216-217", points_dev, "initial_point", nullptr, ""));
+    Context &c = ctx();
+    dzo_adgd_batch_s *h = new (std::nothrow) dzo_adgd_batch_s();
+    DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
+    h->device = c.device; h->dtype = dtype; h->N = (int)n_particles; h->B = batch; h->x = points_dev;
+    const size_t es = dtype_size(dtype), B = (size_t)batch, n3 = 3 * (size_t)n_particles;
+    if (n_particles > 64) h->lds_bytes = 16 * kWaves + 5 * n3 * es;
+    int32_t rc = DZO_OK;
+    if ((rc = ab_alloc(&h->g, es * n3 * B)) || (rc = ab_alloc(&h->dx, es * n3 * B)) || (rc = ab_alloc(&h->dg, es * n3 * B)) ||
+        (rc = ab_alloc(&h->f, es * B)) || (rc = ab_alloc(&h->df, es * B)) || (rc = ab_alloc(&h->cur, es * B)) || (rc = ab_alloc(&h->prev, es * B)) ||
+        (rc = ab_alloc((void **)&h->stuck, 4 * B)) || (rc = ab_alloc((void **)&h->halv, 4 * B)) || (rc = ab_alloc((void **)&h->iters, 8 * B)) ||
+        (rc = ab_alloc((void **)&h->active_dev, 8))) {
+        ab_free(h);
+        return rc;
+    }
+    hipError_t e = hipHostMalloc((void **)&h->active_host, sizeof(int64_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipDeviceSynchronize();          // the memsets above ran on the null stream
+    if (e == hipSuccess && h->lds_bytes > 48 * 1024) {
+        // as in dzo_lbfgs_batch_create: the attribute belongs to the kernel, so it is raised to the limit once and for all handles
+        const void *k = dtype == DZO_F64 ? (const void *)adgd_batch_block_step_kernel<double, LJRadial<double>>
+                                         : (const void *)adgd_batch_block_step_kernel<float, LJRadial<float>>;
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuenchLdsMax);
+    }
+    if (e != hipSuccess) { ab_free(h); return hip_fail(e, "batched AdGD state", __FILE__, __LINE__); }
+    {
+        DZO_TIMED("adgd_batch_init", c.stream);
+        DZO_DISPATCH(dtype, ab_launch_init<T>(c.stream, h, initial_step_length));
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { ab_free(h); return hip_fail(e, "batched AdGD constructor", __FILE__, __LINE__); }
+    *out = h;
+    return DZO_OK;
+}
+
+int32_t dzo_adgd_batch_destroy(dzo_adgd_batch_t h) {
+    if (!h) return DZO_OK;
+    DeviceScope scope(h->device);
+    (void)hipStreamSynchronize(ctx().stream);
+    ab_free(h);
+    return DZO_OK;
+}
+
+// the project's bounded-halvings escape of the loop of :121-153 (dzo_lbfgs_set_max_halvings); at least 1 here
+int32_t dzo_adgd_batch_set_max_halvings(dzo_adgd_batch_t h, int64_t max_halvings) {
+    DZO_REQUIRE(h, DZO_ERR_INVALID, "null handle");
+    DZO_REQUIRE(max_halvings >= 1, DZO_ERR_INVALID, "max_halvings must be at least 1 (got %lld): a launch cannot search without bound", (long long)max_halvings);
+    h->max_halvings = max_halvings;
+    return DZO_OK;
+}
+
+// step!(::AdGDOptimizer), src/DZOptimization.jl:274-312, `steps` times per instance
+int32_t dzo_adgd_batch_step(dzo_adgd_batch_t h, int32_t steps, int32_t *all_stuck) {
+    DZO_TRY(require_init());
+    DZO_REQUIRE(h, DZO_ERR_INVALID, "null handle");
+    DZO_REQUIRE(steps >= 0, DZO_ERR_INVALID, "steps must not be negative (got %d)", steps);
+    DeviceScope scope(h->device);
+    hipStream_t s = ctx().stream;
+    if (steps > 0) {
+        DZO_TIMED("adgd_batch_step", s);
+        DZO_DISPATCH(h->dtype, ab_launch_step<T>(s, h, steps));
+        DZO_HIP(hipGetLastError());
+    }
+    if (all_stuck) {
+        int64_t active = 0;
+        DZO_TRY(qb_count(h, s, &active));
+        *all_stuck = active == 0 ? 1 : 0;
+    }
+    return DZO_OK;
+}
+
+int32_t dzo_adgd_batch_count_active(dzo_adgd_batch_t h, int64_t *active) {
+    DZO_TRY(require_init());
+    DZO_REQUIRE(h && active, DZO_ERR_INVALID, "null argument");
+    DeviceScope scope(h->device);
+    return qb_count(h, ctx().stream, active);
+}
+
+int32_t dzo_adgd_batch_get_ptr(dzo_adgd_batch_t h, int32_t what, void **ptr_dev) {
+    DZO_REQUIRE(h && ptr_dev, DZO_ERR_INVALID, "null argument");
+    size_t bytes = 0;
+    return ab_array(h, what, ptr_dev, &bytes);
+}
+
+int32_t dzo_adgd_batch_read(dzo_adgd_batch_t h, int32_t what, void *out_host) {
+    DZO_TRY(require_init());
+    DZO_REQUIRE(h && out_host, DZO_ERR_INVALID, "null argument");
+    DeviceScope scope(h->device);
+    void *p = nullptr;
+    size_t bytes = 0;
+    DZO_TRY(ab_array(h, what, &p, &bytes));
+    return copy_blocking(out_host, p, bytes, hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        accelerated_pairwise_radial_energy, accelerated_pairwise_radial_gradient!, accelerated_pairwise_radial_hvp!,
        pairwise_radial_energy_delta,
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
-       BatchedLBFGSOptimizer, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!
+       BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -456,6 +456,76 @@ function quench(f::typeof(lj_energy), points::HipVector{T}, n_particles::Integer
         taken += k
     end
     return opt
+end
+
+################################################################################ batched AdGD over Lennard-Jones clusters
+# (not exercised in the build container either; the Python class BatchedAdGD binds the same entry points and IS tested)
+#
+# The live AdGDOptimizer (src/DZOptimization.jl:179-312, constraint_function! = nothing) of `batch` clusters at once, the
+# sibling of BatchedLBFGSOptimizer without a history: the same layout of `points`, aliased (:238).
+
+mutable struct BatchedAdGDOptimizer{T}
+    handle::Ptr{Cvoid}
+    points::HipVector{T}
+    n_particles::Int
+    batch::Int
+end
+
+"""`BatchedAdGDOptimizer(lj_energy, points, n_particles, initial_step_length)` (:245-271 per instance)."""
+function BatchedAdGDOptimizer(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, initial_step_length::Real) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_adgd_batch_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cdouble, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), h))
+    opt = BatchedAdGDOptimizer{T}(h[], points, n_particles, batch)
+    finalizer(opt) do w
+        w.handle != C_NULL && ccall((:dzo_adgd_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return opt
+end
+
+"""`step!(opt, steps; wait=true)`: `steps` calls of step!() (:274-312) of every instance that is not stuck, one launch.
+Returns whether every instance is stuck (`wait=true`, blocking) or `nothing` (enqueued only)."""
+function step!(opt::BatchedAdGDOptimizer, steps::Integer=1; wait::Bool=true)
+    if !wait
+        check(ccall((:dzo_adgd_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), opt.handle, steps, C_NULL))
+        return nothing
+    end
+    flag = Ref{Cint}(0)
+    check(ccall((:dzo_adgd_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), opt.handle, steps, flag))
+    return flag[] != 0
+end
+
+set_max_halvings!(opt::BatchedAdGDOptimizer, v::Integer) =
+    (check(ccall((:dzo_adgd_batch_set_max_halvings, libdzo), Cint, (Ptr{Cvoid}, Int64), opt.handle, v)); opt)
+
+function count_active(opt::BatchedAdGDOptimizer)
+    n = Ref{Int64}(0)
+    check(ccall((:dzo_adgd_batch_count_active, libdzo), Cint, (Ptr{Cvoid}, Ref{Int64}), opt.handle, n))
+    return Int(n[])
+end
+
+"""One of the per-instance arrays of element type `E` (a DZO_ADGD_BATCH_* constant of include/dzo.h with `batch` elements); blocks."""
+function read_per_instance(opt::BatchedAdGDOptimizer, what::Integer, ::Type{E}) where {E}
+    r = Vector{E}(undef, opt.batch)
+    check(ccall((:dzo_adgd_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, what, r))
+    return r
+end
+
+objective_values(opt::BatchedAdGDOptimizer{T}) where {T} = read_per_instance(opt, 4, T)     # DZO_ADGD_BATCH_OBJECTIVES
+iteration_counts(opt::BatchedAdGDOptimizer) = read_per_instance(opt, 7, Int64)             # DZO_ADGD_BATCH_ITERATION_COUNTS
+stuck_flags(opt::BatchedAdGDOptimizer) = read_per_instance(opt, 6, Int32) .!= 0            # DZO_ADGD_BATCH_IS_STUCK
+current_step_sizes(opt::BatchedAdGDOptimizer{T}) where {T} = read_per_instance(opt, 8, T)   # DZO_ADGD_BATCH_CURRENT_STEP_SIZES
+
+"""Device address of one of the DZO_ADGD_BATCH_* arrays of include/dzo.h (no wait)."""
+function array_pointer(opt::BatchedAdGDOptimizer, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_adgd_batch_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), opt.handle, what, p))
+    return p[]
 end
 
 # decorators of legacy/DZOptimization.jl:219-296, applied on the device

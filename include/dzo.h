@@ -397,6 +397,70 @@ int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, 
                                            const void *points_dev, void *energies_dev, void *gradients_dev);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched AdGDOptimizer over many small Lennard-Jones clusters (src/DZOptimization.jl:179-312 with constraint_function! =
+ * nothing, objective = the pairwise radial energy above): the sibling of dzo_lbfgs_batch_* without a history ring.  One
+ * launch runs `steps` calls of step!() (:274-312) of EVERY instance; nothing crosses the host between steps or trials.
+ * Layout, launch shapes (one wave per instance up to 64 particles, one 256-thread block up to
+ * DZO_ADGD_BATCH_MAX_PARTICLES), determinism, error codes and blocking rules are those of dzo_lbfgs_batch_*.
+ *
+ * Arithmetic, per instance (T = the element type).
+ * Constructor (:229-241): f0 and g0 by the routine of dzo_pairwise_batch_energy_gradient; ss = g0.g0 in fp64; is_stuck =
+ * (ss == 0); current_step_size = previous_step_size = is_stuck ? 0 : T(initial_step_length) / T(sqrt(ss)) (the norm rounded
+ * to T, the division in T); delta_point, delta_gradient and delta_objective zero, iteration_count 0.
+ * step!() (:274-312): a stuck instance does nothing.  With iteration_count > 0, every operation in T with IEEE division and
+ * square root: theta = current / previous; next = current sqrt(1 + theta); dgn = sqrt(T(sum delta_gradient^2 in fp64)); if
+ * dgn != 0: inv_L = sqrt(T(sum delta_point^2 in fp64)) / dgn and next = min(next, sqrt(T(1/2)) inv_L) -- the rule and the
+ * operation order of dzo_adgd_*.  Else next = current.  Then previous = current, current = next (:298-299): before the search,
+ * so also on a step that ends stuck.
+ * take_backtracking_step!(opt, -next, current_gradient) (:107-154) from h = 0: trial = fma(-(next 2^-h), gradient, old point),
+ * one fused multiply-add per element (the step is halved once per rejected trial); stuck when the trial isequal the old point
+ * (:128); accepted on strict decrease (:139), otherwise h += 1.  Deviation (as dzo_lbfgs_set_max_halvings): after max_halvings
+ * rejected trials (default 4096) the instance is stuck.
+ * On acceptance: delta_objective = f_new - f, delta_point = new - old and delta_gradient = g_new - g by subtraction
+ * (:306-308), iteration_count += 1.  The gradient of the accepted trial is kept: it is the value gradient_function! returns at
+ * :307.  On the step that finds the instance stuck: the point is unchanged, delta_point holds the copy of the old point made
+ * at :118, delta_gradient, f, g and iteration_count are untouched, and LAST_HALVINGS is the number of halvings tried.
+ * Energy and gradient of a trial come from ONE pair loop, the optimizer's own device routine: the stored f and g of a handle
+ * are, bit for bit, what dzo_pairwise_batch_energy_gradient returns for the stored points.  Sums of squares are in fp64 in a
+ * fixed order that depends on N only.  No floating-point atomics.  An instance computes the same
+ * bits alone or anywhere in any batch, and in one launch of k steps or k launches of one.
+ *
+ * Errors are those of dzo_lbfgs_batch_create: unknown radial or dtype, sizes < 1, steps < 0, null pointers, unknown `what`,
+ * max_halvings < 1 DZO_ERR_INVALID; n_particles > 1024 DZO_ERR_UNSUPPORTED; a host pointer where the reference asserts
+ * backend equality (:216-217) or initial_step_length <= 0 (:229) DZO_ERR_ASSERT.  create, read and count_active block; step
+ * enqueues on the library's stream and blocks only for all_stuck.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_ADGD_BATCH_MAX_PARTICLES 1024
+/* `what` of get_ptr / read (T = the handle's element type) */
+#define DZO_ADGD_BATCH_POINTS 0              /* T, 3N batch: the caller's array, current_point (aliased, :238) */
+#define DZO_ADGD_BATCH_GRADIENTS 1           /* T, 3N batch: current_gradient */
+#define DZO_ADGD_BATCH_DELTA_POINTS 2        /* T, 3N batch: delta_point */
+#define DZO_ADGD_BATCH_DELTA_GRADIENTS 3     /* T, 3N batch: delta_gradient */
+#define DZO_ADGD_BATCH_OBJECTIVES 4          /* T, batch: current_objective_value */
+#define DZO_ADGD_BATCH_DELTA_OBJECTIVES 5    /* T, batch: delta_objective_value */
+#define DZO_ADGD_BATCH_IS_STUCK 6            /* int32, batch */
+#define DZO_ADGD_BATCH_ITERATION_COUNTS 7    /* int64, batch */
+#define DZO_ADGD_BATCH_CURRENT_STEP_SIZES 8  /* T, batch: current_step_size (:195) */
+#define DZO_ADGD_BATCH_PREVIOUS_STEP_SIZES 9 /* T, batch: previous_step_size (:196) */
+#define DZO_ADGD_BATCH_LAST_HALVINGS 10      /* int32, batch: h of the last accepted step (step = -current_step_size 2^-h); on a stuck step the halvings tried */
+typedef struct dzo_adgd_batch_s *dzo_adgd_batch_t;
+/* AdGDOptimizer(nothing, f, g!, initial_point, initial_step_length) of every instance, :245-271 and :201-242.  points_dev:
+ * (3N, batch), instance b at element 3N b, [x | y | z] -- the tempering replica layout; ALIASED like the live constructor
+ * aliases initial_point (:238).  initial_step_length <= 0: DZO_ERR_ASSERT (:229).  Blocking. */
+int32_t dzo_adgd_batch_create(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                              double initial_step_length, dzo_adgd_batch_t *out);
+int32_t dzo_adgd_batch_destroy(dzo_adgd_batch_t h);
+/* the bound on the halvings of one step (the loop of :121-153 has none); default 4096, at least 1 */
+int32_t dzo_adgd_batch_set_max_halvings(dzo_adgd_batch_t h, int64_t max_halvings);
+/* `steps` step!() calls (:274-312) of every instance that is not stuck, one launch; all_stuck may be NULL (then no host wait) */
+int32_t dzo_adgd_batch_step(dzo_adgd_batch_t h, int32_t steps, int32_t *all_stuck);
+/* instances with is_stuck == false (:276).  Blocking. */
+int32_t dzo_adgd_batch_count_active(dzo_adgd_batch_t h, int64_t *active);
+/* device address of an array above (no wait) / a blocking copy of it to host memory, in the array's own element type */
+int32_t dzo_adgd_batch_get_ptr(dzo_adgd_batch_t h, int32_t what, void **ptr_dev);
+int32_t dzo_adgd_batch_read(dzo_adgd_batch_t h, int32_t what, void *out_host);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient

@@ -1,0 +1,88 @@
+"""CPU-side checks of the batched AdGD entry points (the method of tests/test_quench_build.py): the library exports them, the
+Python table binds them, the constants match the header, the header states the arithmetic with the reference's lines, the step
+kernels exist for gfx950 in both launch shapes and element types without scratch memory or spills, and the plain-C example
+compiles and links against the library alone.  No compute here."""
+import ctypes
+import os
+import re
+
+from build_checks import kernel_metadata, link_example
+from dzo_loader import dzo
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
+SYMBOLS = ["dzo_adgd_batch_create", "dzo_adgd_batch_destroy", "dzo_adgd_batch_set_max_halvings", "dzo_adgd_batch_step",
+           "dzo_adgd_batch_count_active", "dzo_adgd_batch_get_ptr", "dzo_adgd_batch_read"]
+WHAT = ["POINTS", "GRADIENTS", "DELTA_POINTS", "DELTA_GRADIENTS", "OBJECTIVES", "DELTA_OBJECTIVES", "IS_STUCK", "ITERATION_COUNTS",
+        "CURRENT_STEP_SIZES", "PREVIOUS_STEP_SIZES", "LAST_HALVINGS"]
+
+
+def test_library_exports_the_batched_adgd_entry_points():
+    lib = ctypes.CDLL(dzo.build())
+    missing = [n for n in SYMBOLS if not hasattr(lib, n)]
+    assert not missing, missing
+    assert [n for n in SYMBOLS if n not in dzo.ABI] == []
+    julia = open(os.path.join(PKG, "julia", "DZOptimizationAMD.jl")).read()
+    assert [n for n in SYMBOLS if "(:%s, libdzo)" % n not in julia] == []
+
+
+def test_python_constants_match_the_header():
+    header = open(os.path.join(ROOT, "include", "dzo.h")).read()
+    values = []
+    for name in WHAT + ["MAX_PARTICLES"]:
+        m = re.search(r"#define\s+DZO_ADGD_BATCH_%s\s+(\d+)\b" % name, header)
+        assert m, name
+        assert getattr(dzo, "ADGD_BATCH_" + name) == int(m.group(1)), name
+        values.append(int(m.group(1)))
+    assert sorted(values[:len(WHAT)]) == list(range(11))
+    assert dzo.ADGD_BATCH_MAX_PARTICLES == 1024
+    assert callable(dzo.BatchedAdGD)
+    for f in ("step", "count_active", "read", "ptr", "set_max_halvings", "close"):
+        assert callable(getattr(dzo.BatchedAdGD, f)), f
+    for p in ("current_points", "current_gradients", "delta_points", "delta_gradients", "current_objective_values",
+              "delta_objective_values", "is_stuck", "iteration_counts", "current_step_sizes", "previous_step_sizes", "last_halvings"):
+        assert isinstance(getattr(dzo.BatchedAdGD, p), property), p
+
+
+def test_header_states_the_arithmetic_with_the_reference_lines():
+    header = open(os.path.join(ROOT, "include", "dzo.h")).read()
+    block = header[header.index("Batched AdGDOptimizer"):header.index("LBFGSOptimizer  (src/DZOptimization.jl:321-509)")]
+    for needle in (":274-312", ":107-154", ":229-241", ":298-299", "max_halvings", ":245-271", ":216-217", ":229)", "sqrt(1 + theta)",
+                   "fused multiply-add", "No floating-point atomics"):
+        assert needle in block, needle
+
+
+def test_adgd_batch_kernels_exist_for_gfx950_without_scratch():
+    """Both launch shapes of the step kernel and the constructor's kernel, two element types each: no private segment, no VGPR
+    or SGPR spill."""
+    meta = kernel_metadata()
+    kernels = sorted(n for n in meta if "adgd_batch_" in n)
+    for shape in ("adgd_batch_wave_step_kernel", "adgd_batch_block_step_kernel", "adgd_batch_init_kernel"):
+        for t in ("If", "Id"):
+            assert any(shape + t in n for n in kernels), (shape, t, kernels)
+    assert len(kernels) == 6, kernels
+    for n in kernels:
+        print(n, meta[n])
+        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
+        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
+        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+
+
+def test_the_evaluation_has_one_definition():
+    """The trial's energy and gradient, the block sums and the dots are the quench's routines, defined once; the step-size rule
+    is the only arithmetic the new section adds."""
+    src = open(os.path.join(PKG, "csrc", "dzo_lbfgs_batch.hip")).read()
+    for routine in ("void q_wave_eval(", "void q_block_eval(", "double q_block_sum_all(", "double q_dot3(", "void quench_count_active_kernel("):
+        assert src.count(routine) == 1, routine
+    section = src[src.index("Batched AdGDOptimizer"):]
+    for call in ("q_wave_eval<T, F>(", "q_block_eval<T, F>(", "q_block_sum_all(", "q_dot3(", "qb_count(", "qb_launch_eval<T>("):
+        assert call in section, call
+    assert "pw_pair" not in section and "F::" not in section
+    assert 'DZO_TIMED("adgd_batch_init"' in section and 'DZO_TIMED("adgd_batch_step"' in section
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuenchLdsMax" in section
+
+
+def test_lj_adgd_quench_example_compiles_and_links(tmp_path):
+    _, wanted, have = link_example(tmp_path, "lj_adgd_quench")
+    assert {"dzo_adgd_batch_create", "dzo_adgd_batch_step", "dzo_adgd_batch_read", "dzo_adgd_batch_count_active",
+            "dzo_tempering_run"} <= wanted and wanted <= have, wanted - have

@@ -127,8 +127,9 @@ def baseline_case(dzo, replicas, n, count):
             "lowest_minimum": float(np.min(finals))}, np.array(finals), which
 
 
-def kernel_figures(lib_path):
-    """name -> {vgpr_count, sgpr_count, lds bytes (static), spills, scratch} of the quench kernels, from the gfx950 code object"""
+def kernel_figures(lib_path, pattern="quench_"):
+    """name -> {vgpr_count, sgpr_count, lds bytes (static), spills, scratch} of the kernels whose name holds `pattern` (the quench
+    kernels), from the gfx950 code object"""
     llvm = "/opt/rocm/lib/llvm/bin"
     out = {}
     if not os.path.exists(os.path.join(llvm, "llvm-objdump")):
@@ -150,13 +151,13 @@ def kernel_figures(lib_path):
                 m = re.match(r"[\s-]+\.name:\s+(\S+)", line)
                 if m:
                     name = m.group(1)
-                    if "quench_" in name:
+                    if pattern in name:
                         out.setdefault(name, {}).update(early)
                 m = re.match(r"[\s-]+\.(%s):\s+(\d+)" % keys, line)
                 if m:
                     if name is None:
                         early[m.group(1)] = int(m.group(2))
-                    elif "quench_" in name:
+                    elif pattern in name:
                         out.setdefault(name, {})[m.group(1)] = int(m.group(2))
     return out
 
