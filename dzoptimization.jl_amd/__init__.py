@@ -196,6 +196,8 @@ ABI = {
     "dzo_adgd_batch_set_max_halvings": [_vp, _i64], "dzo_adgd_batch_step": [_vp, _i32, _P(_i32)],
     "dzo_adgd_batch_count_active": [_vp, _P(_i64)], "dzo_adgd_batch_get_ptr": [_vp, _i32, _P(_vp)],
     "dzo_adgd_batch_read": [_vp, _i32, _vp],
+    "dzo_pairwise_batch_hvp": [_i32, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
+    "dzo_pairwise_batch_hessian": [_i32, _i64, _i64, _i32, _vp, _vp],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -775,6 +777,62 @@ class BatchedAdGD(_HandleArrays):
     current_step_sizes = property(lambda self: self.read(ADGD_BATCH_CURRENT_STEP_SIZES))
     previous_step_sizes = property(lambda self: self.read(ADGD_BATCH_PREVIOUS_STEP_SIZES))
     last_halvings = property(lambda self: self.read(ADGD_BATCH_LAST_HALVINGS))
+
+
+# ------------------------------------------------------------------------------ batched Hessians of Lennard-Jones clusters
+HESSIAN_BATCH_MAX_PARTICLES = 1024
+
+
+def pairwise_batch_hvp(points, directions, n_particles, products=None, curvatures=False, shared_point=False,
+                       radial=RADIAL_LENNARD_JONES):
+    """``accelerated_pairwise_radial_hvp!`` (src/ExampleFunctions.jl:367-468) of every instance in one launch.  ``directions``
+    is a DeviceArray of ``3 * n_particles * batch`` elements, instance b ``[u | v | w]`` at ``3 * n_particles * b``; ``points``
+    has the same layout, or with ``shared_point=True`` holds ONE point to which every direction is applied.  The products go
+    into ``products`` (allocated when None).  Returns the products' DeviceArray, or with ``curvatures=True`` the pair
+    ``(products, c)`` where ``c`` is a host array ``(batch, 2)`` of ``u.Hu`` and ``u.u`` in fp64."""
+    n = int(n_particles)
+    batch = directions.size // (3 * n) if n > 0 else 0
+    assert directions.size == 3 * n * batch and batch >= 1, "directions must hold 3 * n_particles * batch elements"
+    assert points.size == (3 * n if shared_point else 3 * n * batch), "points must hold one point per instance, or one point when shared"
+    assert points.dtype == directions.dtype, "points and directions must have one element type"
+    if products is None:
+        products = DeviceArray(directions.shape, directions.dtype)
+    assert products.size == directions.size and products.dtype == directions.dtype
+    curv = DeviceArray((batch, 2), np.float64) if curvatures else None
+    _check(lib().dzo_pairwise_batch_hvp(radial, n, batch, _dt(points.dtype), points.ptr, 0 if shared_point else 3 * n, directions.ptr,
+                                        products.ptr, curv.ptr if curvatures else None))
+    return (products, curv.to_host()) if curvatures else products
+
+
+def pairwise_batch_hessian(points, n_particles, out=None, radial=RADIAL_LENNARD_JONES):
+    """The dense ``3N x 3N`` Hessian of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b
+    ``[x | y | z]``) from one launch.  Returns a host array ``[b, c, r]``: column c, row r of instance b (the device layout,
+    column-major per instance).  ``out``: a DeviceArray of ``9 * n_particles**2 * batch`` elements to hold the device copy."""
+    n = int(n_particles)
+    batch = points.size // (3 * n) if n > 0 else 0
+    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    if out is None:
+        out = DeviceArray((batch, 3 * n, 3 * n), points.dtype)
+    assert out.size == 9 * n * n * batch and out.dtype == points.dtype
+    _check(lib().dzo_pairwise_batch_hessian(radial, n, batch, _dt(points.dtype), points.ptr, out.ptr))
+    return out.to_host().reshape(batch, 3 * n, 3 * n)
+
+
+def hessian_eigenvalues(points, n_particles, radial=RADIAL_LENNARD_JONES):
+    """Eigenvalues of the Hessian of every instance, ascending, as a ``(batch, 3N)`` fp64 host array: the device Hessians,
+    symmetrised as ``(H + H^T) / 2`` in fp64 on the host (the device does not promise bitwise symmetry), then
+    ``numpy.linalg.eigvalsh``."""
+    h = pairwise_batch_hessian(points, n_particles, radial=radial).astype(np.float64)
+    return np.linalg.eigvalsh(0.5 * (h + h.transpose(0, 2, 1)))
+
+
+def morse_index(eigenvalues, zero_tol):
+    """``(negatives, zeros)`` per instance: the eigenvalues below ``-zero_tol`` (the Morse index) and those with
+    ``|lambda| <= zero_tol`` (six rigid-body modes for a cluster in free space).  ``zero_tol`` is an absolute value in the
+    eigenvalues' unit and depends on the element type and on the scale of the spectrum: there is no default."""
+    ev = np.atleast_2d(np.asarray(eigenvalues, dtype=np.float64))
+    tol = float(zero_tol)
+    return (ev < -tol).sum(axis=1), (np.abs(ev) <= tol).sum(axis=1)
 
 
 # ------------------------------------------------------------------------------ profiling

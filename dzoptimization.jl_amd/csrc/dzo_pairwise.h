@@ -13,7 +13,7 @@ int32_t pairwise_energy_async(hipStream_t s, int32_t radial, int64_t n_particles
 int32_t pairwise_gradient_async(hipStream_t s, int32_t radial, int64_t n_particles, int32_t dtype, void *gx, void *gy, void *gz,
                                 const void *x, const void *y, const void *z, double *ws);
 
-// ------------------------------------------------------------------------------ host helpers of the three units
+// ------------------------------------------------------------------------------ host helpers of the units built on this header
 // hipMalloc (at least 16 bytes) of a piece of `what_for`, cleared when `zero_fill`; DZO_ERR_NOMEM with `what_for` in the message
 int32_t device_alloc(void **p, size_t bytes, const char *what_for, bool zero_fill);
 // The argument checks of every entry point that takes `count` sets of n_particles particles, in this order: radial, dtype,
@@ -24,8 +24,8 @@ int32_t pw_check_args(int32_t radial, int32_t dtype, int64_t n_particles, int64_
 // `bytes` of a handle's array to or from the host on the current context's stream; returns when they have arrived
 int32_t copy_blocking(void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
 
-// The device pieces below are shared by dzo_pairwise.hip, dzo_tempering.hip and dzo_lbfgs_batch.hip (one definition, the same
-// bits in all three).
+// The device pieces below are shared by dzo_pairwise.hip, dzo_tempering.hip, dzo_lbfgs_batch.hip and dzo_hessian_batch.hip (one
+// definition, the same bits in all of them).
 // ------------------------------------------------------------------------------ radial functions (:16-72)
 template <typename T> __device__ __forceinline__ T pw_twice(T a) { return a + a; }
 template <typename T> __device__ __forceinline__ T pw_square(T a) { return a * a; }

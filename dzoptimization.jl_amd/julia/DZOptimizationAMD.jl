@@ -30,7 +30,8 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        accelerated_pairwise_radial_energy, accelerated_pairwise_radial_gradient!, accelerated_pairwise_radial_hvp!,
        pairwise_radial_energy_delta,
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
-       BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!
+       BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!,
+       pairwise_batch_hvp!, pairwise_batch_hessian!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -441,6 +442,29 @@ function pairwise_batch_energy_gradient!(energies::HipVector{T}, gradients::HipV
     check(ccall((:dzo_pairwise_batch_energy_gradient, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
                 DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, energies.ptr, gradients.ptr))
     return energies
+end
+
+"""`pairwise_batch_hvp!(products, points, directions, n_particles; curvatures=nothing, shared_point=false)`:
+accelerated_pairwise_radial_hvp! (src/ExampleFunctions.jl:367-468) of every instance in one launch.  `curvatures`: a
+`HipVector{Float64}` of 2 * batch elements for u.Hu and u.u of each instance.  `shared_point`: `points` holds one point to which
+every direction is applied.  Blocks."""
+function pairwise_batch_hvp!(products::HipVector{T}, points::HipVector{T}, directions::HipVector{T}, n_particles::Integer;
+                             curvatures::Union{Nothing,HipVector{Float64}}=nothing, shared_point::Bool=false) where {T}
+    batch = div(length(directions), 3 * n_particles)
+    check(ccall((:dzo_pairwise_batch_hvp, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, shared_point ? 0 : 3 * n_particles,
+                directions.ptr, products.ptr, curvatures === nothing ? C_NULL : curvatures.ptr))
+    return products
+end
+
+"""`pairwise_batch_hessian!(hessians, points, n_particles)`: the dense 3N x 3N Hessian of every instance, column-major per
+instance (`reshape(Array(hessians), 3N, 3N, batch)`), from one launch.  Blocks."""
+function pairwise_batch_hessian!(hessians::HipVector{T}, points::HipVector{T}, n_particles::Integer) where {T}
+    batch = div(length(points), 3 * n_particles)
+    check(ccall((:dzo_pairwise_batch_hessian, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, hessians.ptr))
+    return hessians
 end
 
 """`quench(lj_energy, points, n_particles; ...)`: run the batched optimizer on `points` (in place) until every instance is

@@ -461,6 +461,54 @@ int32_t dzo_adgd_batch_get_ptr(dzo_adgd_batch_t h, int32_t what, void **ptr_dev)
 int32_t dzo_adgd_batch_read(dzo_adgd_batch_t h, int32_t what, void *out_host);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched Hessian-vector products and dense Hessians of many small Lennard-Jones clusters: second-order information on the
+ * points the batched optimizers above leave behind (minimum or saddle, normal modes, curvature along a direction).  The
+ * product is accelerated_pairwise_radial_hvp! (src/ExampleFunctions.jl:367-468) with lj_first_derivative and
+ * lj_second_derivative (:50-72), every instance in ONE launch.  Both entry points block.
+ *
+ * Layout.  points, directions and products are (3N, batch): instance b at element 3N b, [x(0..N) | y | z] -- the tempering and
+ * quench layout.  point_stride is the distance in elements between the points of consecutive instances: 3N (or more) for one
+ * point per instance, 0 to apply `batch` directions to ONE point (a block product of one cluster); any other value below 3N is
+ * DZO_ERR_INVALID.  curvatures_dev may be NULL; otherwise fp64, (2, batch): u.Hu at 2 b and u.u at 2 b + 1 (their quotient is
+ * the Rayleigh quotient of direction b).  hessians are (3N, 3N, batch), column-major per instance like every matrix in this
+ * header: element r + 3N (c + 3N b) is row r, column c of instance b; row a N + i is component a of particle i.
+ *
+ * Launch shapes.  n_particles <= 64: one wave per instance, lane i holds particle i (and its direction) in registers, particle j
+ * arrives through a lane read, four independent pairs per trip, no barrier.  65 .. 1024 (DZO_HESSIAN_BATCH_MAX_PARTICLES): one
+ * 256-thread block per instance, thread t owns particles t + 256 q, point and direction staged in LDS.
+ *
+ * Arithmetic (T = the element type; this is the specification).
+ * Per pair (i, j), the body of :395-419 with the per-pair operations of dzo_pairwise_hvp, one rounding per operation:
+ * d = r_i - r_j, du = u_i - u_j, r2 = dx dx + dy dy + dz dz (left to right), f = lj_first_derivative(r2) (:30-47), s =
+ * lj_second_derivative(r2) (:50-72), overlap = dx du + dy dv + dz dw (left to right), g = twice(overlap s), term_a = f du_a +
+ * g d_a.  The self term and the padding of the unrolled loop are computed and dropped by a select (f = s = 0; ifelse, :145).
+ * The row sum of particle i runs j = 0 .. N-1 sequentially in T from +0; products_i = twice(sum) (:421-423).
+ * u.Hu and u.u: an fp64 dot in a fixed order that depends on N only -- per particle u_x p_x, then fma(u_y, p_y, .), then
+ * fma(u_z, p_z, .); N <= 64: the wave tree over the particles; above: a thread's particles t, t + 256, ... added in that order,
+ * the wave tree, then the block's four wave sums in wave order.
+ * Dense Hessian.  For finite inputs with no coincident particles, column c of hessians[b] has the same values as
+ * dzo_pairwise_batch_hvp of points[b] with the unit direction e_c (compare with ==; the sign of a zero is free).  It is not
+ * obtained by 3N products but assembled from one pass over the pairs: an off-diagonal block (i != j) is the single term with
+ * du = -e_b: overlap = -d_b, g = twice(overlap s), entry (a, b) = twice(f du_a + g d_a); the diagonal block of particle i is the
+ * sequential sum over j of f delta_ab + twice(d_b s) d_a, then twice.  All other terms of those product rows are exact zeros,
+ * which is why the two agree.  Bitwise symmetry is NOT promised: (d_b s) d_a and (d_a s) d_b round differently.
+ * No floating-point atomics: every element is written once by one thread.  An instance computes the same bits alone or anywhere
+ * in any batch, and with point_stride 0 or 3N.  Coincident particles give non-finite values in their rows, as in the reference.
+ *
+ * Errors are those of dzo_pairwise_batch_energy_gradient: unknown radial or dtype, sizes < 1, a bad point_stride, null pointers
+ * (curvatures_dev excepted) DZO_ERR_INVALID; n_particles > 1024 DZO_ERR_UNSUPPORTED; a host pointer where the reference asserts
+ * backend equality (:453-461) DZO_ERR_ASSERT.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_HESSIAN_BATCH_MAX_PARTICLES 1024
+/* products[b] = Hessian(points[b]) applied to directions[b]     (:367-468, batched) */
+int32_t dzo_pairwise_batch_hvp(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype,
+                               const void *points_dev, int64_t point_stride,
+                               const void *directions_dev, void *products_dev, double *curvatures_dev);
+/* hessians[b] = the dense 3N x 3N Hessian of points[b] */
+int32_t dzo_pairwise_batch_hessian(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype,
+                                   const void *points_dev, void *hessians_dev);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
