@@ -198,6 +198,8 @@ ABI = {
     "dzo_adgd_batch_read": [_vp, _i32, _vp],
     "dzo_pairwise_batch_hvp": [_i32, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
     "dzo_pairwise_batch_hessian": [_i32, _i64, _i64, _i32, _vp, _vp],
+    "dzo_symmetric_batch_eigen": [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32],
+    "dzo_symeig_plan": [_i64, _i32, _P(_i32), _P(_i64), _P(_i64)],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -833,6 +835,65 @@ def morse_index(eigenvalues, zero_tol):
     ev = np.atleast_2d(np.asarray(eigenvalues, dtype=np.float64))
     tol = float(zero_tol)
     return (ev < -tol).sum(axis=1), (np.abs(ev) <= tol).sum(axis=1)
+
+
+# ------------------------------------------------------------------------------ batched symmetric eigensolver
+SYMEIG_MAX_N = 384
+SYMEIG_STORAGE_LDS, SYMEIG_STORAGE_MEMORY = 0, 1
+
+
+def symeig_plan(n, dtype):
+    """``(storage, ld, lds_bytes)`` of ``dzo_symeig_plan``: where the eigensolver keeps an ``n x n`` matrix of ``dtype`` while
+    it iterates.  A pure function; needs no device."""
+    storage, ld, lds = C.c_int32(), C.c_int64(), C.c_int64()
+    _check(lib().dzo_symeig_plan(int(n), _dt(dtype), C.byref(storage), C.byref(ld), C.byref(lds)))
+    return storage.value, ld.value, lds.value
+
+
+def _symeig_device(matrices, n, batch, vectors, max_sweeps, want_sweeps=True):
+    """The device call on a DeviceArray of matrices: DeviceArrays (eigenvalues, eigenvectors or None, sweeps or None)."""
+    w = DeviceArray((batch, n), matrices.dtype)
+    v = DeviceArray((batch, n, n), matrices.dtype) if vectors else None
+    s = DeviceArray((batch,), np.int32) if want_sweeps else None
+    _check(lib().dzo_symmetric_batch_eigen(n, batch, _dt(matrices.dtype), matrices.ptr, w.ptr, v.ptr if vectors else None,
+                                           s.ptr if want_sweeps else None, int(max_sweeps)))
+    return w, v, s
+
+
+def symmetric_batch_eigen(matrices, n, vectors=False, max_sweeps=0):
+    """Eigenvalues, ascending, and with ``vectors=True`` eigenvectors of the symmetric part of every ``n x n`` matrix of
+    ``matrices``, on the device in one launch (``dzo_symmetric_batch_eigen``: cyclic Jacobi, one block per matrix).  ``matrices``
+    is a DeviceArray of ``n * n * batch`` elements, column-major per instance (what ``pairwise_batch_hessian`` writes into its
+    ``out``), or a host array ``(batch, n, n)`` indexed ``[b, c, r]``, which is uploaded.  Returns host arrays: the eigenvalues
+    ``(batch, n)`` in the element type, the eigenvectors ``(batch, n, n)`` in the device layout (``[b, k, :]`` is the vector of
+    eigenvalue k) or None, and the sweeps ``(batch,)`` each instance ran, -1 where ``max_sweeps`` (0: the default, 30) did not
+    suffice.  The matrices are not modified."""
+    n = int(n)
+    if not isinstance(matrices, DeviceArray):
+        matrices = DeviceArray.from_host(matrices)
+    batch = matrices.size // (n * n) if n > 0 else 0
+    assert n >= 1 and matrices.size == n * n * batch and batch >= 1, "matrices must hold n * n * batch elements"
+    w, v, s = _symeig_device(matrices, n, batch, vectors, max_sweeps)
+    return w.to_host().reshape(batch, n), (v.to_host().reshape(batch, n, n) if vectors else None), s.to_host().reshape(batch)
+
+
+def hessian_spectrum(points, n_particles, vectors=False, radial=RADIAL_LENNARD_JONES):
+    """The spectrum of the Hessian of every instance of ``points`` without leaving the device: ``dzo_pairwise_batch_hessian``
+    into ``dzo_symmetric_batch_eigen``; only the results travel to the host.  Returns the eigenvalues, ascending, as a
+    ``(batch, 3N)`` fp64 host array, or with ``vectors=True`` the pair ``(eigenvalues, eigenvectors)`` with the eigenvectors
+    ``(batch, 3N, 3N)`` in the points' element type (``[b, k, :]`` is the normal mode of eigenvalue k).  Raises when an
+    instance did not converge (non-finite Hessian: coincident particles)."""
+    n = int(n_particles)
+    batch = points.size // (3 * n) if n > 0 else 0
+    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    h = DeviceArray((batch, 3 * n, 3 * n), points.dtype)
+    _check(lib().dzo_pairwise_batch_hessian(radial, n, batch, _dt(points.dtype), points.ptr, h.ptr))
+    w, v, s = _symeig_device(h, 3 * n, batch, vectors, 0)
+    sweeps = s.to_host().reshape(batch)
+    if np.any(sweeps < 0):
+        raise DzoError(6, "hessian_spectrum: no convergence in instances %s" % np.flatnonzero(sweeps < 0).tolist())
+    ev = w.to_host().reshape(batch, 3 * n).astype(np.float64)
+    return (ev, v.to_host().reshape(batch, 3 * n, 3 * n)) if vectors else ev
 
 
 # ------------------------------------------------------------------------------ profiling

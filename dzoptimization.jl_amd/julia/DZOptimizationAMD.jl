@@ -31,7 +31,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        pairwise_radial_energy_delta,
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
        BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!,
-       pairwise_batch_hvp!, pairwise_batch_hessian!
+       pairwise_batch_hvp!, pairwise_batch_hessian!, symmetric_batch_eigen!, symeig_plan, hessian_spectrum
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -465,6 +465,44 @@ function pairwise_batch_hessian!(hessians::HipVector{T}, points::HipVector{T}, n
     check(ccall((:dzo_pairwise_batch_hessian, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
                 DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, hessians.ptr))
     return hessians
+end
+
+"""`symmetric_batch_eigen!(eigenvalues, matrices, n; eigenvectors=nothing, max_sweeps=0)`: eigenvalues (ascending, n per
+instance) and optionally eigenvectors (n x n per instance, column-major, column k belongs to eigenvalue k) of the symmetric part
+of every n x n matrix of `matrices` (column-major per instance: what `pairwise_batch_hessian!` writes), by cyclic Jacobi on the
+device, one launch.  Returns the sweeps each instance ran as a `Vector{Int32}`, -1 where `max_sweeps` (0: the default, 30) did
+not suffice.  `matrices` is not modified.  Blocks."""
+function symmetric_batch_eigen!(eigenvalues::HipVector{T}, matrices::HipVector{T}, n::Integer;
+                                eigenvectors::Union{Nothing,HipVector{T}}=nothing, max_sweeps::Integer=0) where {T}
+    batch = div(length(matrices), n * n)
+    sweeps = HipVector{Float32}(undef, batch)               # four bytes per instance: read back as Int32
+    check(ccall((:dzo_symmetric_batch_eigen, libdzo), Cint,
+                (Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint),
+                n, batch, dtype_code(T), matrices.ptr, eigenvalues.ptr, eigenvectors === nothing ? C_NULL : eigenvectors.ptr,
+                sweeps.ptr, max_sweeps))
+    return collect(reinterpret(Int32, Array(sweeps)))
+end
+
+"""`symeig_plan(n, T)`: `(storage, ld, lds_bytes)` -- where `symmetric_batch_eigen!` keeps an n x n matrix of `T` while it
+iterates (0: LDS, 1: device memory), its leading dimension and the dynamic LDS of the launch.  A pure function; no device."""
+function symeig_plan(n::Integer, ::Type{T}) where {T<:Union{Float32,Float64}}
+    storage, ld, lds = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:dzo_symeig_plan, libdzo), Cint, (Int64, Cint, Ref{Cint}, Ref{Int64}, Ref{Int64}),
+                n, dtype_code(T), storage, ld, lds))
+    return Int(storage[]), Int(ld[]), Int(lds[])
+end
+
+"""`hessian_spectrum(points, n_particles)`: the eigenvalues of the Hessian of every instance as a `3N x batch` `Matrix{Float64}`,
+ascending per column: `pairwise_batch_hessian!` into `symmetric_batch_eigen!` without leaving the device.  Throws when an
+instance does not converge (a non-finite Hessian)."""
+function hessian_spectrum(points::HipVector{T}, n_particles::Integer) where {T}
+    n = 3 * n_particles
+    batch = div(length(points), n)
+    hessians = pairwise_batch_hessian!(HipVector{T}(undef, n * n * batch), points, n_particles)
+    eigenvalues = HipVector{T}(undef, n * batch)
+    sweeps = symmetric_batch_eigen!(eigenvalues, hessians, n)
+    any(<(0), sweeps) && error("hessian_spectrum: no convergence in instances $(findall(<(0), sweeps))")
+    return Float64.(reshape(Array(eigenvalues), n, batch))
 end
 
 """`quench(lj_energy, points, n_particles; ...)`: run the batched optimizer on `points` (in place) until every instance is

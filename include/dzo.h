@@ -509,6 +509,68 @@ int32_t dzo_pairwise_batch_hessian(int32_t radial, int64_t n_particles, int64_t 
                                    const void *points_dev, void *hessians_dev);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched symmetric eigensolver: the spectrum of many small dense symmetric matrices on the device -- the Hessians that
+ * dzo_pairwise_batch_hessian writes, diagonalised where they are (minimum or saddle, the Morse index, the six rigid-body
+ * zeros, normal modes).  Two-sided cyclic Jacobi in a parallel (round-robin) ordering, every instance in ONE launch, one
+ * 256-thread block per instance.  Nothing in the reference diagonalises anything: this block is the specification.
+ *
+ * Layout.  matrices are (n, n, batch), column-major per instance like every matrix in this header: element r + n (c + n b) is
+ * row r, column c of instance b.  eigenvalues are (n, batch), ascending.  eigenvectors are (n, n, batch), column-major: column k
+ * of instance b belongs to eigenvalue k.  sweeps are int32, (batch).
+ *
+ * Storage (dzo_symeig_plan tells).  DZO_SYMEIG_STORAGE_LDS whenever 64 bytes, 2 m elements (m = n + (n & 1)) and n ld elements,
+ * ld = n | 1 (the smallest odd number >= n), fit the 160 KiB of LDS of a compute unit: the matrix stays in LDS for the whole
+ * iteration.  That covers n = 141 in fp64 (114 = 3 * 38 is the workload) and n = 201 in fp32.  Above that
+ * DZO_SYMEIG_STORAGE_MEMORY: the same kernel body on a per-call device workspace copy with ld = n, functional rather than
+ * fast, up to DZO_SYMEIG_MAX_N.  Both storages compute the same bits.  V lives in eigenvectors_dev in both.
+ *
+ * Arithmetic (T = the element type; every operation in T with one rounding, no contraction, IEEE division and square root,
+ * unless fp64 is named).
+ * 1. Load.  a[r,c] = T(0.5) * (A[r,c] + A[c,r]): the symmetric part (the Hessian kernel does not promise bitwise symmetry).
+ *    With eigenvectors V = I.  fro = sqrt(sum a[r,c]^2), in fp64 in a fixed order that depends on n only, the ORDER OF THE
+ *    NORMS: thread (w, l), w = 0 .. 3, l = 0 .. 63, adds the squares (one fp64 product, one fp64 sum each, from +0) of columns
+ *    c = w, w + 4, ... (outer) and rows r = l, l + 64, ... (inner); the 64 values of a wave are added by the xor tree with
+ *    offsets 32, 16, 8, 4, 2, 1; the four wave sums are added in wave order from +0.
+ * 2. Sweep test, at the start of every sweep.  off = sqrt(sum over r != c of a[r,c]^2), from the off-diagonal entries
+ *    themselves (never as a difference of two sums), in fp64 in the order of the norms with an exact 0 in place of a diagonal
+ *    square.  Converged when off <= eps_T * fro and eps_T * fro is finite, both sides in fp64, eps_T = 2^-52 or 2^-23: a
+ *    diagonal or zero matrix runs 0 sweeps.  Otherwise, after max_sweeps sweeps: stop, sweeps = -1.
+ * 3. Round order.  A sweep is m - 1 rounds.  idx = [0 .. m-1]; a round pairs idx[k] with idx[m-1-k], k = 0 .. m/2 - 1; a pair
+ *    that contains the padding index n (odd n) is dropped; p = min, q = max of the pair.  After a round
+ *    idx = [idx[0], idx[m-1], idx[1], ..., idx[m-2]].  The list is reset at the start of every sweep (after m - 1 rounds it
+ *    has returned to [0 .. m-1] by itself, so resetting and not resetting are the same order).
+ * 4. Angles.  Of all pairs of a round from the matrix as it stands at the start of the round, with a_pq = a[p,q] (row p):
+ *    tau = (a_qq - a_pp) / (a_pq + a_pq), t = copysign(1, tau) / (|tau| + sqrt(1 + tau*tau)), c = 1 / sqrt(1 + t*t), s = t * c.
+ *    If a_pq == 0: c = 1, s = 0.  An overflowing tau or tau*tau gives t = 0 by itself; tau = 0 gives the 45 degree rotation.
+ * 5. Apply.  Columns first, for all rows r: (a[r,p], a[r,q]) = (c*a[r,p] - s*a[r,q], s*a[r,p] + c*a[r,q]); V gets the same
+ *    column update and nothing else.  Then, with every column of the round done, rows for all columns k:
+ *    (a[p,k], a[q,k]) = (c*a[p,k] - s*a[q,k], s*a[p,k] + c*a[q,k]); then a[p,q] = a[q,p] = 0 exactly.  Rotations with c = 1,
+ *    s = 0 are applied like any other.  The pairs of a round are disjoint: one writer per element and phase, no atomics.
+ * 6. Finish.  The eigenvalues are the diagonal, ascending and stable: eigenvalue k goes to place
+ *    #{j : d_j < d_k} + #{j < k : d_j == d_k}, and column k of V with it.
+ * Non-finite input gives sweeps = -1 and unspecified values, and returns: the loop is bounded by max_sweeps.  An instance
+ * computes the same bits alone or anywhere in any batch, with or without eigenvectors, with or without sweeps_dev.
+ *
+ * Errors follow dzo_pairwise_batch_hessian: unknown dtype, n < 1, batch outside 1 .. 2^30, a null matrices_dev or
+ * eigenvalues_dev DZO_ERR_INVALID; n > DZO_SYMEIG_MAX_N DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required
+ * DZO_ERR_ASSERT; no memory for the workspace DZO_ERR_NOMEM.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_SYMEIG_MAX_N 384
+#define DZO_SYMEIG_DEFAULT_SWEEPS 30
+#define DZO_SYMEIG_STORAGE_LDS 0
+#define DZO_SYMEIG_STORAGE_MEMORY 1
+/* eigenvalues[b] (T, n per instance, ascending) and, unless eigenvectors_dev is NULL, eigenvectors[b] ((n, n), column-major,
+ * column k belongs to eigenvalue k) of the symmetric part of matrices[b] ((n, n, batch), column-major per instance: the layout
+ * dzo_pairwise_batch_hessian writes).  sweeps_dev (int32, batch) may be NULL: the sweeps instance b ran, or -1 when max_sweeps
+ * were run without convergence.  max_sweeps <= 0: the default, 30.  matrices_dev is not modified.  Blocking. */
+int32_t dzo_symmetric_batch_eigen(int64_t n, int64_t batch, int32_t dtype, const void *matrices_dev,
+                                  void *eigenvalues_dev, void *eigenvectors_dev, int32_t *sweeps_dev, int32_t max_sweeps);
+/* Where dzo_symmetric_batch_eigen keeps an n x n matrix of this dtype while it iterates: the storage, the leading dimension
+ * and the dynamic LDS of the launch.  A pure function of (n, dtype): no device needed.  Any of the three outputs may be NULL.
+ * Unknown dtype or n < 1 DZO_ERR_INVALID, n > DZO_SYMEIG_MAX_N DZO_ERR_UNSUPPORTED. */
+int32_t dzo_symeig_plan(int64_t n, int32_t dtype, int32_t *storage, int64_t *ld, int64_t *lds_bytes);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
