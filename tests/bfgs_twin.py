@@ -15,6 +15,10 @@ Three tools:
 
 and the shape tables ``FULL_F64`` / ``FULL_F32`` / ``TRI`` / ``MFMA`` with the path functions ``takes_vec`` / ``takes_tri`` that
 say which kernel instantiation a shape runs.
+
+For the batched kernel of csrc/dzo_batch.hip (tests/test_gpu_bfgs_batch_shapes.py), which keeps t = H0*dg in LDS: the table
+``BATCH`` with ``batch_form``, the elementwise bound ``batch_update_bound`` of the update computed from its inputs alone, and for
+fp32 ``t_rounded`` (the device's t is the rounding of the exact sum, up to a few undecided rows) with ``replay_update_undecided``.
 """
 import collections
 import math
@@ -314,3 +318,173 @@ def device_norm(d):
     and lam = T(-t_b) and the step length are rounded once more each.  The caller allows 3 u_T for all of it (lam_rel)."""
     T = d.dtype
     return np.sqrt(np.array([(d.astype(LD) ** 2).sum()]).astype(T))[0]
+
+
+# ------------------------------------------------------------------------------ the batched kernel (csrc/dzo_batch.hip)
+BatchForm = collections.namedtuple("BatchForm", "rp wide uj lds_bytes needs_attribute")
+BATCH_LDS_DEFAULT = 48 * 1024       # dynamic LDS a kernel may ask for before hipFuncAttributeMaxDynamicSharedMemorySize is needed
+BATCH_WIDE_ABOVE = 448              # RP = 2: two columns in flight at two blocks per CU up to here, four at one block beyond
+BATCH_FORMS = ("rp1", "rp2 narrow", "rp2 wide", "rp4")
+
+
+def batch_form(n, dtype):
+    """(rp, wide, uj, lds_bytes, needs_attribute) of batch_step_kernel for an even n in 2..1024, as batch_create_impl and the
+    kernel's ``UJ`` line choose them: rp row pairs per thread (n <= 256 rp), the wide form of rp = 2 above 448, uj columns per
+    chunk of the two-deep pipeline, and the dynamic LDS: nine vectors of T, then in double the half-combine scratch, four
+    waves' column parts and 16 scalars, then a flag."""
+    assert n % 2 == 0 and 2 <= n <= 1024
+    rp = 1 if n <= 256 else (2 if n <= 512 else 4)
+    wide = rp == 2 and n > BATCH_WIDE_ABOVE
+    uj = 4 if rp == 1 else ((4 if wide else 2) if rp == 2 else 2)
+    np_ = (n + 1) & ~1
+    lds = 9 * np_ * np.dtype(dtype).itemsize + (5 * np_ + 16) * 8 + 16
+    return BatchForm(rp, wide, uj, lds, lds > BATCH_LDS_DEFAULT)
+
+
+def batch_form_name(n, dtype):
+    f = batch_form(n, dtype)
+    return "rp1" if f.rp == 1 else ("rp4" if f.rp == 4 else ("rp2 wide" if f.wide else "rp2 narrow"))
+
+
+# Even n.  A thread owns the row pairs 2 (lane + 128 r), r < rp; the two 128-thread halves take the even / the odd columns, so a
+# half has n / 2 columns, walks them uj at a time and two chunks (2 uj columns) per trip of the pipeline loop.
+BATCH = [
+    2,              # one row pair, one column per half: a chunk with 1 live column
+    4, 6, 8,        # 2, 3, 4 live columns in the first chunk (uj = 4); the pair (j - 1, j) of every odd column straddles the diagonal
+    10,             # 5 columns per half: a second chunk with one live column
+    14, 16, 18,     # 7 / 8 / 9 columns per half: short of one whole pipeline trip (2 uj = 8), exactly one, one column more
+    30, 32, 34,     # two trips' edge
+    62, 64, 66,     # 32 row pairs: half a wave of each half has work; 66: 33 columns, a fifth trip with one column
+    126, 128, 130,  # 64 row pairs = one whole wave per half; 130: the lane that starts the second wave of a half
+    254, 256,       # 256: every thread of a half owns a pair, the last size of rp 1 (fp64: 28816 bytes of LDS)
+    258,            # rp 2 narrow (uj = 2): the first thread with a second pair
+    260, 262, 264, 266,   # 130 .. 133 columns per half against trips of 4: the last trip holds 2, 3, 4 (whole) and 1 columns
+    384,            # the benchmarked size
+    436, 438,       # fp64: 48976 / 49200 bytes of LDS, either side of the 48 KiB above which the attribute must be set
+    446, 448,       # the last narrow sizes
+    450,            # rp 2 wide (uj = 4): the first size of the form
+    510, 512,       # 255 / 256 columns per half; 512: every thread owns two pairs, the last size of rp 2
+    514, 516,       # rp 4 (uj = 2): one / two threads in the third row pair
+    644, 646,       # fp32: 49088 / 49240 bytes of LDS, either side of 48 KiB
+    768, 770,       # three whole row pairs per thread; 770: one thread in the fourth
+    1022, 1024,     # the last sizes: 1024 is every thread with four pairs (fp64: 114832 bytes of LDS)
+]
+BATCH_ONE_PER_FORM = [130, 262, 450, 770]   # ragged in every form: a lone lane in the second wave, a last trip of 3 columns, the
+#                                             first wide size, one thread in the fourth row pair
+BATCH_SEEDS = (1000, 1003, 1006)            # starts of the trajectories: instance b of start k is pcg_fill(n, BATCH_SEEDS[k] + b)
+UNDECIDED_CAP = 2                           # rows of t = H0*dg per step whose fp32 rounding the replay may have to search
+
+
+def batch_update_bound(H0, d, dg, lam, dtype, lam_rel=0.0):
+    """(exact, bound) per element [i, j] of the batched kernel's update H0 + (delta*(s_i*s_j) - (t_i*s_j + s_i*t_j)), first order.
+
+    exact: in longdouble from H0, the UNSCALED direction d, dg and lam = -t_b alone: ov = sum d dg, t = H0 dg, q = sum dg t,
+    delta = lam ov + q, s = d / ov.  Nothing the kernel computed enters it, so a wrong t, overlap or delta is seen as well as a
+    wrong element.
+
+    bound: the build uses -ffp-contract=off, so every operation of the element type T rounds once, relative error at most
+    u = u_T; the three sums are accumulated in double in an order the kernel is free to choose and rounded once to T, so each
+    is within a sum |terms| + u |sum| of the exact sum OF THE TERMS IT WAS GIVEN, a = (n + 2) 2^-53 (see ``sum_bound``).  Hats
+    are the device's values.
+      ov^ :  |ov^ - ov| <= a Sov + u |ov| = e_ov                                                 (Sov = sum |d dg|)
+      s^_i = T(d_i T(1 / ov^)) = s_i (ov / ov^) (1 + e1)(1 + e2):  |s^_i - s_i| <= rho |s_i|,  rho = e_ov / |ov| + 2 u
+      t^_i:  |t^_i - t_i| <= a St_i + u |t_i| = tau_i                                            (St_i = sum_j |H0_ij dg_j|)
+      q^ = T(sum dg_i t^_i): the terms carry tau, the sum its own error: e_q = a Sq + sum |dg_i| tau_i + u |q|   (Sq = sum |dg t|)
+      delta^ = T(T(lam ov^) + q^): |lam| e_ov + u |lam ov| from the product, e_q, and u |delta| <= u (|lam ov| + |q|) from the
+               sum: e_delta = |lam| e_ov + e_q + 2 u (|lam ov| + |q|) (+ lam_rel |lam ov| for a lam known to lam_rel only)
+    and for the element, with P = |delta s_i s_j|, Q = |t_i s_j| + |s_i t_j|:
+      T(s^_i s^_j)               relative 2 rho + u
+      T(delta^ . )               |s_i s_j| e_delta + (2 rho + 2 u) P
+      T(t^_i s^_j), T(s^_i t^_j) tau_i |s_j| + tau_j |s_i| + (rho + u) Q
+      their sum                  + u Q
+      the difference             + u (P + Q)
+      the sum into H0            + u (|H0_ij| + P + Q)
+    in all  |s_i s_j| (e_delta + 2 rho |delta|) + tau_i |s_j| + tau_j |s_i| + rho Q + u (|H0_ij| + 4 P + 4 Q), and the last
+    term is rounded up to 4 u (|H0_ij| + P + Q): the three spare u |H0_ij| stand for the second-order terms.  The bound is
+    symmetric in i and j, as the expression is."""
+    n = d.size
+    u = LD(unit_roundoff(dtype))
+    a = (n + 2) * LD(2.0) ** -53
+    H, dl, yl, lam = H0.astype(LD), d.astype(LD), dg.astype(LD), LD(lam)
+    ov_terms = dl * yl
+    ov, Sov = ov_terms.sum(), np.abs(ov_terms).sum()
+    t_terms = H * yl[None, :]
+    t, St = t_terms.sum(axis=1), np.abs(t_terms).sum(axis=1)
+    q_terms = yl * t
+    q, Sq = q_terms.sum(), np.abs(q_terms).sum()
+    delta = lam * ov + q
+    s = dl / ov
+    e_ov = a * Sov + u * abs(ov)
+    rho = e_ov / abs(ov) + 2 * u
+    tau = a * St + u * np.abs(t)
+    e_q = a * Sq + (np.abs(yl) * tau).sum() + u * abs(q)
+    e_delta = abs(lam) * e_ov + e_q + 2 * u * (abs(lam * ov) + abs(q)) + LD(lam_rel) * abs(lam * ov)
+    ss = np.multiply.outer(s, s)
+    ts, st = np.multiply.outer(t, s), np.multiply.outer(s, t)
+    exact = H + (delta * ss - (ts + st))
+    sa = np.abs(s)
+    Q = np.abs(ts) + np.abs(st)
+    bound = np.abs(ss) * (e_delta + 2 * rho * abs(delta)) + np.multiply.outer(tau, sa) + np.multiply.outer(sa, tau) + rho * Q \
+        + 4 * u * (np.abs(H) + np.abs(delta * ss) + Q)
+    return exact, np.maximum(bound, bound.T)                  # (equal up to the order of the longdouble sums behind them)
+
+
+def overlap_cancellation(d, dg):
+    """sum |d dg| / |sum d dg|: how much of the overlap's terms cancels (every bound and window above grows with it)."""
+    terms = d.astype(LD) * dg.astype(LD)
+    return float(np.abs(terms).sum() / abs(terms.sum())) if terms.sum() != 0 else float("inf")
+
+
+def t_rounded(H0, dg, dtype=np.float32):
+    """fp32: (t, undecided).  The batched kernel's t = H0*dg is a sum accumulated in double and rounded ONCE to fp32.  The
+    products of two floats are exact in double, the double sum is within a St_i = (n + 2) 2^-53 sum_j |H0_ij dg_j| of the exact
+    one in any order, and rounding is monotone: the device's t_i is the rounding of the exact sum (here: the longdouble sum,
+    whose own n 2^-64 St_i the + 2 of a covers) unless a tie between two neighbouring floats lies within a St_i of it.
+    Such rows are ``undecided``: a list of (row, the other candidate), the neighbour of t[row] across that tie."""
+    assert np.dtype(dtype) == np.float32 and H0.dtype == np.float32 and dg.dtype == np.float32
+    n = dg.size
+    exact, S = exact_matvec(H0, dg)
+    t = exact.astype(np.float32)
+    w = (n + 2) * LD(2.0) ** -53 * S
+    undecided = []
+    for other in (np.nextafter(t, np.float32(-np.inf)), np.nextafter(t, np.float32(np.inf))):
+        tie = (t.astype(LD) + other.astype(LD)) / 2
+        for i in np.nonzero(np.abs(exact - tie) <= w)[0]:
+            undecided.append((int(i), other[i]))
+    return t, undecided
+
+
+def replay_update_undecided(H0, d, dg, t, undecided, H_new, **kw):
+    """``replay_update`` over the 2^k values t can have when k of its rows are undecided (``t_rounded``); the first that
+    reproduces H_new, else the last failure."""
+    assert len(undecided) <= UNDECIDED_CAP, undecided
+    r = None
+    for mask in range(1 << len(undecided)):
+        tt = t.copy()
+        for k, (i, other) in enumerate(undecided):
+            if mask >> k & 1:
+                tt[i] = other
+        r = replay_update(H0, d, dg, tt, H_new, **kw)
+        if r.ok:
+            return r
+    return r
+
+
+def batch_start(orc, n, dtype, k, b, quadratic=False):
+    """start of instance b on trajectory k (``orc``: the oracle module; this one stays free of it)."""
+    x = orc.pcg_fill(n, BATCH_SEEDS[k] + b)
+    return (x - 0.5 if quadratic else x).astype(dtype)
+
+
+def batch_matrix(orc, n, b, dtype, r=8):
+    """A_b = D_b + U_b U_b'/r (positive definite, symmetric bit for bit), a different one per instance."""
+    dvec = 1.0 + (9.0 + 30.0 * b) * orc.pcg_fill(n, 20 + b)
+    U = (orc.pcg_fill(n * r, 40 + b) - 0.5).reshape(n, r, order="F")
+    A = (U @ U.T) / r
+    A[np.diag_indices(n)] += dvec
+    return np.ascontiguousarray((0.5 * (A + A.T)).astype(dtype))
+
+
+def batch_steps(n):
+    """steps a trajectory is followed for: the first is the update of H = I, the later ones of a dense H."""
+    return 2 if n >= 512 else 3

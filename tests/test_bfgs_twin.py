@@ -1,7 +1,9 @@
 """tests/bfgs_twin.py against things it does not depend on: the replay checker must accept the CPU oracle's
 ``update_inverse_hessian!`` at every full-storage shape of the GPU tests and reject five kinds of subtly wrong result; the sum
 bound must hold for a double-accumulated product and fail when one term is missing; the path functions must say what the
-launchers of csrc/dzo_bfgs.hip say.  No GPU."""
+launchers of csrc/dzo_bfgs.hip say.  For the batched kernel of csrc/dzo_batch.hip: the shape table against the source, the
+elementwise bound of the update (it accepts a numpy evaluation with its sums in three orders, it rejects four planted errors at a
+single element), and the cap on the rows of t whose fp32 rounding the replay has to search.  No GPU."""
 import os
 import re
 
@@ -199,3 +201,166 @@ def test_path_functions_restate_the_launchers():
     assert all(tw.takes_tri(n, dt, 2) for n in tw.TRI for dt in (np.float32, np.float64))
     assert not any(tw.takes_tri(n, np.float64) for n in tw.FULL_F64 + tw.TRI)         # the default keeps them on full storage
     assert all(n % 16 == 0 for n in tw.MFMA) and [n // 16 for n in tw.MFMA] == [1, 3, 5, 7, 16]
+
+
+# ------------------------------------------------------------------------------ the batched kernel (csrc/dzo_batch.hip)
+F64, F32 = np.float64, np.float32
+STEP_BFGS = 2
+
+
+def test_batch_form_restates_the_source_at_every_table_entry():
+    """rp, the wide form, UJ and the LDS request as batch_create_impl and batch_step_kernel state them (whole lines of the
+    source: a change there has to change bfgs_twin.batch_form knowingly), the form each entry of BATCH is listed under, and the
+    table's promise: the first and last size of every form and both sides of both 48 KiB edges."""
+    src = _source("dzo_batch.hip")
+    assert "b->rp = n <= 256 ? 1 : (n <= 512 ? 2 : 4);" in src
+    assert 'b->wide = (b->rp == 2 && n > tune_env("DZO_TUNE_BATCH_RP2_WIDE_ABOVE", 448)) ? 1 : 0;' in src
+    assert "b->lds_bytes = 9 * np * es + (5 * np + 16) * sizeof(double) + 16;" in src
+    assert "constexpr int UJ = RP == 1 ? 4 : (RP == 2 ? (WIDE ? 4 : 2) : 2);" in src
+    assert "if (b->lds_bytes > 48 * 1024) {" in src
+    stated = {"rp1": [2, 4, 6, 8, 10, 14, 16, 18, 30, 32, 34, 62, 64, 66, 126, 128, 130, 254, 256],
+              "rp2 narrow": [258, 260, 262, 264, 266, 384, 436, 438, 446, 448],
+              "rp2 wide": [450, 510, 512],
+              "rp4": [514, 516, 644, 646, 768, 770, 1022, 1024]}
+    assert tw.BATCH == sum((stated[f] for f in tw.BATCH_FORMS), [])
+    want = {"rp1": (1, False, 4), "rp2 narrow": (2, False, 2), "rp2 wide": (2, True, 4), "rp4": (4, False, 2)}
+    for dtype, es in ((F64, 8), (F32, 4)):
+        for name, sizes in stated.items():
+            for n in sizes:
+                f = tw.batch_form(n, dtype)
+                assert (f.rp, f.wide, f.uj) == want[name] and tw.batch_form_name(n, dtype) == name, (n, f)
+                assert f.lds_bytes == 9 * n * es + (5 * n + 16) * 8 + 16 and f.needs_attribute == (f.lds_bytes > 49152)
+                assert n <= 256 * f.rp                                      # every row pair has a thread
+        # first and last size of each form: the even n either side of it takes another form
+        for name, sizes in stated.items():
+            lo, hi = sizes[0], sizes[-1]
+            assert lo == 2 or tw.batch_form_name(lo - 2, dtype) != name
+            assert hi == 1024 or tw.batch_form_name(hi + 2, dtype) != name
+        # the attribute edge: the last size without and the first with it are both in the table
+        edge = [n for n in range(2, 1026, 2) if tw.batch_form(n, dtype).needs_attribute][0]
+        assert edge == (438 if dtype == F64 else 646) and edge in tw.BATCH and edge - 2 in tw.BATCH
+    assert [tw.batch_form_name(n, F64) for n in tw.BATCH_ONE_PER_FORM] == list(tw.BATCH_FORMS)
+    assert all(n in tw.BATCH for n in tw.BATCH_ONE_PER_FORM)
+
+
+def _batch_oracle(n, dtype, k, b, quadratic):
+    if quadratic:
+        prob = orc.Problem(orc.QUADRATIC, n, dtype, A=tw.batch_matrix(orc, n, b, dtype))
+    else:
+        prob = orc.Problem(orc.ROSENBROCK_CHAIN, n, dtype)
+    return orc.BFGS(prob, tw.batch_start(orc, n, dtype, k, b, quadratic), 1.0)
+
+
+def _batch_oracle_updates(n, dtype, k, b, quadratic=False, steps=None):
+    """(H0, d, dg, lam) of every BFGS step of one oracle trajectory; lam = T(-last_step_length / ||d||), close to the oracle's."""
+    ref = _batch_oracle(n, dtype, k, b, quadratic)
+    out = []
+    for _ in range(tw.batch_steps(n) if steps is None else steps):
+        if ref.has_terminated:
+            break
+        H0, d = np.ascontiguousarray(ref.approximate_inverse_hessian), ref.next_step_direction.copy()
+        ref.step()
+        if ref.last_step_type == STEP_BFGS and not ref.has_terminated:
+            lam = dtype(-LD(ref.last_step_length) / LD(tw.device_norm(d)))
+            out.append((H0, d, ref.delta_gradient.copy(), lam))
+    return out
+
+
+def _sum_forward(a):
+    return np.cumsum(a, axis=-1)[..., -1]
+
+
+def _sum_reversed(a):
+    return np.cumsum(a[..., ::-1], axis=-1)[..., -1]
+
+
+def _sum_halves(a):
+    m = a.shape[-1]
+    return a[..., 0] if m == 1 else _sum_halves(a[..., :m // 2]) + _sum_halves(a[..., m // 2:])
+
+
+def _as_the_kernel(H0, d, dg, lam, wide_sum):
+    """The update in numpy as the batched kernel evaluates it: the three sums in double (``wide_sum`` gives the order) rounded
+    once to T, every other operation in T.  Returns (H_new, s, t, delta)."""
+    T = H0.dtype.type
+    D = np.float64
+    t = wide_sum(H0.astype(D) * dg.astype(D)[None, :]).astype(T)
+    overlap = T(wide_sum(d.astype(D) * dg.astype(D)))
+    dgt = T(wide_sum(dg.astype(D) * t.astype(D)))
+    inv = T(1) / overlap
+    delta = lam * overlap + dgt
+    s = d * inv
+    return tw.update_expression(H0, s, t, delta), s, t, delta
+
+
+@pytest.mark.parametrize("quadratic", [False, True], ids=["rosenbrock", "quadratic"])
+@pytest.mark.parametrize("dtype", [F64, F32])
+@pytest.mark.parametrize("n", [6, 130, 258, 514])
+def test_batch_update_bound_accepts_three_summation_orders_and_rejects_four_planted_errors(n, dtype, quadratic):
+    ups = _batch_oracle_updates(n, dtype, 0, 0, quadratic, steps=3)
+    assert len(ups) >= 2
+    worst, seen = 0.0, {k: 0.0 for k in ("left out", "twice", "t from j + 1", "partner of the straddling pair")}
+    for H0, d, dg, lam in ups:
+        if tw.overlap_cancellation(d, dg) > 100:
+            continue
+        exact, bound = tw.batch_update_bound(H0, d, dg, lam, dtype)
+        assert np.array_equal(bound, bound.T) and (bound > 0).all()
+        for wide_sum in (_sum_forward, _sum_reversed, _sum_halves):
+            H_new, s, t, delta = _as_the_kernel(H0, d, dg, lam, wide_sum)
+            ratio = float((np.abs(H_new.astype(LD) - exact) / bound).max())
+            worst = max(worst, ratio)
+            assert ratio <= 1.0, (n, wide_sum.__name__, ratio)
+        # one lower-triangle element of the (last, pairwise) result wrong in four ways, each at the element where it shows best
+        lower = np.tril(np.ones((n, n), bool), -1)
+        t_next = np.roll(t, -1)                                                # t_{j + 1} in place of t_j (the last column wraps)
+        shifted = H0 + (delta * np.multiply.outer(s, s) - (np.multiply.outer(t, s) + np.multiply.outer(s, t_next)))
+        sub = np.zeros((n, n), bool)
+        sub[np.arange(1, n, 2), np.arange(0, n - 1, 2)] = True                  # (j, j - 1), j odd: the partner of the pair (j - 1, j)
+        plants = {"left out": (H0, lower), "twice": (H_new + (H_new - H0), lower), "t from j + 1": (shifted, lower),
+                  "partner of the straddling pair": (H0, sub)}
+        for name, (wrong, where) in plants.items():
+            score = np.where(where, np.abs(wrong.astype(LD) - H_new.astype(LD)) / bound, 0)
+            i, j = np.unravel_index(int(np.argmax(score)), score.shape)
+            M = H_new.copy()
+            M[i, j] = wrong[i, j]
+            over = np.abs(M.astype(LD) - exact) > bound
+            assert over[i, j] and over.sum() == 1, (n, name, i, j, float(score[i, j]))
+            seen[name] = max(seen[name], float((score[where] > 2).mean()))
+    assert worst > 0
+    print(f"\nn={n} {np.dtype(dtype).name} {'quadratic' if quadratic else 'rosenbrock'}: worst error/bound over three orders {worst:.3f}; "
+          + "share of the elements at which it is seen for certain: " + ", ".join(f"{k} {v:.2f}" for k, v in seen.items()))
+
+
+@pytest.mark.parametrize("n", tw.BATCH)
+def test_undecided_rows_of_t_stay_under_the_cap_on_the_trajectories_of_the_gpu_test(n):
+    """The fp32 replay searches 2^k values of t for k undecided rows: k <= UNDECIDED_CAP at every step of every trajectory the
+    GPU test follows (expected: about n 2^-29 per row, so none).  And t_rounded does report a row that sits on a tie."""
+    most = 0
+    orc.set_dot_mode(orc.DOT_WIDE)                                            # as the GPU test runs the fp32 oracle
+    try:
+        for k in range(len(tw.BATCH_SEEDS)):
+            for b in (0, 2):
+                for H0, d, dg, lam in _batch_oracle_updates(n, F32, k, b):
+                    t, undecided = tw.t_rounded(H0, dg)
+                    most = max(most, len(undecided))
+                    assert len(undecided) <= tw.UNDECIDED_CAP, (n, k, b, undecided)
+    finally:
+        orc.set_dot_mode(orc.DOT_SEQUENTIAL)
+    print(f"\nn={n}: at most {most} undecided rows per step")
+
+
+def test_t_rounded_reports_a_tie_and_the_replay_searches_it():
+    H0 = np.array([[1, 2.0 ** -24], [2.0 ** -24, 1]], F32)                      # row 0: 1 + 2^-24, exactly between 1 and 1 + 2^-23
+    dg = np.array([1, 1], F32)
+    t, undecided = tw.t_rounded(H0, dg)
+    assert t[0] == F32(1) and len(undecided) == 2 and undecided[0][0] in (0, 1)
+    assert {(i, float(v)) for i, v in undecided} == {(0, 1 + 2.0 ** -23), (1, 1 + 2.0 ** -23)}
+    d = np.array([0.5, 0.25], F32)
+    lam = F32(-0.5)
+    for t_dev in (np.array([1, 1], F32), np.array([1 + 2.0 ** -23, 1], F32), np.array([1 + 2.0 ** -23, 1 + 2.0 ** -23], F32)):
+        overlap = F32(d @ dg)
+        H_new = tw.update_expression(H0, d * (F32(1) / overlap), t_dev, lam * overlap + F32(dg @ t_dev))
+        assert tw.replay_update_undecided(H0, d, dg, t, undecided, H_new, lam=lam).ok
+    H_bad = H_new.copy()
+    H_bad[1, 0] = np.nextafter(H_bad[1, 0], F32(9))
+    assert not tw.replay_update_undecided(H0, d, dg, t, undecided, H_bad, lam=lam).ok

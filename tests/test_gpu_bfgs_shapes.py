@@ -14,7 +14,7 @@ is exact to n 2^-53, so the error is the final rounding to fp32 alone, up to hal
 equals that when all terms of a row have one sign.  A correct kernel cannot exceed it for any seed; fp64 sits at 0.1 - 0.3.
 
 Not covered, on purpose: DZO_TUNE_BFGS_COLS = 8 / 16 (read once per process), the n >= 65535 * 4 branch of step! (H would not
-fit), the batched kernel of dzo_batch.hip, the line searches."""
+fit), the line searches.  The batched kernel of dzo_batch.hip has its own file, tests/test_gpu_bfgs_batch_shapes.py."""
 import numpy as np
 import pytest
 
