@@ -633,29 +633,30 @@ def pairwise_batch_energy_gradient(points, n_particles, gradients=None, radial=R
     return e.to_host()
 
 
-class BatchedLBFGS(_HandleArrays):
-    """``LBFGSOptimizer`` (src/DZOptimization.jl:321-509, no constraint) of many small Lennard-Jones clusters at once:
-    ``step(k)`` runs k calls of ``step!()`` of every instance in ONE launch.  ``points`` is a DeviceArray of
-    ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
-    ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
-    _read_fn, _ptr_fn = "dzo_lbfgs_batch_read", "dzo_lbfgs_batch_get_ptr"
+class _BatchedOptimizer(_HandleArrays):
+    """What ``BatchedLBFGS`` and ``BatchedAdGD`` share.  A subclass names the prefix of its entry points (``_prefix``) and the
+    ``what`` constants of the arrays both have (``_what``: property name -> constant), calls ``_create`` with the arguments
+    that follow ``points`` in its ``create`` entry, and has ``_shape(what)``."""
+    _prefix = None
+    _what = {}
 
-    def __init__(self, points, n_particles, initial_step_length, history_length, radial=RADIAL_LENNARD_JONES):
+    def _fn(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    def _create(self, points, n_particles, radial, *args):
         _need_init()
         self.points = points
         self.dtype = points.dtype
         self.n_particles = int(n_particles)
         self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
         assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
-        self.history_length = int(history_length)
         h = C.c_void_p()
-        _check(lib().dzo_lbfgs_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, float(initial_step_length),
-                                            self.history_length, C.byref(h)))
+        _check(self._fn("create")(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, *args, C.byref(h)))
         self.h = h
 
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_lbfgs_batch_destroy(self.h)
+            self._fn("destroy")(self.h)
         self.h = None
 
     def __del__(self):
@@ -665,22 +666,49 @@ class BatchedLBFGS(_HandleArrays):
             pass
 
     def set_max_halvings(self, v):
-        _check(lib().dzo_lbfgs_batch_set_max_halvings(self.h, int(v)))
+        _check(self._fn("set_max_halvings")(self.h, int(v)))
 
     def step(self, steps=1, wait=True):
         """``steps`` calls of ``step!()`` of every instance that is not stuck.  ``wait=True``: blocks and returns whether all
         instances are stuck; ``wait=False``: enqueues only and returns None."""
         if not wait:
-            _check(lib().dzo_lbfgs_batch_step(self.h, int(steps), None))
+            _check(self._fn("step")(self.h, int(steps), None))
             return None
         flag = C.c_int32(0)
-        _check(lib().dzo_lbfgs_batch_step(self.h, int(steps), C.byref(flag)))
+        _check(self._fn("step")(self.h, int(steps), C.byref(flag)))
         return bool(flag.value)
 
     def count_active(self):
         n = C.c_int64(0)
-        _check(lib().dzo_lbfgs_batch_count_active(self.h, C.byref(n)))
+        _check(self._fn("count_active")(self.h, C.byref(n)))
         return int(n.value)
+
+    current_points = property(lambda self: self.read(self._what["current_points"]))
+    current_gradients = property(lambda self: self.read(self._what["current_gradients"]))
+    current_objective_values = property(lambda self: self.read(self._what["current_objective_values"]))
+    delta_points = property(lambda self: self.read(self._what["delta_points"]))
+    delta_gradients = property(lambda self: self.read(self._what["delta_gradients"]))
+    delta_objective_values = property(lambda self: self.read(self._what["delta_objective_values"]))
+    is_stuck = property(lambda self: self.read(self._what["is_stuck"]).astype(bool))
+    iteration_counts = property(lambda self: self.read(self._what["iteration_counts"]))
+    last_halvings = property(lambda self: self.read(self._what["last_halvings"]))
+
+
+class BatchedLBFGS(_BatchedOptimizer):
+    """``LBFGSOptimizer`` (src/DZOptimization.jl:321-509, no constraint) of many small Lennard-Jones clusters at once:
+    ``step(k)`` runs k calls of ``step!()`` of every instance in ONE launch.  ``points`` is a DeviceArray of
+    ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
+    ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
+    _prefix = "dzo_lbfgs_batch_"
+    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
+    _what = dict(current_points=LBFGS_BATCH_POINTS, current_gradients=LBFGS_BATCH_GRADIENTS, current_objective_values=LBFGS_BATCH_OBJECTIVES,
+                 delta_points=LBFGS_BATCH_DELTA_POINTS, delta_gradients=LBFGS_BATCH_DELTA_GRADIENTS,
+                 delta_objective_values=LBFGS_BATCH_DELTA_OBJECTIVES, is_stuck=LBFGS_BATCH_IS_STUCK,
+                 iteration_counts=LBFGS_BATCH_ITERATION_COUNTS, last_halvings=LBFGS_BATCH_LAST_HALVINGS)
+
+    def __init__(self, points, n_particles, initial_step_length, history_length, radial=RADIAL_LENNARD_JONES):
+        self.history_length = int(history_length)
+        self._create(points, n_particles, radial, float(initial_step_length), self.history_length)
 
     def _shape(self, what):
         b, n3, m = self.batch, 3 * self.n_particles, self.history_length
@@ -692,17 +720,8 @@ class BatchedLBFGS(_HandleArrays):
                 LBFGS_BATCH_Y: ((b, m, n3), self.dtype), LBFGS_BATCH_RHO: ((b, m), np.float64),
                 LBFGS_BATCH_LAST_HALVINGS: ((b,), np.int32)}[what]
 
-    current_points = property(lambda self: self.read(LBFGS_BATCH_POINTS))
-    current_gradients = property(lambda self: self.read(LBFGS_BATCH_GRADIENTS))
-    current_objective_values = property(lambda self: self.read(LBFGS_BATCH_OBJECTIVES))
     step_directions = property(lambda self: self.read(LBFGS_BATCH_DIRECTIONS))
-    delta_points = property(lambda self: self.read(LBFGS_BATCH_DELTA_POINTS))
-    delta_gradients = property(lambda self: self.read(LBFGS_BATCH_DELTA_GRADIENTS))
-    delta_objective_values = property(lambda self: self.read(LBFGS_BATCH_DELTA_OBJECTIVES))
-    is_stuck = property(lambda self: self.read(LBFGS_BATCH_IS_STUCK).astype(bool))
-    iteration_counts = property(lambda self: self.read(LBFGS_BATCH_ITERATION_COUNTS))
     history_counts = property(lambda self: self.read(LBFGS_BATCH_HISTORY_COUNTS))
-    last_halvings = property(lambda self: self.read(LBFGS_BATCH_LAST_HALVINGS))
 
 
 # ------------------------------------------------------------------------------ batched AdGD over Lennard-Jones clusters
@@ -712,53 +731,20 @@ ADGD_BATCH_MAX_PARTICLES = 1024
  ADGD_BATCH_PREVIOUS_STEP_SIZES, ADGD_BATCH_LAST_HALVINGS) = range(11)
 
 
-class BatchedAdGD(_HandleArrays):
+class BatchedAdGD(_BatchedOptimizer):
     """``AdGDOptimizer`` (src/DZOptimization.jl:179-312, no constraint) of many small Lennard-Jones clusters at once:
     ``step(k)`` runs k calls of ``step!()`` of every instance in ONE launch.  ``points`` is a DeviceArray of
     ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
     ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
-    _read_fn, _ptr_fn = "dzo_adgd_batch_read", "dzo_adgd_batch_get_ptr"
+    _prefix = "dzo_adgd_batch_"
+    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
+    _what = dict(current_points=ADGD_BATCH_POINTS, current_gradients=ADGD_BATCH_GRADIENTS, current_objective_values=ADGD_BATCH_OBJECTIVES,
+                 delta_points=ADGD_BATCH_DELTA_POINTS, delta_gradients=ADGD_BATCH_DELTA_GRADIENTS,
+                 delta_objective_values=ADGD_BATCH_DELTA_OBJECTIVES, is_stuck=ADGD_BATCH_IS_STUCK,
+                 iteration_counts=ADGD_BATCH_ITERATION_COUNTS, last_halvings=ADGD_BATCH_LAST_HALVINGS)
 
     def __init__(self, points, n_particles, initial_step_length, radial=RADIAL_LENNARD_JONES):
-        _need_init()
-        self.points = points
-        self.dtype = points.dtype
-        self.n_particles = int(n_particles)
-        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
-        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
-        h = C.c_void_p()
-        _check(lib().dzo_adgd_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, float(initial_step_length),
-                                           C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_adgd_batch_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_max_halvings(self, v):
-        _check(lib().dzo_adgd_batch_set_max_halvings(self.h, int(v)))
-
-    def step(self, steps=1, wait=True):
-        """``steps`` calls of ``step!()`` of every instance that is not stuck.  ``wait=True``: blocks and returns whether all
-        instances are stuck; ``wait=False``: enqueues only and returns None."""
-        if not wait:
-            _check(lib().dzo_adgd_batch_step(self.h, int(steps), None))
-            return None
-        flag = C.c_int32(0)
-        _check(lib().dzo_adgd_batch_step(self.h, int(steps), C.byref(flag)))
-        return bool(flag.value)
-
-    def count_active(self):
-        n = C.c_int64(0)
-        _check(lib().dzo_adgd_batch_count_active(self.h, C.byref(n)))
-        return int(n.value)
+        self._create(points, n_particles, radial, float(initial_step_length))
 
     def _shape(self, what):
         b, n3 = self.batch, 3 * self.n_particles
@@ -768,17 +754,8 @@ class BatchedAdGD(_HandleArrays):
                 ADGD_BATCH_ITERATION_COUNTS: ((b,), np.int64), ADGD_BATCH_CURRENT_STEP_SIZES: sc,
                 ADGD_BATCH_PREVIOUS_STEP_SIZES: sc, ADGD_BATCH_LAST_HALVINGS: ((b,), np.int32)}[what]
 
-    current_points = property(lambda self: self.read(ADGD_BATCH_POINTS))
-    current_gradients = property(lambda self: self.read(ADGD_BATCH_GRADIENTS))
-    delta_points = property(lambda self: self.read(ADGD_BATCH_DELTA_POINTS))
-    delta_gradients = property(lambda self: self.read(ADGD_BATCH_DELTA_GRADIENTS))
-    current_objective_values = property(lambda self: self.read(ADGD_BATCH_OBJECTIVES))
-    delta_objective_values = property(lambda self: self.read(ADGD_BATCH_DELTA_OBJECTIVES))
-    is_stuck = property(lambda self: self.read(ADGD_BATCH_IS_STUCK).astype(bool))
-    iteration_counts = property(lambda self: self.read(ADGD_BATCH_ITERATION_COUNTS))
     current_step_sizes = property(lambda self: self.read(ADGD_BATCH_CURRENT_STEP_SIZES))
     previous_step_sizes = property(lambda self: self.read(ADGD_BATCH_PREVIOUS_STEP_SIZES))
-    last_halvings = property(lambda self: self.read(ADGD_BATCH_LAST_HALVINGS))
 
 
 # ------------------------------------------------------------------------------ batched Hessians of Lennard-Jones clusters

@@ -2,7 +2,7 @@
 // accelerated_pairwise_radial_hvp! (src/ExampleFunctions.jl:367-468) with lj_second_derivative (:50-72) of every instance in one
 // launch, and the dense 3N x 3N Hessian of every instance from one pass over its pairs.
 //
-// The launch shapes are the quench's (dzo_lbfgs_batch.hip):
+// The launch shapes are those of dzo_cluster.h, which also holds the dots and the block sum used here:
 //
 //   * WAVE shape (N <= 64): one wave per instance (a block of 64 threads).  Lane i holds particle i and its direction in
 //     registers; particle j arrives from lane j through v_readlane, four independent pairs per trip.  No barrier, no LDS.
@@ -11,8 +11,8 @@
 //
 // Per pair the arithmetic is pw_pair<T, F, kPwHvp> of dzo_pairwise.h and nothing else: the self term and the padding are
 // dropped by its select.  The row sum of particle i runs j = 0 .. N-1 sequentially in T from +0 and is doubled once, the order
-// of the quench's gradient.  u.Hu and u.u are fp64 dots: per particle like the quench's dots (a product and two fused
-// multiply-adds), a thread's particles in order, then the wave tree, then the block's four wave sums in wave order.
+// of the quench's gradient.  u.Hu and u.u are fp64 dots: per particle cl_dot3 (a product and two fused multiply-adds), a
+// thread's particles in order, then the wave tree, then the block's four wave sums in wave order (cl_block_sum2).
 //
 // The Hessian kernels do not run 3N products.  Column (b, j) of the Hessian is the product with the unit direction e_(b,j), and
 // in that product every pair term but one is an exact zero (du = dv = dw = 0 gives overlap = 0, g = 0 and a term 0 * f + 0 * d):
@@ -27,12 +27,14 @@
 // are stored once at the end.  For a fixed column and row component the lanes' addresses a N + i are consecutive: every store
 // instruction of the pair loop is coalesced.  The kernel is bound by its writes, 9 N^2 elements per instance against N^2 pair
 // terms.  Nothing is accumulated in memory: an entry is written once, by one lane.
+#include "dzo_cluster.h"
 #include "dzo_pairwise.h"
 
 namespace dzo {
 
 constexpr int kHessMaxN = DZO_HESSIAN_BATCH_MAX_PARTICLES;
 constexpr int kHessPer = kHessMaxN / kBlock;                 // particles a thread of the BLOCK shape owns at most
+static_assert(kHessMaxN == kClMaxN, "the argument checks of dzo_cluster.h state the particle bound");
 
 template <typename T> struct HessBatchArgs {
     int N;
@@ -42,26 +44,6 @@ template <typename T> struct HessBatchArgs {
     T *out;                    // hvp: products (3N, batch); hessian: (3N, 3N, batch), column-major per instance
     double *curv;              // hvp: (2, batch) u.Hu and u.u, or null
 };
-
-// a lane's / thread's share of a dot over one particle, in fp64
-template <typename T> __device__ __forceinline__ double hb_dot3(T ax, T ay, T az, T bx, T by, T bz) {
-    double p = (double)ax * (double)bx;
-    p = __builtin_fma((double)ay, (double)by, p);
-    return __builtin_fma((double)az, (double)bz, p);
-}
-
-// two block-wide sums behind one barrier, valid in every thread: wave trees, then the four waves in wave order.  `red` holds
-// 2 * kWaves doubles; called once per kernel.
-__device__ __forceinline__ void hb_block_sum2(double &v0, double &v1, double *red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const double w0 = wave_sum_all(v0), w1 = wave_sum_all(v1);
-    if (lane == 0) { red[wv] = w0; red[kWaves + wv] = w1; }
-    __syncthreads();
-    double r0 = 0, r1 = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) { r0 += red[k]; r1 += red[kWaves + k]; }
-    v0 = r0; v1 = r1;
-}
 
 // ------------------------------------------------------------------------------ products, WAVE shape: grid batch, block 64
 template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hvp_kernel(HessBatchArgs<T> a) {
@@ -84,8 +66,8 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void hess_bat
     const T px = live ? pw_twice(ax) : T(0), py = live ? pw_twice(ay) : T(0), pz = live ? pw_twice(az) : T(0);   // :421-423
     if (live) { a.out[base + lane] = px; a.out[base + N + lane] = py; a.out[base + 2 * N + lane] = pz; }
     if (!a.curv) return;                                     // the same in every lane
-    const double uhu = wave_sum_all(hb_dot3(pi.u, pi.v, pi.w, px, py, pz));
-    const double uu = wave_sum_all(hb_dot3(pi.u, pi.v, pi.w, pi.u, pi.v, pi.w));
+    const double uhu = wave_sum_all(cl_dot3(pi.u, pi.v, pi.w, px, py, pz));
+    const double uu = wave_sum_all(cl_dot3(pi.u, pi.v, pi.w, pi.u, pi.v, pi.w));
     if (lane == 0) { a.curv[2 * b] = uhu; a.curv[2 * b + 1] = uu; }
 }
 
@@ -115,12 +97,12 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess
             }
             const T px = pw_twice(ax), py = pw_twice(ay), pz = pw_twice(az);
             a.out[base + i] = px; a.out[base + N + i] = py; a.out[base + 2 * N + i] = pz;
-            uhu += hb_dot3(pi.u, pi.v, pi.w, px, py, pz);
-            uu += hb_dot3(pi.u, pi.v, pi.w, pi.u, pi.v, pi.w);
+            uhu += cl_dot3(pi.u, pi.v, pi.w, px, py, pz);
+            uu += cl_dot3(pi.u, pi.v, pi.w, pi.u, pi.v, pi.w);
         }
     }
     if (!a.curv) return;                                     // the same in every thread
-    hb_block_sum2(uhu, uu, red);
+    cl_block_sum2(uhu, uu, red);
     if (tid == 0) { a.curv[2 * b] = uhu; a.curv[2 * b + 1] = uu; }
 }
 
@@ -230,10 +212,6 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess
 }
 
 // ------------------------------------------------------------------------------ host side
-static int32_t hb_check_common(int32_t radial, int64_t N, int64_t batch, int32_t dtype) {
-    return pw_check_args(radial, dtype, N, batch, "batch", kHessMaxN, DZO_ERR_UNSUPPORTED, "the batched kernels hold an instance in one block");
-}
-
 template <typename T> static void hb_launch_hvp(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
     if (a.N <= 64) hipLaunchKernelGGL((hess_batch_wave_hvp_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((hess_batch_block_hvp_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
@@ -255,7 +233,7 @@ int32_t dzo_pairwise_batch_hvp(int32_t radial, int64_t n_particles, int64_t batc
                                const void *directions_dev, void *products_dev, double *curvatures_dev) {
     DZO_TRY(require_init());
     DZO_REQUIRE(points_dev && directions_dev && products_dev, DZO_ERR_INVALID, "null argument");
-    DZO_TRY(hb_check_common(radial, n_particles, batch, dtype));
+    DZO_TRY(cl_check_args(radial, n_particles, batch, dtype));
     DZO_REQUIRE(point_stride == 0 || point_stride >= 3 * n_particles, DZO_ERR_INVALID,
                 "point_stride must be 0 (one shared point) or at least 3 n_particles = %lld (got %lld)", (long long)(3 * n_particles),
                 (long long)point_stride);
@@ -278,7 +256,7 @@ int32_t dzo_pairwise_batch_hvp(int32_t radial, int64_t n_particles, int64_t batc
 int32_t dzo_pairwise_batch_hessian(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, const void *points_dev, void *hessians_dev) {
     DZO_TRY(require_init());
     DZO_REQUIRE(points_dev && hessians_dev, DZO_ERR_INVALID, "null argument");
-    DZO_TRY(hb_check_common(radial, n_particles, batch, dtype));
+    DZO_TRY(cl_check_args(radial, n_particles, batch, dtype));
     DZO_TRY(require_same_backend("accelerated_pairwise_radial_hvp!", "src/ExampleFunctions.jl:453-461", points_dev, "points", hessians_dev, "hessians"));
     Context &c = ctx();
     {

@@ -24,8 +24,8 @@ int32_t pw_check_args(int32_t radial, int32_t dtype, int64_t n_particles, int64_
 // `bytes` of a handle's array to or from the host on the current context's stream; returns when they have arrived
 int32_t copy_blocking(void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
 
-// The device pieces below are shared by dzo_pairwise.hip, dzo_tempering.hip, dzo_lbfgs_batch.hip and dzo_hessian_batch.hip (one
-// definition, the same bits in all of them).
+// The device pieces below are shared by dzo_pairwise.hip, dzo_tempering.hip, dzo_hessian_batch.hip and, through dzo_cluster.h,
+// dzo_lbfgs_batch.hip and dzo_adgd_batch.hip (one definition, the same bits in all of them).
 // ------------------------------------------------------------------------------ radial functions (:16-72)
 template <typename T> __device__ __forceinline__ T pw_twice(T a) { return a + a; }
 template <typename T> __device__ __forceinline__ T pw_square(T a) { return a * a; }

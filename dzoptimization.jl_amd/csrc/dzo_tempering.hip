@@ -15,6 +15,7 @@
 // The per-pair arithmetic is pairwise_energy_delta_kernel's: both call pw_pair_energy of dzo_pairwise.h (the self term removed by a select);
 // lane sums are in T, sums across lanes / waves in fp64 in a fixed order, one rounding back to T.  No floating-point atomic.
 // The random-number rule is stated in include/dzo.h; it is the specification and tests/tempering_twin.py replays it.
+#include "dzo_cluster.h"
 #include "dzo_pairwise.h"
 
 #include <cmath>
@@ -176,19 +177,6 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void temper_w
     if (lane == 0) end.store(radius, acc, rej, s);
 }
 
-// two block-wide sums in EVERY thread, fixed order (wave trees, then the four waves in wave order); red: 2 * kWaves doubles.
-// The caller puts a barrier between the reads of one call and the next call.
-__device__ __forceinline__ void block_sum2_all(double &v0, double &v1, double *red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const double w0 = wave_sum_all(v0), w1 = wave_sum_all(v1);
-    if (lane == 0) { red[wv] = w0; red[kWaves + wv] = w1; }
-    __syncthreads();
-    double r0 = 0, r1 = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) { r0 += red[w]; r1 += red[kWaves + w]; }
-    v0 = r0; v1 = r1;
-}
-
 // ------------------------------------------------------------------------------ BLOCK shape: grid R, block 256
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temper_block_kernel(TemperArgs<T> a) {
     __shared__ T cx[kTemperMaxN], cy[kTemperMaxN], cz[kTemperMaxN];
@@ -208,7 +196,7 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
         }
         rows += (double)row;
     }
-    block_sum2_all(rows, unused, red);
+    cl_block_sum2(rows, unused, red);
     __syncthreads();
     T energy = (T)(0.5 * rows);
     uint64_t s = a.rng[k];
@@ -236,7 +224,7 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
             }
         }
         double so = (double)e_old, sn = (double)e_new;
-        block_sum2_all(so, sn, red);                         // (both barriers are passed by every thread on every step)
+        cl_block_sum2(so, sn, red);                         // (both barriers are passed by every thread on every step)
         int code = 2;
         if (inside) {
             const T delta = (T)sn - (T)so;
@@ -293,7 +281,7 @@ __global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd,
         sa += (double)row_a;
         sb += (double)row_b;
     }
-    block_sum2_all(sa, sb, red);
+    cl_block_sum2(sa, sb, red);
     const T energy_a = (T)(0.5 * sa), energy_b = (T)(0.5 * sb);
     const T log_prob = (energy_a - energy_b) * (inv_temps[ka] - inv_temps[kb]);
     const T u = (T)((double)pcg_draw(s) * kTwoM32);          // always consumed

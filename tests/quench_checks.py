@@ -56,7 +56,7 @@ def consistent(opt, n, st, what):
 
 # ------------------------------------------------------------------------------ the shapes
 # dzo_lbfgs_batch_create restated (csrc/dzo_lbfgs_batch.hip): N <= 64 is one wave per instance; above, one 256-thread block whose
-# dynamic LDS holds rho | alpha (16 m), the sums' scratch (128), five vectors and, where it fits kQuenchLdsMax, the 2 m vectors
+# dynamic LDS holds rho | alpha (16 m), the sums' scratch (128), five vectors and, where it fits kClLdsMax, the 2 m vectors
 # of the history ring; else the ring is in the handle's slab in device memory.
 WAVE, BLOCK_LDS, BLOCK_SLAB = "wave", "block, history in LDS", "block, history in device memory"
 LDS_MAX = 160 * 1024 - 1024

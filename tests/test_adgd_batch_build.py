@@ -68,18 +68,38 @@ def test_adgd_batch_kernels_exist_for_gfx950_without_scratch():
         assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
 
 
+def _csrc():
+    """(dzo_cluster.h, {name: text of every .hip})"""
+    csrc = os.path.join(PKG, "csrc")
+    return open(os.path.join(csrc, "dzo_cluster.h")).read(), {f: open(os.path.join(csrc, f)).read()
+                                                              for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+
+
 def test_the_evaluation_has_one_definition():
-    """The trial's energy and gradient, the block sums and the dots are the quench's routines, defined once; the step-size rule
-    is the only arithmetic the new section adds."""
-    src = open(os.path.join(PKG, "csrc", "dzo_lbfgs_batch.hip")).read()
-    for routine in ("void q_wave_eval(", "void q_block_eval(", "double q_block_sum_all(", "double q_dot3(", "void quench_count_active_kernel("):
-        assert src.count(routine) == 1, routine
-    section = src[src.index("Batched AdGDOptimizer"):]
-    for call in ("q_wave_eval<T, F>(", "q_block_eval<T, F>(", "q_block_sum_all(", "q_dot3(", "qb_count(", "qb_launch_eval<T>("):
+    """The trial's energy and gradient, the block sums and the dots are the routines of dzo_cluster.h, defined once there and in
+    no .hip; the step-size rule is the only arithmetic dzo_adgd_batch.hip adds."""
+    header, hips = _csrc()
+    for routine in ("void cl_wave_eval(", "void cl_block_eval(", "double cl_block_sum(", "void cl_block_sum2(", "double cl_dot3(",
+                    "#define CL_FOR_OWN(", "int32_t cl_check_args("):
+        assert header.count(routine) == 1, routine
+        assert [f for f, text in hips.items() if routine in text] == [], routine
+    assert "__global__" not in header
+    assert [f for f, text in hips.items() if "void quench_count_active_kernel(" in text] == ["dzo_lbfgs_batch.hip"]
+    assert hips["dzo_lbfgs_batch.hip"].count("void quench_count_active_kernel(") == 1
+    assert "#undef" not in header and [f for f, text in hips.items() if "CL_FOR_OWN" in text and "#define" in text] == []
+    for name in ("q_wave_eval", "q_block_eval", "q_block_sum_all", "q_dot3", "DZO_Q_OWN", "hb_dot3", "hb_block_sum2", "block_sum2_all"):
+        assert [f for f, text in hips.items() if name in text] == [] and name not in header, name
+    section = hips["dzo_adgd_batch.hip"]
+    for call in ("cl_wave_eval<T, F>(", "cl_block_eval<T, F>(", "cl_block_sum(", "cl_dot3(", "cl_step(", "cl_count(", "cl_launch_eval<T>("):
         assert call in section, call
+    assert "dzo_lbfgs_batch_s" not in section                # the evaluation needs no handle of the other optimizer
     assert "pw_pair" not in section and "F::" not in section
     assert 'DZO_TIMED("adgd_batch_init"' in section and 'DZO_TIMED("adgd_batch_step"' in section
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuenchLdsMax" in section
+    assert header.count("hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax") == 1
+    # ... which dzo_adgd_batch_create raises for its block step kernel of either element type
+    assert re.search(r"\(const void \*\)adgd_batch_block_step_kernel<double, LJRadial<double>>\s*:\s*\(const void \*\)adgd_batch_block_step_kernel<float,", section)
+    assert "cl_finish_create(" in section
+    assert "csrc/dzo_adgd_batch.hip" in open(os.path.join(PKG, "Makefile")).read()
 
 
 def test_lj_adgd_quench_example_compiles_and_links(tmp_path):

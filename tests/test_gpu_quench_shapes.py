@@ -35,7 +35,7 @@ def device():
 
 # ------------------------------------------------------------------------------ the table (no GPU)
 def test_shape_table_covers_every_path_on_both_sides_of_its_limits():
-    """quench_checks.path restates the constructor's choice; if kQuenchLdsMax or the LDS layout changes, this names the cases that
+    """quench_checks.path restates the constructor's choice; if kClLdsMax or the LDS layout changes, this names the cases that
     moved."""
     assert qc.LDS_MAX == 162816 and qc.lds_request(98, 32, np.float64) == 16 * 32 + 128 + 69 * 3 * 98 * 8
     for dtype in qc.DTYPES:

@@ -74,15 +74,16 @@ def test_hessian_batch_kernels_exist_for_gfx950_without_scratch():
 
 
 def test_the_pair_term_has_one_definition():
-    """The per-pair arithmetic is pw_pair of dzo_pairwise.h: the new file calls no radial function itself and adds up nothing in
-    memory; its fp64 reductions are its own, on wave_sum_all."""
+    """The per-pair arithmetic is pw_pair of dzo_pairwise.h: the file calls no radial function itself and adds up nothing in
+    memory; its fp64 dots and its block sum are those of dzo_cluster.h, on wave_sum_all."""
     src = open(os.path.join(PKG, "csrc", "dzo_hessian_batch.hip")).read()
     assert '#include "dzo_pairwise.h"' in src
     assert "pw_pair<T, F, kPwHvp>(" in src
     assert "F::" not in src and "atomic" not in src
     assert "wave_sum_all(" in src
-    for routine in ("q_dot3", "q_block_sum_all", "q_wave_eval", "q_block_eval"):
-        assert routine not in src, routine
+    assert '#include "dzo_cluster.h"' in src and "cl_dot3(" in src and "cl_block_sum2(" in src
+    for own in ("hb_dot3", "hb_block_sum2", "hb_check_common", "__builtin_fma", "__syncthreads();\n    double r"):
+        assert own not in src, own                           # no dot or block sum of its own
     assert 'DZO_TIMED("hess_batch_hvp"' in src and 'DZO_TIMED("hess_batch_hessian"' in src
     makefile = open(os.path.join(PKG, "Makefile")).read()
     assert "csrc/dzo_hessian_batch.hip" in makefile

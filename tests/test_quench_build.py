@@ -67,11 +67,16 @@ def test_quench_kernels_exist_for_gfx950_without_scratch():
 
 
 def test_source_uses_the_shared_pair_arithmetic():
-    src = open(os.path.join(PKG, "csrc", "dzo_lbfgs_batch.hip")).read()
-    assert '#include "dzo_pairwise.h"' in src and "LJRadial<T>" in src and "pw_pair<" in src
-    assert "F::energy(" not in src and "F::first(" not in src
-    assert "atomicAdd(&total" in src and src.count("atomic") <= 4      # the one integer count; no floating-point atomic
-    assert "csrc/dzo_lbfgs_batch.hip" in open(os.path.join(PKG, "Makefile")).read()
+    """The quench, the batched AdGD and the header both are built on (dzo_cluster.h, which holds their pair loops)."""
+    src, adgd, header = (open(os.path.join(PKG, "csrc", f)).read() for f in ("dzo_lbfgs_batch.hip", "dzo_adgd_batch.hip", "dzo_cluster.h"))
+    assert '#include "dzo_cluster.h"' in src and '#include "dzo_cluster.h"' in adgd and '#include "dzo_pairwise.h"' in header
+    assert "LJRadial<T>" in src and "LJRadial<T>" in adgd and "pw_pair<" in header
+    for text in (src, adgd, header):
+        assert "F::energy(" not in text and "F::first(" not in text
+    # the one integer count; no floating-point atomic
+    assert "atomicAdd(&total" in src and src.count("atomic") + adgd.count("atomic") + header.count("atomic") <= 4
+    makefile = open(os.path.join(PKG, "Makefile")).read()
+    assert "csrc/dzo_lbfgs_batch.hip" in makefile and "csrc/dzo_adgd_batch.hip" in makefile
 
 
 def test_lj_quench_example_compiles_and_links(tmp_path):

@@ -1,4 +1,4 @@
-"""Measurement of the batched AdGD optimizer (dzo_adgd_batch_*, csrc/dzo_lbfgs_batch.hip) on the device: recorded, not gated.
+"""Measurement of the batched AdGD optimizer (dzo_adgd_batch_*, csrc/dzo_adgd_batch.hip) on the device: recorded, not gated.
 
     python tools/bench_adgd_batch.py [--out profiles/adgd_batch_bench.json] [--repeats 5] [--baseline-count 256]
 

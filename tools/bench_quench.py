@@ -1,4 +1,4 @@
-"""Measurement of the batched L-BFGS quench (csrc/dzo_lbfgs_batch.hip) on the device: recorded, not gated.
+"""Measurement of the batched L-BFGS quench (csrc/dzo_lbfgs_batch.hip on csrc/dzo_cluster.h) on the device: recorded, not gated.
 
     python tools/bench_quench.py [--out profiles/quench_bench.json] [--repeats 5] [--baseline-count 256]
 
