@@ -472,6 +472,44 @@ template <int R> __device__ __forceinline__ void block_sum_multi(const double (&
     __syncthreads();
 }
 
+// Block maximum for kBlock threads; `lds` holds kWaves doubles.  Result valid in thread 0.
+__device__ __forceinline__ double block_max(double v, double *lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = 0;
+    if (threadIdx.x == 0) {
+        r = lds[0];
+        for (int w = 1; w < kWaves; ++w) r = fmax(r, lds[w]);
+    }
+    return r;
+}
+
+// One block's per-thread sums of R rows of `count` partials each (row r at partials + r * count): v[r] += the elements
+// threadIdx.x, threadIdx.x + kBlock, ... of row r, the first stage of the one-block finish kernels.  One block pulling
+// R x count values through one CU is bound by load latency: eight strided steps of loads are in flight before the first
+// add; the adds keep the order of the plain loop, so every value is what the plain loop gives for the same partials
+// (9.2 -> about 3 us for six rows of 4096).
+template <int R> __device__ __forceinline__ void strided_sums(const double *__restrict__ partials, int64_t count, double (&v)[R]) {
+    int64_t i = threadIdx.x;
+    for (; i + 7 * kBlock < count; i += 8 * kBlock) {
+        double t[8][R];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int r = 0; r < R; ++r) t[u][r] = partials[(int64_t)r * count + i + (int64_t)u * kBlock];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int r = 0; r < R; ++r) v[r] += t[u][r];
+    }
+    for (; i < count; i += kBlock) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] += partials[(int64_t)r * count + i];
+    }
+}
+
 // Every thread of every block obtains the same sum of `count` per-block partials, read in
 // a fixed order (the second stage of the two-stage reductions).  `lds` holds kWaves doubles.
 __device__ __forceinline__ double reduce_partials_all(const double *__restrict__ partials,

@@ -271,7 +271,6 @@ __global__ __launch_bounds__(kBlock) void rosen_edge_terms_kernel(int64_t n, con
     }
     if (r == 0) {
         for (int64_t e = nvec * N; e + 1 < n; ++e) acc += rosen_term<T>(x[e], x[e + 1]);
-        if (nvec == 0 && n >= 2) { /* all terms are tail terms, handled by the loop above */ }
     }
     const double s = block_sum(acc, lds);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -312,18 +311,60 @@ __global__ __launch_bounds__(kBlock) void quadratic_kernel(int64_t n, const T *_
 __global__ __launch_bounds__(kBlock) void finish_scaled_sum_kernel(const double *__restrict__ partials, int64_t count,
                                                                    double scale, double *__restrict__ result) {
     __shared__ double lds[kWaves];
-    double v = 0;
-    int64_t i = threadIdx.x;
-    for (; i + 7 * kBlock < count; i += 8 * kBlock) {           // (loads first, adds in the plain loop's order)
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = partials[i + (int64_t)u * kBlock];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v += t[u];
-    }
-    for (; i < count; i += kBlock) v += partials[i];
-    double r = block_sum(v, lds);
+    double v[1] = {0};
+    strided_sums<1>(partials, count, v);
+    double r = block_sum(v[0], lds);
     if (threadIdx.x == 0) result[0] = scale * r;
+}
+
+// One search direction with up to three step sizes evaluated in the same pass over A (the request the search needs
+// now plus the one or two it will most likely need next).
+template <typename T> struct PhiDir {
+    const T *dir;
+    T ts[3];
+    T *point_out[3];
+    const T *ref[3];       // stagnation test against a stored point (may be null) ...
+    int ref_req[3];        // ... or against request ref_req[q] of the same direction in this launch (-1: none)
+    T *grad_out[3];        // may be null: A*x_t, the gradient at the trial point, is a by-product (c_j = A[:,j].x_t)
+    int active[3];
+};
+// the one request of quadratic_phi_kernel: request 0 of side a
+template <typename T> __device__ __forceinline__ PhiDir<T> phi_single_request(const T *dir, T ts, T *point_out, const T *ref) {
+    PhiDir<T> d;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { d.ts[r] = (T)0; d.point_out[r] = nullptr; d.ref[r] = nullptr; d.ref_req[r] = -1; d.grad_out[r] = nullptr; d.active[r] = 0; }
+    d.dir = dir; d.ts[0] = ts; d.point_out[0] = point_out; d.ref[0] = ref; d.active[0] = 1;
+    return d;
+}
+
+// What ONE thread does for element j of one direction once the column sums c_j = A[:,j].x_t of its requests are known:
+// per active request the objective partial x_t[j] c_j, element j of the trial point, of its gradient (a by-product) and the
+// bracket's three flags (:71-80 and the :150 stagnation test).  `sum_of(slot)`: the column sum of request slot = 3 side + r
+// (asked for active requests only).  The references are read before any point_out store: a reference may be one of this
+// launch's own output buffers.  FLAGS_MAY_BE_NULL: the single-request kernel's plain evaluations carry no flags.
+template <typename T, bool FLAGS_MAY_BE_NULL = false, typename SumOf>
+__device__ __forceinline__ void phi_finish_element(const PhiDir<T> &d, int side, int64_t j, T xo, SumOf sum_of,
+                                                   double *__restrict__ partials, int32_t *__restrict__ flags, int64_t n) {
+    const T dj = d.dir[j];
+    T xt[3], refv[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) xt[r] = dfma(d.ts[r], dj, xo);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) refv[r] = (d.active[r] && d.ref[r]) ? d.ref[r][j] : (T)0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        if (!d.active[r]) continue;
+        const int slot = side * 3 + r;
+        const double c = sum_of(slot);
+        partials[(int64_t)slot * n + j] = c * (double)xt[r];
+        d.point_out[r][j] = xt[r];
+        if (d.grad_out[r]) d.grad_out[r][j] = (T)c;              // exactly what quadratic_kernel<WRITE_G> stores
+        if (FLAGS_MAY_BE_NULL && !flags) continue;
+        if (xo != xt[r]) flags[slot * 3 + 0] = 1;
+        if (dj != (T)0) flags[slot * 3 + 1] = 1;
+        if (d.ref[r]) { if (!is_equal(xt[r], refv[r])) flags[slot * 3 + 2] = 1; }
+        else if (d.ref_req[r] >= 0) { if (!is_equal(xt[r], xt[d.ref_req[r]])) flags[slot * 3 + 2] = 1; }
+    }
 }
 
 // phi(t) = f(x + ts*dir) for the dense quadratic (legacy/DZOptimization.jl:25-46) without a separate
@@ -356,35 +397,10 @@ __global__ __launch_bounds__(kBlock) void quadratic_phi_kernel(int64_t n, const 
             for (int64_t i = threadIdx.x; i < n; i += kBlock) acc = __builtin_fma((double)col[i], (double)dfma(ts, dir[i], x[i]), acc);
         }
         const double c = block_sum(acc, lds);
-        if (threadIdx.x == 0) {
-            const T xo = x[j], dj = dir[j];
-            const T xt = dfma(ts, dj, xo);
-            partials[j] = c * (double)xt;
-            point_out[j] = xt;
-            if (flags) {                                   // the bracket's flags (:71-80) and its :150 stagnation test
-                if (xo != xt) flags[0] = 1;
-                if (dj != (T)0) flags[1] = 1;
-                if (ref && !is_equal(xt, ref[j])) flags[2] = 1;
-            }
-        }
+        if (threadIdx.x == 0)
+            phi_finish_element<T, true>(phi_single_request<T>(dir, ts, point_out, ref), 0, j, x[j], [&](int) { return c; }, partials, flags, n);
     }
 }
-
-// Two line-search evaluations in one pass over A (the two searches of the dense BFGS step run
-// side by side, legacy/DZOptimization.jl:922-932): request r evaluates f(x + ts[r]*dir[r]); each A
-// column is loaded once and used for both.  Per request the arithmetic is that of
-// quadratic_phi_kernel, so every value is bit-identical to a separate evaluation.
-// One search direction with up to three step sizes evaluated in the same pass (the request the search
-// needs now plus the one or two it will most likely need next).
-template <typename T> struct PhiDir {
-    const T *dir;
-    T ts[3];
-    T *point_out[3];
-    const T *ref[3];       // stagnation test against a stored point (may be null) ...
-    int ref_req[3];        // ... or against request ref_req[q] of the same direction in this launch (-1: none)
-    T *grad_out[3];        // may be null: A*x_t, the gradient at the trial point, is a by-product (c_j = A[:,j].x_t)
-    int active[3];
-};
 
 // device-driven searches: the requests as the previous round's finish kernel posted them (see quadratic_phi6_kernel)
 template <typename T> __device__ __forceinline__ int phi6_take_requests(PhiDir<T> &a, PhiDir<T> &b, const PhiReqDev *__restrict__ dreq) {
@@ -403,6 +419,10 @@ template <typename T> __device__ __forceinline__ int phi6_take_requests(PhiDir<T
     return any;
 }
 
+// Two line-search evaluations in one pass over A (the two searches of the dense BFGS step run
+// side by side, legacy/DZOptimization.jl:922-932): request r evaluates f(x + ts[r]*dir[r]); each A
+// column is loaded once and used for both.  Per request the arithmetic is that of
+// quadratic_phi_kernel, so every value is bit-identical to a separate evaluation.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void quadratic_phi6_kernel(int64_t n, const T *__restrict__ A, const T *__restrict__ x,
                                                                 PhiDir<T> a, PhiDir<T> b,
@@ -447,47 +467,34 @@ __global__ __launch_bounds__(kBlock) void quadratic_phi6_kernel(int64_t n, const
         if (threadIdx.x == 0) {
             const T xo = x[j];
 #pragma unroll
-            for (int side = 0; side < 2; ++side) {
-                const PhiDir<T> &d = side ? b : a;
-                const T dj = d.dir[j];
-                T xt[3], refv[3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) xt[r] = dfma(d.ts[r], dj, xo);
-#pragma unroll
-                for (int r = 0; r < 3; ++r) refv[r] = (d.active[r] && d.ref[r]) ? d.ref[r][j] : (T)0;   // first: a reference may be one of this launch's own output buffers
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    if (!d.active[r]) continue;
-                    const int slot = side * 3 + r;
-                    partials[(int64_t)slot * n + j] = c[slot] * (double)xt[r];
-                    d.point_out[r][j] = xt[r];
-                    if (d.grad_out[r]) d.grad_out[r][j] = (T)c[slot];      // exactly what quadratic_kernel<WRITE_G> stores
-                    if (xo != xt[r]) flags[slot * 3 + 0] = 1;
-                    if (dj != (T)0) flags[slot * 3 + 1] = 1;
-                    if (d.ref[r]) { if (!is_equal(xt[r], refv[r])) flags[slot * 3 + 2] = 1; }
-                    else if (d.ref_req[r] >= 0) { if (!is_equal(xt[r], xt[d.ref_req[r]])) flags[slot * 3 + 2] = 1; }
-                }
-            }
+            for (int side = 0; side < 2; ++side)
+                phi_finish_element<T>(side ? b : a, side, j, xo, [&](int slot) { return c[slot]; }, partials, flags, n);
         }
     }
 }
 
-// The same launch with a block walking CG columns at once and three register sets of requests in flight (round 4).  The
+// The same launch with a block walking kPhi6Cols columns at once and two register sets of requests in flight (round 4).  The
 // one-column kernel waits for each iteration's four loads before it asks for the next ones (24 KB per CU in flight).  Here
-// the loads of iterations it + 1 and it + 2 are on their way while iteration it is computed -- and they are UNCONDITIONAL
+// the loads of iteration it + 1 are on their way while iteration it is computed -- and they are UNCONDITIONAL
 // (addresses clamped to the last vector, the sums predicated instead): a prefetch under `if (i < n)` makes the compiler
 // wait for vmcnt(0) before the older set may be used, because requests complete in order and a younger request that may
 // not have been issued cannot be counted on (that is why the first pipelined forms of this kernel measured nothing,
-// profiles/r04_phi6_experiments.md).  x, dir_a, dir_b are loaded and the six trial values formed once per CG columns.
+// profiles/r04_phi6_experiments.md).  x, dir_a, dir_b are loaded and the six trial values formed once per kPhi6Cols columns.
 // Element i still belongs to thread (i / N) % 256 in iteration i / (256 N), the per-thread sums run over q, then over the
 // iterations, and the block sum is wave_sum + the waves in order: every value is bit for bit what quadratic_phi6_kernel
 // (and quadratic_phi_kernel, quadratic_kernel) give.  n % N == 0 only.
-template <typename T, int CG, int DEPTH = 2, int BPC = 1>
-__global__ __launch_bounds__(kBlock, BPC) void quadratic_phi6_cols_kernel(int64_t n, const T *__restrict__ A, const T *__restrict__ x,
+// Two columns, ONE set ahead, 108 registers = four blocks per CU in fp64 (two in fp32), so that the 2048 groups of config 2
+// are two full rounds of the 1024 resident blocks: 27.3 us per round against the one-column kernel's 32.4.  (Two sets ahead,
+// 140 registers, three blocks per CU: 28.8 us; four columns: 30.2 us; forms pressed into more blocks per CU than their
+// registers allow spill and lose everything, 35-55 us.  Both were retired.)
+constexpr int kPhi6Cols = 2;
+template <typename T>
+__global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? 4 : 2)) void quadratic_phi6_cols_kernel(int64_t n, const T *__restrict__ A, const T *__restrict__ x,
                                                                      PhiDir<T> a, PhiDir<T> b,
                                                                      double *__restrict__ partials, int32_t *__restrict__ flags,
                                                                      const PhiReqDev *__restrict__ dreq) {
     constexpr int N = Vec16<T>::N;
+    constexpr int CG = kPhi6Cols;
     __shared__ double lds[CG * 6 * kWaves];
     if (dreq) { if (!phi6_take_requests<T>(a, b, dreq)) return; }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -539,28 +546,14 @@ __global__ __launch_bounds__(kBlock, BPC) void quadratic_phi6_cols_kernel(int64_
                 }
             }
         };
-        if constexpr (DEPTH == 2) {
-            Tile t0, t1, t2;
-            fetch(t0, 0);
-            fetch(t1, 1);
-            int it = 0;
-            for (; it + 3 <= iters; it += 3) {
-                fetch(t2, it + 2); consume(t0, it);
-                fetch(t0, it + 3); consume(t1, it + 1);
-                fetch(t1, it + 4); consume(t2, it + 2);
-            }
-            if (it < iters) consume(t0, it);
-            if (it + 1 < iters) consume(t1, it + 1);
-        } else {
-            Tile t0, t1;
-            fetch(t0, 0);
-            int it = 0;
-            for (; it + 2 <= iters; it += 2) {
-                fetch(t1, it + 1); consume(t0, it);
-                fetch(t0, it + 2); consume(t1, it + 1);
-            }
-            if (it < iters) consume(t0, it);
+        Tile t0, t1;
+        fetch(t0, 0);
+        int it = 0;
+        for (; it + 2 <= iters; it += 2) {
+            fetch(t1, it + 1); consume(t0, it);
+            fetch(t0, it + 2); consume(t1, it + 1);
         }
+        if (it < iters) consume(t0, it);
 #pragma unroll
         for (int c = 0; c < CG; ++c) {
 #pragma unroll
@@ -576,240 +569,16 @@ __global__ __launch_bounds__(kBlock, BPC) void quadratic_phi6_cols_kernel(int64_
             const int c = threadIdx.x;
             const int64_t j = j0 + c;
             const T xo = x[j];
+            auto sum_of = [&](int slot) {
+                double cs = 0;
 #pragma unroll
-            for (int side = 0; side < 2; ++side) {
-                const PhiDir<T> &d = side ? b : a;
-                const T dj = d.dir[j];
-                T xtj[3], refv[3];
+                for (int w = 0; w < kWaves; ++w) cs += lds[(c * 6 + slot) * kWaves + w];
+                return cs;
+            };
 #pragma unroll
-                for (int r = 0; r < 3; ++r) xtj[r] = dfma(d.ts[r], dj, xo);
-#pragma unroll
-                for (int r = 0; r < 3; ++r) refv[r] = (d.active[r] && d.ref[r]) ? d.ref[r][j] : (T)0;   // first: a reference may be one of this launch's own output buffers
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    if (!d.active[r]) continue;
-                    const int slot = side * 3 + r;
-                    double cs = 0;
-#pragma unroll
-                    for (int w = 0; w < kWaves; ++w) cs += lds[(c * 6 + slot) * kWaves + w];
-                    partials[(int64_t)slot * n + j] = cs * (double)xtj[r];
-                    d.point_out[r][j] = xtj[r];
-                    if (d.grad_out[r]) d.grad_out[r][j] = (T)cs;             // exactly what quadratic_kernel<WRITE_G> stores
-                    if (xo != xtj[r]) flags[slot * 3 + 0] = 1;
-                    if (dj != (T)0) flags[slot * 3 + 1] = 1;
-                    if (d.ref[r]) { if (!is_equal(xtj[r], refv[r])) flags[slot * 3 + 2] = 1; }
-                    else if (d.ref_req[r] >= 0) { if (!is_equal(xtj[r], xtj[d.ref_req[r]])) flags[slot * 3 + 2] = 1; }
-                }
-            }
+            for (int side = 0; side < 2; ++side) phi_finish_element<T>(side ? b : a, side, j, xo, sum_of, partials, flags, n);
         }
         __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same evaluations on the LOWER TRIANGLE of A (round 4).  A is symmetric by definition (f = 1/2 x'Ax, "dense
-// symmetric A", include/dzo.h), so c = A x_t needs every element of the triangle once:
-//     row part   c_i += A[i,j] x_t[j]   (j <= i)   thread-local
-//     col part   c_j += A[i,j] x_t[i]   (i >  j)   summed across the wave
-// -- the split of tri_pass_kernel (dzo_bfgs.hip), here for up to six trial points x_t = fma(ts, dir, x) at once (the two
-// line searches' requests of a round, legacy/DZOptimization.jl:922-932) and with a block walking kQtWPB windows, so that
-// the row part leaves one value per 128 columns instead of one per 32.  At config 2 a round reads 67 MB of A instead of
-// 135 MB (both from the Infinity Cache); a second, small kernel adds the parts in a fixed order and does what thread 0
-// of quadratic_phi6_kernel does per element (objective partial, trial point, its gradient, the bracket's flags).
-// EVERY evaluation of the dense quadratic goes this way when the triangle form is on (objective, gradient, phi, phi6):
-// the stored gradient of a point and a recomputed one are then the same bits (run_and_test!, legacy :1025-1032).
-constexpr int kQtPH = 256;           // rows per panel (128 row pairs)
-constexpr int kQtCW = 32;            // columns per window (16 per parity)
-constexpr int kQtUJ = 8;             // columns of one parity per chunk
-#ifndef DZO_QT_WPB
-#define DZO_QT_WPB 4
-#endif
-constexpr int kQtWPB = DZO_QT_WPB;   // windows per block
-
-template <typename T> __device__ __forceinline__ void qt_load2(const T *p, T (&hv)[2]) {
-    if constexpr (sizeof(T) == 8) { const double2 q = *reinterpret_cast<const double2 *>(p); hv[0] = q.x; hv[1] = q.y; }
-    else { const float2 q = *reinterpret_cast<const float2 *>(p); hv[0] = q.x; hv[1] = q.y; }
-}
-
-// rowpart: [6][ranges][n], colpart: [6][panels][n] (ranges = ceil(n / (kQtCW kQtWPB)), panels = ceil(n / kQtPH))
-template <typename T>
-__global__ __launch_bounds__(kBlock, 2) void quadratic_tri6_kernel(int64_t n, const T *__restrict__ A, const T *__restrict__ x,
-                                                                   PhiDir<T> a, PhiDir<T> b, double *__restrict__ rowpart,
-                                                                   double *__restrict__ colpart, const PhiReqDev *__restrict__ dreq) {
-    const int P = blockIdx.y, R = blockIdx.x;
-    const int64_t r_first = (int64_t)R * (kQtCW * kQtWPB);
-    if (r_first >= ((int64_t)P + 1) * kQtPH || r_first >= n) return;         // the range lies right of the panel's diagonal
-    if (dreq) { if (!phi6_take_requests<T>(a, b, dreq)) return; }
-    __shared__ double wp[6][kWaves][kQtCW];
-    __shared__ double rp[6][kQtPH];
-    // (wave-uniform, and told so: the column index of a load then is a scalar, and x[j] / dir[j] arrive through the scalar cache)
-    const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x / 128);
-    const int lane_h = threadIdx.x % 128;
-    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    const int64_t row = (int64_t)P * kQtPH + 2 * lane_h;
-    const int64_t ranges = (n + kQtCW * kQtWPB - 1) / (kQtCW * kQtWPB), panels = (n + kQtPH - 1) / kQtPH;
-    int act[6]; T ts[6]; const T *dir[6];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        act[q] = a.active[q]; ts[q] = a.ts[q]; dir[q] = a.dir;
-        act[3 + q] = b.active[q]; ts[3 + q] = b.ts[q]; dir[3 + q] = b.dir;
-    }
-    // the trial points at this thread's two rows
-    double v0[6], v1[6];
-    {
-        const bool in = row < n;
-        const T x0 = in ? x[row] : (T)0, x1 = in ? x[row + 1] : (T)0;
-        const T a0 = in ? a.dir[row] : (T)0, a1 = in ? a.dir[row + 1] : (T)0;
-        const T b0 = in ? b.dir[row] : (T)0, b1 = in ? b.dir[row + 1] : (T)0;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            v0[q] = in ? (double)dfma(ts[q], q < 3 ? a0 : b0, x0) : 0.0;
-            v1[q] = in ? (double)dfma(ts[q], q < 3 ? a1 : b1, x1) : 0.0;
-        }
-    }
-    double acc[6][2];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) { acc[q][0] = 0; acc[q][1] = 0; }
-    // loads: unconditional (masked lanes read the first bytes of A), a chunk of eight columns per request, one chunk ahead
-    auto issue = [&](int64_t c_first, int c0, T (&hv)[kQtUJ][2]) {
-#pragma unroll
-        for (int u = 0; u < kQtUJ; ++u) {
-            const int64_t j = c_first + half + 2 * (c0 + u);
-            const bool on = c0 + u < kQtCW / 2 && j < n && row < n && row + 1 >= j;
-            qt_load2<T>(on ? A + j * n + row : A, hv[u]);
-        }
-    };
-    auto chunk = [&](int64_t c_first, int c0, const T (&hv)[kQtUJ][2]) {
-        double h0[kQtUJ], h1[kQtUJ], m0[kQtUJ], m1[kQtUJ];
-        T xj[kQtUJ], aj[kQtUJ], bj[kQtUJ];
-#pragma unroll
-        for (int u = 0; u < kQtUJ; ++u) {
-            const int64_t j = c_first + half + 2 * (c0 + u);
-            const bool inw = c0 + u < kQtCW / 2 && j < n;
-            const bool on = inw && row < n && row + 1 >= j;
-            const bool lo0 = on && row >= j;                                 // (row == j - 1: an upper element of the pair, left alone)
-            const int64_t jc = inw ? j : 0;
-            xj[u] = x[jc]; aj[u] = a.dir[jc]; bj[u] = b.dir[jc];
-            h0[u] = lo0 ? (double)hv[u][0] : 0.0; h1[u] = on ? (double)hv[u][1] : 0.0;
-            m0[u] = row > j ? h0[u] : 0.0; m1[u] = row + 1 > j ? h1[u] : 0.0;   // strictly lower: the mirror part
-            if (!inw) { xj[u] = (T)0; aj[u] = (T)0; bj[u] = (T)0; }
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (!act[q]) continue;                                          // (wave-uniform: later rounds carry one or two requests per direction)
-            double col[8];
-#pragma unroll
-            for (int u = 0; u < kQtUJ; ++u) {
-                const double vj = (double)dfma(ts[q], q < 3 ? aj[u] : bj[u], xj[u]);
-                acc[q][0] = __builtin_fma(h0[u], vj, acc[q][0]);
-                acc[q][1] = __builtin_fma(h1[u], vj, acc[q][1]);
-                col[u] = __builtin_fma(m1[u], v1[q], m0[u] * v0[q]);
-            }
-            const double tot = wave_sum8(col, ln);
-            const int cw = 2 * (c0 + wave_sum8_owner(ln)) + half;           // column within the window
-            if (ln < 8 && cw < kQtCW) wp[q][wv][cw] = tot;
-        }
-    };
-    // chunks of a block in order: window w = c / 2, columns (c % 2) kQtUJ ... of each parity; two buffers, one chunk ahead
-    T hvA[kQtUJ][2], hvB[kQtUJ][2];
-    auto window_on = [&](int w) { const int64_t c = r_first + (int64_t)w * kQtCW; return w < kQtWPB && c < n && c < ((int64_t)P + 1) * kQtPH; };
-    auto flush_window = [&](int w) {                                        // the window's column parts: the two waves of a parity
-        __syncthreads();
-        if (threadIdx.x < kQtCW) {
-            const int cw = threadIdx.x, hw = cw & 1;                        // parity hw lives in waves 2 hw, 2 hw + 1
-            const int64_t j = r_first + (int64_t)w * kQtCW + cw;
-            if (j < n) {
-#pragma unroll
-                for (int q = 0; q < 6; ++q) if (act[q]) colpart[((int64_t)q * panels + P) * n + j] = wp[q][2 * hw][cw] + wp[q][2 * hw + 1][cw];
-            }
-        }
-        __syncthreads();
-    };
-    int nwin = 0;
-    while (window_on(nwin)) ++nwin;                                         // (uniform)
-    const int nchunks = 2 * nwin;
-    issue(r_first, 0, hvA);
-    for (int c = 0; c < nchunks; c += 2) {
-        const int w = c / 2;
-        const int64_t c_first = r_first + (int64_t)w * kQtCW;
-        issue(c_first, kQtUJ, hvB);                                         // chunk c + 1: the second half of window w
-        chunk(c_first, 0, hvA);
-        if (c + 2 < nchunks) issue(c_first + kQtCW, 0, hvA);               // chunk c + 2: the first half of window w + 1
-        chunk(c_first, kQtUJ, hvB);
-        flush_window(w);
-    }
-    // row part: the two column parities of a row pair
-    if (half == 1) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) { rp[q][2 * lane_h] = acc[q][0]; rp[q][2 * lane_h + 1] = acc[q][1]; }
-    }
-    __syncthreads();
-    if (half == 0 && row < n) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (!act[q]) continue;
-            double *dst = rowpart + ((int64_t)q * ranges + R) * n + row;
-            dst[0] = acc[q][0] + rp[q][2 * lane_h];
-            dst[1] = acc[q][1] + rp[q][2 * lane_h + 1];
-        }
-    }
-}
-
-// c_i of every active request = its row parts of the ranges up to the diagonal + its column parts of the panels from
-// the diagonal on, fixed order; then, per element, what thread 0 of quadratic_phi6_kernel does for its column.
-// partials: [6][n] (the objective's x_t[i] c_i); flags may be null (plain objective / gradient evaluations).
-constexpr int kQtRI = 32, kQtRG = kBlock / kQtRI;
-template <typename T>
-__global__ __launch_bounds__(kBlock) void quadratic_tri6_reduce_kernel(int64_t n, const T *__restrict__ x, PhiDir<T> a, PhiDir<T> b,
-                                                                       const double *__restrict__ rowpart, const double *__restrict__ colpart,
-                                                                       double *__restrict__ partials, int32_t *__restrict__ flags,
-                                                                       const PhiReqDev *__restrict__ dreq) {
-    if (dreq) { if (!phi6_take_requests<T>(a, b, dreq)) return; }
-    __shared__ double grp[6][kQtRG][kQtRI];
-    const int li = threadIdx.x % kQtRI, gq = threadIdx.x / kQtRI;
-    const int64_t i = (int64_t)blockIdx.x * kQtRI + li;
-    const int64_t ranges = (n + kQtCW * kQtWPB - 1) / (kQtCW * kQtWPB), panels = (n + kQtPH - 1) / kQtPH;
-    int act[6];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { act[q] = a.active[q]; act[3 + q] = b.active[q]; }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        double s = 0;
-        if (act[q] && i < n) {
-            for (int64_t r = gq; r <= i / (kQtCW * kQtWPB); r += kQtRG) s += rowpart[((int64_t)q * ranges + r) * n + i];
-            for (int64_t pp = i / kQtPH + gq; pp < panels; pp += kQtRG) s += colpart[((int64_t)q * panels + pp) * n + i];
-        }
-        grp[q][gq][li] = s;
-    }
-    __syncthreads();
-    if (gq != 0 || i >= n) return;
-    const T xo = x[i];
-#pragma unroll
-    for (int side = 0; side < 2; ++side) {
-        const PhiDir<T> &d = side ? b : a;
-        const T dj = d.dir[i];
-        T xt[3], refv[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) xt[r] = dfma(d.ts[r], dj, xo);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) refv[r] = (d.active[r] && d.ref[r]) ? d.ref[r][i] : (T)0;   // first: a reference may be one of this launch's own output buffers
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            if (!d.active[r]) continue;
-            const int slot = side * 3 + r;
-            double c = 0;
-#pragma unroll
-            for (int g8 = 0; g8 < kQtRG; ++g8) c += grp[slot][g8][li];
-            partials[(int64_t)slot * n + i] = c * (double)xt[r];
-            if (d.point_out[r]) d.point_out[r][i] = xt[r];
-            if (d.grad_out[r]) d.grad_out[r][i] = (T)c;
-            if (flags) {
-                if (xo != xt[r]) flags[slot * 3 + 0] = 1;
-                if (dj != (T)0) flags[slot * 3 + 1] = 1;
-                if (d.ref[r]) { if (!is_equal(xt[r], refv[r])) flags[slot * 3 + 2] = 1; }
-                else if (d.ref_req[r] >= 0) { if (!is_equal(xt[r], xt[d.ref_req[r]])) flags[slot * 3 + 2] = 1; }
-            }
-        }
     }
 }
 
@@ -819,25 +588,7 @@ __global__ __launch_bounds__(kBlock) void finish_phi6_kernel(const double *__res
                                                              double *__restrict__ out, int32_t *__restrict__ flags, double ticket) {
     __shared__ double lds6[6 * kWaves];
     double v[6] = {0, 0, 0, 0, 0, 0};
-    // (one block pulling 6 x count values through one CU is bound by load latency: eight strided steps of loads are
-    // in flight before the first add; the adds keep the order of the plain loop, so every value is what
-    // finish_phi_kernel gives for the same partials -- 9.2 -> about 3 us at n = 4096)
-    int64_t i = threadIdx.x;
-    for (; i + 7 * kBlock < count; i += 8 * kBlock) {
-        double t[8][6];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int r = 0; r < 6; ++r) t[u][r] = partials[(int64_t)r * count + i + (int64_t)u * kBlock];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int r = 0; r < 6; ++r) v[r] += t[u][r];
-    }
-    for (; i < count; i += kBlock) {
-#pragma unroll
-        for (int r = 0; r < 6; ++r) v[r] += partials[(int64_t)r * count + i];
-    }
+    strided_sums<6>(partials, count, v);
     double sres[6];
     block_sum_multi<6>(v, lds6, sres);
     if (threadIdx.x == 0) {
@@ -864,17 +615,9 @@ __global__ __launch_bounds__(kBlock) void finish_phi6_kernel(const double *__res
 __global__ __launch_bounds__(kBlock) void finish_phi_kernel(const double *__restrict__ partials, int64_t count, double scale,
                                                             double *__restrict__ out, int32_t *__restrict__ flags) {
     __shared__ double lds[kWaves];
-    double v = 0;
-    int64_t i = threadIdx.x;
-    for (; i + 7 * kBlock < count; i += 8 * kBlock) {           // (loads first, adds in the plain loop's order: see finish_phi6_kernel)
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = partials[i + (int64_t)u * kBlock];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v += t[u];
-    }
-    for (; i < count; i += kBlock) v += partials[i];
-    const double r = block_sum(v, lds);
+    double v[1] = {0};
+    strided_sums<1>(partials, count, v);
+    const double r = block_sum(v[0], lds);
     if (threadIdx.x == 0) {
         out[0] = scale * r;
         if (flags) {
@@ -894,30 +637,16 @@ __global__ __launch_bounds__(kBlock) void lse_max_kernel(int64_t n, const T *__r
     double mx = -1.7976931348623157e308;
     const int64_t nthreads = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthreads) mx = fmax(mx, (double)x[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = lds[0];
-        for (int w = 1; w < kWaves; ++w) r = fmax(r, lds[w]);
-        partials[blockIdx.x] = r;
-    }
+    const double r = block_max(mx, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 __global__ __launch_bounds__(kBlock) void lse_finish_max_kernel(const double *__restrict__ partials, int count,
                                                                 double *__restrict__ result) {
     __shared__ double lds[kWaves];
     double mx = -1.7976931348623157e308;
     for (int i = threadIdx.x; i < count; i += kBlock) mx = fmax(mx, partials[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = lds[0];
-        for (int w = 1; w < kWaves; ++w) r = fmax(r, lds[w]);
-        result[0] = r;
-    }
+    const double r = block_max(mx, lds);
+    if (threadIdx.x == 0) result[0] = r;
 }
 // partials[b] = sum exp(x - mx), partials[grid + b] = sum (x - c)^2
 template <typename T>
@@ -1016,40 +745,52 @@ int32_t box_clamp_async(hipStream_t s, int64_t n, int32_t dtype, void *x, double
 }
 
 // ------------------------------------------------------------------ host side
-// ---- the triangle form of the dense quadratic's evaluations (quadratic_tri6_kernel)
-// MEASURED (round 4, config 2, rocprofv3) and OFF by default (DZO_TUNE_QUAD_TRI=1 selects it, read when a
-// problem handle is created): the round's six evaluations take 26.7 us in quadratic_tri6_kernel + 21.1 us in its reduce
-// kernel (one window per block: 25 MB of row parts) or 50.6 us in all with four windows per block, against 32.8 us for
-// quadratic_phi6_kernel + its share of the finish reading the FULL matrix -- 5250-5330 against 6430-6460 step!()/s.  The
-// full matrix streams out of the Infinity Cache at 4.4 TB/s from 4096 independent column blocks; the triangle halves the
-// bytes but pays for six transposed wave reductions per chunk and a second kernel, and has 272 (or 1100) tiles to hide
-// its load latency with.  Bit-compatible with every search variant (the whole BFGS suite passes with it on).
-static bool quad_tri_knob() { return getenv("DZO_TUNE_QUAD_TRI") ? atoi(getenv("DZO_TUNE_QUAD_TRI")) != 0 : false; }
-static bool quad_tri_on(const dzo_problem_s *p) {
-    static const int min_n = getenv("DZO_TUNE_QUAD_TRI_MIN_N") ? atoi(getenv("DZO_TUNE_QUAD_TRI_MIN_N")) : 1024;
-    return p->tri_part != nullptr && p->n % 2 == 0 && p->n >= min_n && (reinterpret_cast<uintptr_t>(p->A) & 15u) == 0;
+// f(T{}) with T the problem's element type, for launches in functions that do not return a status (DZO_DISPATCH's
+// error branch returns an int32_t)
+template <typename F> static inline void with_dtype(int32_t dtype, F &&f) {
+    if (dtype == DZO_F64) f(double{}); else f(float{});
 }
-static inline int64_t quad_tri_doubles(int64_t n) {
-    const int64_t ranges = (n + kQtCW * kQtWPB - 1) / (kQtCW * kQtWPB), panels = (n + kQtPH - 1) / kQtPH;
-    return 6 * (ranges + panels) * n;
+// one block per column (or group of columns) of the dense quadratic's A
+static inline int quad_grid(int64_t columns) { return (int)(columns < 65535 ? columns : 65535); }
+
+// The three objectives whose value is a plain scaled sum of per-block partials: their profile name (null for every
+// other kind) and the launch that leaves the partials.
+static const char *scaled_sum_objective(int32_t kind) {
+    switch (kind) {
+    case DZO_PROBLEM_ROSENBROCK_CHAIN: return "objective_rosenbrock_chain";
+    case DZO_PROBLEM_QUADRATIC: return "objective_quadratic";
+    case DZO_PROBLEM_QUADRATIC_CHAIN: return "objective_quadratic_chain";
+    default: return nullptr;
+    }
 }
 template <typename T>
-static void quad_tri_launch(dzo_problem_s *p, hipStream_t s, const T *x, const PhiDir<T> &a, const PhiDir<T> &b, int32_t *flags, const PhiReqDev *dreq) {
+static void eval_partials_t(dzo_problem_s *p, hipStream_t s, const T *x, const double **partials, int64_t *count, double *scale) {
     const int64_t n = p->n;
-    const int64_t ranges = (n + kQtCW * kQtWPB - 1) / (kQtCW * kQtWPB), panels = (n + kQtPH - 1) / kQtPH;
-    double *rowpart = p->tri_part, *colpart = p->tri_part + 6 * ranges * n;
-    hipLaunchKernelGGL(quadratic_tri6_kernel<T>, dim3((unsigned)ranges, (unsigned)panels), dim3(kBlock), 0, s, n, (const T *)p->A, x, a, b, rowpart, colpart, dreq);
-    hipLaunchKernelGGL(quadratic_tri6_reduce_kernel<T>, dim3((unsigned)((n + kQtRI - 1) / kQtRI)), dim3(kBlock), 0, s, n, x, a, b,
-                       (const double *)rowpart, (const double *)colpart, p->scratch, flags, dreq);
+    *partials = p->scratch; *scale = 1.0;
+    if (p->kind == DZO_PROBLEM_ROSENBROCK_CHAIN) {
+        const int grid = stream_grid(n, Vec16<T>::N * 2);
+        hipLaunchKernelGGL(rosen_chain_eval_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, p->scratch);
+        *count = grid;
+    } else if (p->kind == DZO_PROBLEM_QUADRATIC_CHAIN) {
+        const int grid = stream_grid(n, 4);
+        hipLaunchKernelGGL(qchain_eval_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, (T)p->lambda, p->scratch);
+        *count = grid;
+    } else {                                                     // DZO_PROBLEM_QUADRATIC
+        hipLaunchKernelGGL((quadratic_kernel<T, false>), dim3(quad_grid(n)), dim3(kBlock), 0, s, n, (const T *)p->A, x,
+                           (T *)nullptr, p->scratch);
+        *count = n; *scale = 0.5;
+    }
 }
-// one plain evaluation at x itself (objective partials in scratch[0 .. n), gradient to g when given): request 0 of side a with dir = x, ts = 0
-template <typename T> static void quad_tri_eval(dzo_problem_s *p, hipStream_t s, const T *x, T *g) {
-    PhiDir<T> a, b;
-    memset(&a, 0, sizeof(a)); memset(&b, 0, sizeof(b));
-    a.dir = x; b.dir = x;
-    for (int r = 0; r < 3; ++r) { a.ref_req[r] = -1; b.ref_req[r] = -1; }
-    a.active[0] = 1; a.grad_out[0] = g;                     // x_t = fma(0, x, x) = x
-    quad_tri_launch<T>(p, s, x, a, b, nullptr, nullptr);
+
+// The scalars of the log-sum-exp objective, shared by its value and its gradient: max, its finish, the two sums, their finish.
+struct LseScalars { double *mx, *res; };                         // [mx], [f, se], behind the partials in the problem's scratch
+template <typename T> static LseScalars lse_scalars_launch(dzo_problem_s *p, hipStream_t s, const T *x, int grid) {
+    const LseScalars k = {p->scratch + 2 * kMaxPartialBlocks, p->scratch + 2 * kMaxPartialBlocks + 2};
+    hipLaunchKernelGGL(lse_max_kernel<T>, dim3(grid), dim3(kBlock), 0, s, p->n, x, p->scratch);
+    hipLaunchKernelGGL(lse_finish_max_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, k.mx);
+    hipLaunchKernelGGL(lse_sums_kernel<T>, dim3(grid), dim3(kBlock), 0, s, p->n, x, (const T *)p->c, k.mx, p->scratch);
+    hipLaunchKernelGGL(lse_finish_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, k.mx, p->lambda, k.res);
+    return k;
 }
 
 template <typename T> static int32_t eval_async_t(dzo_problem_s *p, hipStream_t s, const T *x, double *result_dev) {
@@ -1060,40 +801,19 @@ template <typename T> static int32_t eval_async_t(dzo_problem_s *p, hipStream_t 
         hipLaunchKernelGGL(rosen2d_eval_kernel<T>, dim3(1), dim3(64), 0, s, x, result_dev);
         break;
     }
-    case DZO_PROBLEM_ROSENBROCK_CHAIN: {
-        DZO_TIMED("objective_rosenbrock_chain", s);
-        const int grid = stream_grid(n, Vec16<T>::N * 2);
-        hipLaunchKernelGGL(rosen_chain_eval_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, p->scratch);
-        hipLaunchKernelGGL(finish_scaled_sum_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, (int64_t)grid, 1.0,
-                           result_dev);
-        break;
-    }
-    case DZO_PROBLEM_QUADRATIC: {
-        DZO_TIMED("objective_quadratic", s);
-        const int grid = (int)(n < 65535 ? n : 65535);
-        if (quad_tri_on(p)) quad_tri_eval<T>(p, s, x, (T *)nullptr);
-        else hipLaunchKernelGGL((quadratic_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s, n, (const T *)p->A, x,
-                                (T *)nullptr, p->scratch);
-        hipLaunchKernelGGL(finish_scaled_sum_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, n, 0.5, result_dev);
-        break;
-    }
+    case DZO_PROBLEM_ROSENBROCK_CHAIN:
+    case DZO_PROBLEM_QUADRATIC:
     case DZO_PROBLEM_QUADRATIC_CHAIN: {
-        DZO_TIMED("objective_quadratic_chain", s);
-        const int grid = stream_grid(n, 4);
-        hipLaunchKernelGGL(qchain_eval_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, (T)p->lambda, p->scratch);
-        hipLaunchKernelGGL(finish_scaled_sum_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, (int64_t)grid, 1.0, result_dev);
+        DZO_TIMED(scaled_sum_objective(p->kind), s);
+        const double *partials; int64_t count; double scale;
+        eval_partials_t<T>(p, s, x, &partials, &count, &scale);
+        hipLaunchKernelGGL(finish_scaled_sum_kernel, dim3(1), dim3(kBlock), 0, s, partials, count, scale, result_dev);
         break;
     }
     case DZO_PROBLEM_LSE: {
         DZO_TIMED("objective_lse", s);
-        const int grid = stream_grid(n, 4);
-        double *mx = p->scratch + 2 * kMaxPartialBlocks;       // [mx]
-        double *res = p->scratch + 2 * kMaxPartialBlocks + 2;   // [f, se]
-        hipLaunchKernelGGL(lse_max_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, p->scratch);
-        hipLaunchKernelGGL(lse_finish_max_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, mx);
-        hipLaunchKernelGGL(lse_sums_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, (const T *)p->c, mx, p->scratch);
-        hipLaunchKernelGGL(lse_finish_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, mx, p->lambda, res);
-        DZO_HIP(hipMemcpyAsync(result_dev, res, sizeof(double), hipMemcpyDeviceToDevice, s));
+        const LseScalars k = lse_scalars_launch<T>(p, s, x, stream_grid(n, 4));
+        DZO_HIP(hipMemcpyAsync(result_dev, k.res, sizeof(double), hipMemcpyDeviceToDevice, s));
         break;
     }
     case DZO_PROBLEM_PAIRWISE_LJ: {                          // point = [x | y | z], N = n / 3 (dzo_pairwise.hip)
@@ -1126,10 +846,8 @@ template <typename T> static int32_t grad_async_t(dzo_problem_s *p, hipStream_t 
     }
     case DZO_PROBLEM_QUADRATIC: {
         DZO_TIMED("gradient_quadratic", s);
-        const int grid = (int)(n < 65535 ? n : 65535);
-        if (quad_tri_on(p)) quad_tri_eval<T>(p, s, x, g);
-        else hipLaunchKernelGGL((quadratic_kernel<T, true>), dim3(grid), dim3(kBlock), 0, s, n, (const T *)p->A, x, g,
-                                (double *)nullptr);
+        hipLaunchKernelGGL((quadratic_kernel<T, true>), dim3(quad_grid(n)), dim3(kBlock), 0, s, n, (const T *)p->A, x, g,
+                           (double *)nullptr);
         break;
     }
     case DZO_PROBLEM_QUADRATIC_CHAIN: {
@@ -1140,13 +858,8 @@ template <typename T> static int32_t grad_async_t(dzo_problem_s *p, hipStream_t 
     case DZO_PROBLEM_LSE: {
         DZO_TIMED("gradient_lse", s);
         const int grid = stream_grid(n, 4);
-        double *mx = p->scratch + 2 * kMaxPartialBlocks;
-        double *res = p->scratch + 2 * kMaxPartialBlocks + 2;
-        hipLaunchKernelGGL(lse_max_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, p->scratch);
-        hipLaunchKernelGGL(lse_finish_max_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, mx);
-        hipLaunchKernelGGL(lse_sums_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, x, (const T *)p->c, mx, p->scratch);
-        hipLaunchKernelGGL(lse_finish_kernel, dim3(1), dim3(kBlock), 0, s, p->scratch, grid, mx, p->lambda, res);
-        hipLaunchKernelGGL(lse_grad_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, g, x, (const T *)p->c, mx, res + 1,
+        const LseScalars k = lse_scalars_launch<T>(p, s, x, grid);
+        hipLaunchKernelGGL(lse_grad_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, g, x, (const T *)p->c, k.mx, k.res + 1,
                            p->lambda);
         break;
     }
@@ -1176,12 +889,11 @@ int32_t problem_fused_post_async(dzo_problem_s *p, hipStream_t s, const void *x,
     const int vecn = p->dtype == DZO_F64 ? 2 : 4;
     const int grid = stream_grid(n, vecn * 2);
     const void *xo = xold_src ? xold_src : dx, *go = gold_src ? gold_src : g;
-    if (p->dtype == DZO_F64)
-        hipLaunchKernelGGL(rosen_accept_grad_delta_kernel<double>, dim3(grid), dim3(kBlock), 0, s, n, (const double *)x,
-                           (double *)dx, (double *)g, (double *)dg, partials, gate, (const double *)xo, (const double *)go);
-    else
-        hipLaunchKernelGGL(rosen_accept_grad_delta_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n, (const float *)x,
-                           (float *)dx, (float *)g, (float *)dg, partials, gate, (const float *)xo, (const float *)go);
+    with_dtype(p->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(rosen_accept_grad_delta_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, (const T *)x, (T *)dx, (T *)g, (T *)dg,
+                           partials, gate, (const T *)xo, (const T *)go);
+    });
     *grid_out = grid;
     DZO_HIP(hipGetLastError());
     return DZO_OK;
@@ -1199,18 +911,18 @@ bool problem_trial_eval_async(dzo_problem_s *p, hipStream_t s, void *x, void *ba
     int egrid = (int)((rows + kBlock - 1) / kBlock);
     if (egrid < 1) egrid = 1;
     if ((int64_t)grid + egrid > 2 * kMaxPartialBlocks) return false;    // partials live in p->scratch
-    {
-        DZO_TIMED("lbfgs_trial_objective", s);
-#define L(TT, F) hipLaunchKernelGGL((rosen_trial_eval_kernel<TT, F>), dim3(grid), dim3(kBlock), 0, s, n, (TT *)x, (TT *)backup, (const TT *)d, (TT)t, changed, p->scratch)
-        if (p->dtype == DZO_F64) { if (first) L(double, true); else L(double, false); }
-        else { if (first) L(float, true); else L(float, false); }
-#undef L
-    }
-    {
-        DZO_TIMED("objective_edge_terms", s);
-        if (p->dtype == DZO_F64) hipLaunchKernelGGL(rosen_edge_terms_kernel<double>, dim3(egrid), dim3(kBlock), 0, s, n, (const double *)x, p->scratch + grid);
-        else hipLaunchKernelGGL(rosen_edge_terms_kernel<float>, dim3(egrid), dim3(kBlock), 0, s, n, (const float *)x, p->scratch + grid);
-    }
+    with_dtype(p->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        {
+            DZO_TIMED("lbfgs_trial_objective", s);
+            hipLaunchKernelGGL((first ? rosen_trial_eval_kernel<T, true> : rosen_trial_eval_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s,
+                               n, (T *)x, (T *)backup, (const T *)d, (T)t, changed, p->scratch);
+        }
+        {
+            DZO_TIMED("objective_edge_terms", s);
+            hipLaunchKernelGGL(rosen_edge_terms_kernel<T>, dim3(egrid), dim3(kBlock), 0, s, n, (const T *)x, p->scratch + grid);
+        }
+    });
     *partials = p->scratch; *count = grid + egrid; *scale = 1.0;
     return true;
 }
@@ -1222,25 +934,11 @@ bool problem_phi_async(dzo_problem_s *p, hipStream_t s, const void *x, const voi
     if (!p || p->kind != DZO_PROBLEM_QUADRATIC || p->l2 != 0.0 || p->cons_on) return false;
     const int64_t n = p->n;
     DZO_TIMED("objective_quadratic_phi", s);
-    const int grid = (int)(n < 65535 ? n : 65535);
-    if (quad_tri_on(p)) {
-        auto go = [&](auto tag) {
-            using T = decltype(tag);
-            PhiDir<T> a, b;
-            memset(&a, 0, sizeof(a)); memset(&b, 0, sizeof(b));
-            a.dir = (const T *)dir; b.dir = (const T *)dir;
-            for (int r = 0; r < 3; ++r) { a.ref_req[r] = -1; b.ref_req[r] = -1; }
-            a.active[0] = 1; a.ts[0] = (T)ts; a.point_out[0] = (T *)point_out; a.ref[0] = (const T *)ref;
-            // (single-request flags live in flags[0..2]: the same words request 0 of side a uses)
-            quad_tri_launch<T>(p, s, (const T *)x, a, b, flags, nullptr);
-        };
-        if (p->dtype == DZO_F64) go(double{}); else go(float{});
-    } else if (p->dtype == DZO_F64)
-        hipLaunchKernelGGL(quadratic_phi_kernel<double>, dim3(grid), dim3(kBlock), 0, s, n, (const double *)p->A, (const double *)x,
-                           (const double *)dir, ts, (double *)point_out, p->scratch, flags, (const double *)ref);
-    else
-        hipLaunchKernelGGL(quadratic_phi_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n, (const float *)p->A, (const float *)x,
-                           (const float *)dir, (float)ts, (float *)point_out, p->scratch, flags, (const float *)ref);
+    with_dtype(p->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(quadratic_phi_kernel<T>, dim3(quad_grid(n)), dim3(kBlock), 0, s, n, (const T *)p->A, (const T *)x,
+                           (const T *)dir, (T)ts, (T *)point_out, p->scratch, flags, (const T *)ref);
+    });
     hipLaunchKernelGGL(finish_phi_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)p->scratch, n, 0.5, result_dev, flags);
     return true;
 }
@@ -1254,8 +952,7 @@ bool problem_phi6_async(dzo_problem_s *p, hipStream_t s, const void *x, const Ph
     const int64_t n = p->n;
     if (p->scratch_doubles < 6 * n) return false;
     DZO_TIMED("objective_quadratic_phi", s);
-    const int grid = (int)(n < 65535 ? n : 65535);
-    auto launch = [&](auto tag) {
+    with_dtype(p->dtype, [&](auto tag) {
         using T = decltype(tag);
         PhiDir<T> d[2];
         for (int side = 0; side < 2; ++side) {
@@ -1269,27 +966,13 @@ bool problem_phi6_async(dzo_problem_s *p, hipStream_t s, const void *x, const Ph
                 d[side].active[r] = req[side].active[r] ? 1 : 0;
             }
         }
-        if (quad_tri_on(p)) quad_tri_launch<T>(p, s, (const T *)x, d[0], d[1], flags, dreq);
-        else {
-            // DZO_TUNE_PHI6_COLS: columns of A a block walks at once.  1: the one-column kernel (32.4 us per round at config 2);
-            // 2, the default: two columns, ONE set of requests ahead, 108 registers = four blocks per CU, so that the 2048 groups
-            // are two full rounds of the 1024 resident blocks (27.3 us); 22: two sets ahead, 140 registers, three blocks per CU,
-            // 2.67 rounds (28.8 us); 4: four columns, two sets ahead (30.2 us).  Forms pressed into more blocks per CU than their
-            // registers allow spill and lose everything (35-55 us).
-            const int cols_knob = getenv("DZO_TUNE_PHI6_COLS") ? atoi(getenv("DZO_TUNE_PHI6_COLS")) : 2;
-            constexpr int N = Vec16<T>::N;
-            const int cg = (n % N != 0 || n < 64) ? 1 : cols_knob;
-            const int cgc = cg == 22 ? 2 : (cg > 1 ? cg : 1);
-            const int64_t groups = (n + cgc - 1) / cgc;
-            const int ggrid = (int)(groups < 65535 ? groups : 65535);
-            if (cg == 4) hipLaunchKernelGGL((quadratic_phi6_cols_kernel<T, 4>), dim3(ggrid), dim3(kBlock), 0, s, n, (const T *)p->A, (const T *)x, d[0], d[1], p->scratch, flags, dreq);
-            else if (cg == 2) hipLaunchKernelGGL((quadratic_phi6_cols_kernel<T, 2, 1, (sizeof(T) == 8 ? 4 : 2)>), dim3(ggrid), dim3(kBlock), 0, s, n, (const T *)p->A, (const T *)x, d[0], d[1], p->scratch, flags, dreq);
-            else if (cg == 22) hipLaunchKernelGGL((quadratic_phi6_cols_kernel<T, 2, 2, 1>), dim3(ggrid), dim3(kBlock), 0, s, n, (const T *)p->A, (const T *)x, d[0], d[1], p->scratch, flags, dreq);
-            else hipLaunchKernelGGL(quadratic_phi6_kernel<T>, dim3(grid), dim3(kBlock), 0, s, n, (const T *)p->A, (const T *)x, d[0], d[1],
-                                    p->scratch, flags, dreq);
-        }
-    };
-    if (p->dtype == DZO_F64) launch(double{}); else launch(float{});
+        // DZO_TUNE_PHI6_COLS=1: the one-column kernel everywhere (32.4 us per round at config 2 against 27.3); it is the
+        // only form for a ragged or a small n
+        const bool one_col = n % Vec16<T>::N != 0 || n < 64 || (getenv("DZO_TUNE_PHI6_COLS") && atoi(getenv("DZO_TUNE_PHI6_COLS")) == 1);
+        const int ggrid = quad_grid(one_col ? n : (n + kPhi6Cols - 1) / kPhi6Cols);
+        hipLaunchKernelGGL(one_col ? quadratic_phi6_kernel<T> : quadratic_phi6_cols_kernel<T>, dim3(ggrid), dim3(kBlock), 0, s, n,
+                           (const T *)p->A, (const T *)x, d[0], d[1], p->scratch, flags, dreq);
+    });
     if (dreq) return true;                                       // (the caller's finish kernel sums, advances the searches and posts the next requests)
     hipLaunchKernelGGL(finish_phi6_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)p->scratch, n, 0.5, result_dev, flags, ticket);
     return true;
@@ -1300,35 +983,13 @@ bool problem_phi6_async(dzo_problem_s *p, hipStream_t s, const void *x, const Ph
 // objectives whose finish is not a plain scaled sum.
 bool problem_eval_partials_async(dzo_problem_s *p, hipStream_t s, const void *x, const double **partials,
                                  int64_t *count, double *scale) {
-    if (p->l2 != 0.0) return false;
-    const int64_t n = p->n;
-    if (p->kind == DZO_PROBLEM_ROSENBROCK_CHAIN) {
-        DZO_TIMED("objective_rosenbrock_chain", s);
-        const int vecn = p->dtype == DZO_F64 ? 2 : 4;
-        const int grid = stream_grid(n, vecn * 2);
-        if (p->dtype == DZO_F64) hipLaunchKernelGGL(rosen_chain_eval_kernel<double>, dim3(grid), dim3(kBlock), 0, s, n, (const double *)x, p->scratch);
-        else hipLaunchKernelGGL(rosen_chain_eval_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n, (const float *)x, p->scratch);
-        *partials = p->scratch; *count = grid; *scale = 1.0;
-        return true;
-    }
-    if (p->kind == DZO_PROBLEM_QUADRATIC_CHAIN) {
-        DZO_TIMED("objective_quadratic_chain", s);
-        const int grid = stream_grid(n, 4);
-        if (p->dtype == DZO_F64) hipLaunchKernelGGL(qchain_eval_kernel<double>, dim3(grid), dim3(kBlock), 0, s, n, (const double *)x, (double)p->lambda, p->scratch);
-        else hipLaunchKernelGGL(qchain_eval_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n, (const float *)x, (float)p->lambda, p->scratch);
-        *partials = p->scratch; *count = grid; *scale = 1.0;
-        return true;
-    }
-    if (p->kind == DZO_PROBLEM_QUADRATIC) {
-        DZO_TIMED("objective_quadratic", s);
-        const int grid = (int)(n < 65535 ? n : 65535);
-        if (quad_tri_on(p)) { if (p->dtype == DZO_F64) quad_tri_eval<double>(p, s, (const double *)x, (double *)nullptr); else quad_tri_eval<float>(p, s, (const float *)x, (float *)nullptr); }
-        else if (p->dtype == DZO_F64) hipLaunchKernelGGL((quadratic_kernel<double, false>), dim3(grid), dim3(kBlock), 0, s, n, (const double *)p->A, (const double *)x, (double *)nullptr, p->scratch);
-        else hipLaunchKernelGGL((quadratic_kernel<float, false>), dim3(grid), dim3(kBlock), 0, s, n, (const float *)p->A, (const float *)x, (float *)nullptr, p->scratch);
-        *partials = p->scratch; *count = n; *scale = 0.5;
-        return true;
-    }
-    return false;
+    if (p->l2 != 0.0 || !scaled_sum_objective(p->kind)) return false;
+    DZO_TIMED(scaled_sum_objective(p->kind), s);
+    with_dtype(p->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        eval_partials_t<T>(p, s, (const T *)x, partials, count, scale);
+    });
+    return true;
 }
 
 int32_t problem_eval_async(dzo_problem_s *p, hipStream_t s, const void *x, double *result_dev) {
@@ -1371,18 +1032,17 @@ static int32_t problem_alloc_workspace(dzo_problem_s *p) {
     e = hipHostMalloc((void **)&p->host, sizeof(double) * 4, hipHostMallocDefault);
     if (e != hipSuccess) { (void)hipFree(p->scratch); p->scratch = nullptr; p->host = nullptr; return hip_fail(e, "hipHostMalloc", __FILE__, __LINE__); }
     p->result = p->scratch + scratch - 8;
-    p->tri_part = nullptr;
-    if (p->kind == DZO_PROBLEM_QUADRATIC && n % 2 == 0 && n >= 512 && quad_tri_knob()) {
-        // row / column parts of the triangle form (2.3 % of A's own size); without them the full-matrix kernels serve
-        if (hipMalloc((void **)&p->tri_part, sizeof(double) * (size_t)quad_tri_doubles(n)) != hipSuccess) { (void)hipGetLastError(); p->tri_part = nullptr; }
-    }
     return DZO_OK;
+}
+static void problem_free_workspace(dzo_problem_s *p) {
+    if (p->scratch) (void)hipFree(p->scratch);
+    if (p->host) (void)hipHostFree(p->host);
 }
 
 int32_t problem_view_create(dzo_problem_s *parent, dzo_problem_s **out) {
     dzo_problem_s *root = parent->parent ? parent->parent : parent;
     dzo_problem_s *v = new dzo_problem_s(*root);
-    v->parent = root; v->scratch = nullptr; v->result = nullptr; v->host = nullptr; v->tri_part = nullptr;
+    v->parent = root; v->scratch = nullptr; v->result = nullptr; v->host = nullptr;
     const int32_t rc = problem_alloc_workspace(v);
     if (rc != DZO_OK) { delete v; return rc; }
     *out = v;
@@ -1399,9 +1059,7 @@ void problem_view_sync(dzo_problem_s *v) {
 
 void problem_view_destroy(dzo_problem_s *v) {
     if (!v || !v->parent) return;                            // only views are owned by optimizers
-    if (v->scratch) (void)hipFree(v->scratch);
-    if (v->tri_part) (void)hipFree(v->tri_part);
-    if (v->host) (void)hipHostFree(v->host);
+    problem_free_workspace(v);
     delete v;
 }
 
@@ -1463,9 +1121,7 @@ int32_t dzo_box_clamp(int64_t n, int32_t dtype, void *x_dev, double lower_bound,
 
 int32_t dzo_problem_destroy(dzo_problem_t p) {
     if (!p) return DZO_OK;
-    (void)hipFree(p->scratch);
-    if (p->tri_part) (void)hipFree(p->tri_part);
-    (void)hipHostFree(p->host);
+    problem_free_workspace(p);
     delete p;
     return DZO_OK;
 }

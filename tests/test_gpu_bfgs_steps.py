@@ -333,47 +333,23 @@ def test_per_instance_matrices_constructor_rejects_what_it_cannot_run():
     dzo._check(dzo.lib().dzo_bfgs_batch_destroy(h))
 
 
-def test_dense_step_on_the_lower_triangle_of_A_matches_the_oracle(monkeypatch):
-    """DZO_TUNE_QUAD_TRI=1 (off by default: measured slower, csrc/dzo_problems.hip): every evaluation of the dense quadratic
-    -- objective, gradient and the line searches' rounds of up to six trial points -- reads the LOWER triangle of the
-    symmetric A only (quadratic_tri6_kernel).  Per step from the oracle's installed state, as the default path is tested."""
-    monkeypatch.setenv("DZO_TUNE_QUAD_TRI", "1")
-    n = 1024
-    rng = np.random.default_rng(5)
-    U = rng.standard_normal((n, 8))
-    A = np.diag(1.0 + 99.0 * rng.random(n)) + U @ U.T / 8
-    A = 0.5 * (A + A.T)
-    x0 = rng.random(n) - 0.5
-    ref = orc.BFGS(orc.Problem(orc.QUADRATIC, n, A=A), x0.copy(), 1.0)
-    prob = dzo.Problem(dzo.QUADRATIC, n, A=A)
-    opt = dzo.BFGSOptimizer(prob, None, dzo.DeviceArray.from_host(x0), 1.0)
-    dx = dzo.DeviceArray.from_host(x0)
-    assert abs(prob(dx) - ref.current_objective_value) <= 1e-12 * abs(ref.current_objective_value)
-    g = prob.gradient_(dzo.DeviceArray(n, np.float64), dx).to_host()
-    assert np.linalg.norm(g - ref.current_gradient) <= 1e-12 * np.linalg.norm(ref.current_gradient)
-    for it in range(8):
-        opt.step(); ref.step()
-        assert opt.last_step_type == ref.last_step_type and opt.iteration_count == ref.iteration_count, it
-        x = opt.current_point.to_host()
-        assert np.linalg.norm(x - ref.current_point) <= 1e-9 * np.linalg.norm(ref.current_point), it
-        assert opt.current_objective_value == pytest.approx(ref.current_objective_value, rel=1e-9)
-        assert np.array_equal(opt.current_gradient.to_host(), prob.gradient_(dzo.DeviceArray(n, np.float64), opt.current_point).to_host())   # run_and_test! :1025-1032
-
-
-@pytest.mark.parametrize("n,dtype", [(1024, np.float64), (1030, np.float64), (772, np.float32), (96, np.float64)])
+@pytest.mark.parametrize("n,dtype", [(1024, np.float64), (1030, np.float64), (772, np.float32), (96, np.float64),
+                                     (64, np.float64), (62, np.float64), (202, np.float32)])
 def test_search_rounds_over_several_columns_at_once_are_the_same_bits(n, dtype, monkeypatch):
-    """quadratic_phi6_cols_kernel (default: two columns of A per block, three register sets of requests in flight, every
-    request unconditional) keeps the one-column kernel's assignment of elements to threads and its order of sums, so a run
-    with DZO_TUNE_PHI6_COLS = 1 / 2 / 22 / 4 is the same run bit for bit -- points, gradients (the search's by-product against a
-    separate evaluation, run_and_test! legacy :1025-1032), step types and evaluation counts.  n = 1030 / 772: a last iteration
-    that only some threads have, a last group with a column past the end."""
+    """quadratic_phi6_cols_kernel (default: two columns of A per block, two register sets of requests in flight -- one being
+    computed, one on its way -- every request unconditional) keeps the one-column kernel's assignment of elements to threads and
+    its order of sums, so a run with DZO_TUNE_PHI6_COLS = 1 (quadratic_phi6_kernel) / 2 (the default) is the same run bit for bit
+    -- points, gradients (the search's by-product against a separate evaluation, run_and_test! legacy :1025-1032), step types and
+    evaluation counts.  n = 1030 / 772: a last iteration that only some threads have, a last group with a column past the end.
+    The sizes where the choice of kernel flips: n = 64, the smallest on the two-column kernel; n = 62, the largest even n below
+    it (the one-column kernel's vector path under either setting); n = 202 in fp32, n % 4 != 0 (its scalar path under either)."""
     rng = np.random.default_rng(7)
     U = rng.standard_normal((n, 6))
     A = np.diag(1.0 + 49.0 * rng.random(n)) + U @ U.T / 6
     A = (0.5 * (A + A.T)).astype(dtype)
     x0 = (rng.random(n) - 0.5).astype(dtype)
     runs = []
-    for cols in ("1", "2", "22", "4"):
+    for cols in ("1", "2"):
         monkeypatch.setenv("DZO_TUNE_PHI6_COLS", cols)
         prob = dzo.Problem(dzo.QUADRATIC, n, dtype=dtype, A=A)
         opt = dzo.BFGSOptimizer(prob, None, dzo.DeviceArray.from_host(x0), 1.0)
