@@ -200,6 +200,12 @@ ABI = {
     "dzo_pairwise_batch_hessian": [_i32, _i64, _i64, _i32, _vp, _vp],
     "dzo_symmetric_batch_eigen": [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32],
     "dzo_symeig_plan": [_i64, _i32, _P(_i32), _P(_i64), _P(_i64)],
+    "dzo_modefollow_batch_apply": [_i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp],
+    "dzo_modefollow_batch_create": [_i32, _i64, _i64, _i32, _vp, _i32, _dbl, _dbl, _dbl, _P(_vp)], "dzo_modefollow_batch_destroy": [_vp],
+    "dzo_modefollow_batch_set_start_mode": [_vp, _i32], "dzo_modefollow_batch_set_directions": [_vp, _vp],
+    "dzo_modefollow_batch_step": [_vp, _i32, _P(_i32)], "dzo_modefollow_batch_count_active": [_vp, _P(_i64)],
+    "dzo_modefollow_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_modefollow_batch_read": [_vp, _i32, _vp],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -871,6 +877,167 @@ def hessian_spectrum(points, n_particles, vectors=False, radial=RADIAL_LENNARD_J
         raise DzoError(6, "hessian_spectrum: no convergence in instances %s" % np.flatnonzero(sweeps < 0).tolist())
     ev = w.to_host().reshape(batch, 3 * n).astype(np.float64)
     return (ev, v.to_host().reshape(batch, 3 * n, 3 * n)) if vectors else ev
+
+
+# ------------------------------------------------------------------------------ batched eigenvector following
+MODEFOLLOW_MAX_PARTICLES = 128
+MODEFOLLOW_ACTIVE, MODEFOLLOW_CONVERGED, MODEFOLLOW_FAILED = 0, 1, 2
+(MODEFOLLOW_POINTS, MODEFOLLOW_GRADIENTS, MODEFOLLOW_ENERGIES, MODEFOLLOW_GRMS, MODEFOLLOW_STATUS, MODEFOLLOW_INDEX, MODEFOLLOW_ZEROS,
+ MODEFOLLOW_FOLLOWED_MODE, MODEFOLLOW_STEP_LENGTHS, MODEFOLLOW_ITERATION_COUNTS, MODEFOLLOW_EIGENVALUES, MODEFOLLOW_EIGENVECTORS,
+ MODEFOLLOW_SWEEPS, MODEFOLLOW_FOLLOW) = range(14)
+
+
+def modefollow_apply(points, eigenvalues, eigenvectors, n_particles, target_index=0, start_mode=0, max_step=0.2, zero_tol=1e-4,
+                     grad_tol=0.0, follow=None, follow_set=None, radial=RADIAL_LENNARD_JONES):
+    """``dzo_modefollow_batch_apply``: ONE eigenvector-following step (include/dzo.h) of every instance from modes the caller
+    supplies.  ``points`` (DeviceArray, ``3 * n_particles * batch`` elements) is moved in place; ``eigenvalues`` ``(batch, 3N)``
+    ascending and ``eigenvectors`` ``(batch, 3N, 3N)`` in the device layout (``[b, k, :]`` is the vector of eigenvalue k) are
+    DeviceArrays or host arrays, which are uploaded.  ``target_index=1`` needs ``follow`` (DeviceArray ``(batch, 3N)``, updated)
+    and ``follow_set`` (DeviceArray of int32 ``(batch,)``, updated).  Returns a dict of host arrays: ``energies``, ``gradients``,
+    ``projections`` (F), ``grms``, ``status``, ``index``, ``zeros``, ``followed_mode``, ``step_lengths``."""
+    n = int(n_particles)
+    n3 = 3 * n
+    batch = points.size // n3 if n > 0 else 0
+    assert points.size == n3 * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    lam, vec = _as_dev(eigenvalues, points.dtype), _as_dev(eigenvectors, points.dtype)
+    assert lam.dtype == points.dtype and vec.dtype == points.dtype, "points and modes must have one element type"
+    assert lam.size == n3 * batch and vec.size == n3 * n3 * batch, "modes must hold 3N and 3N * 3N elements per instance"
+    if int(target_index) == 1:
+        assert follow is not None and follow_set is not None, "target_index=1 needs follow and follow_set"
+        assert follow.size == n3 * batch and follow.dtype == points.dtype and follow_set.size == batch and follow_set.dtype == np.int32
+    e, g, f = DeviceArray(batch, points.dtype), DeviceArray((batch, n3), points.dtype), DeviceArray.zeros((batch, n3), points.dtype)
+    grms, sl = DeviceArray(batch, np.float64), DeviceArray(batch, np.float64)
+    st, ix, zr, fm = (DeviceArray(batch, np.int32) for _ in range(4))
+    _check(lib().dzo_modefollow_batch_apply(radial, n, batch, _dt(points.dtype), points.ptr, lam.ptr, vec.ptr,
+                                            follow.ptr if follow is not None else None, follow_set.ptr if follow_set is not None else None,
+                                            int(target_index), int(start_mode), float(max_step), float(zero_tol), float(grad_tol), e.ptr, g.ptr,
+                                            f.ptr, grms.ptr, st.ptr, ix.ptr, zr.ptr, fm.ptr, sl.ptr))
+    return dict(energies=e.to_host(), gradients=g.to_host(), projections=f.to_host(), grms=grms.to_host(), status=st.to_host(),
+                index=ix.to_host(), zeros=zr.to_host(), followed_mode=fm.to_host(), step_lengths=sl.to_host())
+
+
+class ModeFollowing(_HandleArrays):
+    """Eigenvector following (Cerjan-Miller / Wales; include/dzo.h states the step) of many small Lennard-Jones clusters at once:
+    ``step(k)`` enqueues, k times, the dense Hessians, their eigenvalues and eigenvectors and the step kernel, with no host wait
+    in between.  ``target_index=0`` polishes minima, ``target_index=1`` searches transition states.  ``points`` is a DeviceArray
+    of ``3 * n_particles * batch`` elements (the tempering replica layout), aliased and moved.  An instance ends CONVERGED
+    (``grms <= grad_tol``) or FAILED (non-finite values, no convergence of the eigensolver, no mode to follow) and is then left
+    alone; ``index`` and ``zeros`` tell what kind of stationary point it ended on."""
+    _prefix = "dzo_modefollow_batch_"
+    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
+
+    def __init__(self, points, n_particles, target_index=0, max_step=0.2, zero_tol=1e-4, grad_tol=1e-10, radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.points = points
+        self.dtype = points.dtype
+        self.n_particles = int(n_particles)
+        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
+        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        h = C.c_void_p()
+        _check(lib().dzo_modefollow_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, int(target_index),
+                                                 float(max_step), float(zero_tol), float(grad_tol), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            lib().dzo_modefollow_batch_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_start_mode(self, mode):
+        _check(lib().dzo_modefollow_batch_set_start_mode(self.h, int(mode)))
+
+    def set_directions(self, directions):
+        """An initial followed vector per instance: a DeviceArray or host array ``(batch, 3N)``."""
+        d = _as_dev(directions, self.dtype)
+        assert d.size == 3 * self.n_particles * self.batch and d.dtype == self.dtype
+        _check(lib().dzo_modefollow_batch_set_directions(self.h, d.ptr))
+        synchronize()                                       # `d` may be a temporary
+
+    def step(self, steps=1, wait=True):
+        """``steps`` steps of every ACTIVE instance.  ``wait=True``: blocks and returns whether no instance is ACTIVE any more;
+        ``wait=False``: enqueues only and returns None."""
+        if not wait:
+            _check(lib().dzo_modefollow_batch_step(self.h, int(steps), None))
+            return None
+        flag = C.c_int32(0)
+        _check(lib().dzo_modefollow_batch_step(self.h, int(steps), C.byref(flag)))
+        return bool(flag.value)
+
+    def run(self, max_steps, steps_per_call=10):
+        """Steps until no instance is ACTIVE, at most ``max_steps`` per instance.  Returns the steps enqueued."""
+        done, taken = self.count_active() == 0, 0
+        while not done and taken < max_steps:
+            k = min(int(steps_per_call), int(max_steps) - taken)
+            done = self.step(k)
+            taken += k
+        return taken
+
+    def count_active(self):
+        n = C.c_int64(0)
+        _check(lib().dzo_modefollow_batch_count_active(self.h, C.byref(n)))
+        return int(n.value)
+
+    def _shape(self, what):
+        b, n3 = self.batch, 3 * self.n_particles
+        vec, sc, i32, f64 = ((b, n3), self.dtype), ((b,), self.dtype), ((b,), np.int32), ((b,), np.float64)
+        return {MODEFOLLOW_POINTS: vec, MODEFOLLOW_GRADIENTS: vec, MODEFOLLOW_ENERGIES: sc, MODEFOLLOW_GRMS: f64, MODEFOLLOW_STATUS: i32,
+                MODEFOLLOW_INDEX: i32, MODEFOLLOW_ZEROS: i32, MODEFOLLOW_FOLLOWED_MODE: i32, MODEFOLLOW_STEP_LENGTHS: f64,
+                MODEFOLLOW_ITERATION_COUNTS: ((b,), np.int64), MODEFOLLOW_EIGENVALUES: vec,
+                MODEFOLLOW_EIGENVECTORS: ((b, n3, n3), self.dtype), MODEFOLLOW_SWEEPS: i32, MODEFOLLOW_FOLLOW: vec}[what]
+
+    current_points = property(lambda self: self.read(MODEFOLLOW_POINTS))
+    current_gradients = property(lambda self: self.read(MODEFOLLOW_GRADIENTS))
+    energies = property(lambda self: self.read(MODEFOLLOW_ENERGIES))
+    grms = property(lambda self: self.read(MODEFOLLOW_GRMS))
+    status = property(lambda self: self.read(MODEFOLLOW_STATUS))
+    index = property(lambda self: self.read(MODEFOLLOW_INDEX))
+    zeros = property(lambda self: self.read(MODEFOLLOW_ZEROS))
+    followed_mode = property(lambda self: self.read(MODEFOLLOW_FOLLOWED_MODE))
+    step_lengths = property(lambda self: self.read(MODEFOLLOW_STEP_LENGTHS))
+    iteration_counts = property(lambda self: self.read(MODEFOLLOW_ITERATION_COUNTS))
+    eigenvalues = property(lambda self: self.read(MODEFOLLOW_EIGENVALUES))
+    eigenvectors = property(lambda self: self.read(MODEFOLLOW_EIGENVECTORS))
+    sweeps = property(lambda self: self.read(MODEFOLLOW_SWEEPS))
+    follow = property(lambda self: self.read(MODEFOLLOW_FOLLOW))
+
+
+def polish_minima(points, n_particles, grad_tol=1e-10, max_steps=50, max_step=0.2, zero_tol=1e-4, radial=RADIAL_LENNARD_JONES):
+    """Polishes the points a quench left at ``is_stuck`` (a DeviceArray, moved in place) with eigenvector following of target
+    index 0 until ``grms <= grad_tol``, at most ``max_steps`` steps.  Returns the ``ModeFollowing`` handle: ``status``,
+    ``energies``, ``grms``, ``index`` and ``zeros`` tell how every instance ended."""
+    mf = ModeFollowing(points, n_particles, 0, max_step, zero_tol, grad_tol, radial)
+    mf.run(max_steps)
+    return mf
+
+
+def find_saddles(minima, n_particles, start_mode=0, kick=0.05, grad_tol=1e-10, max_steps=300, max_step=0.1, zero_tol=1e-4,
+                 polish_steps=50, radial=RADIAL_LENNARD_JONES):
+    """Transition-state searches from the minima in ``minima`` (a DeviceArray, moved in place): polishes them
+    (``polish_minima``), displaces every polished minimum by ``kick`` along its ``start_mode``-th non-zero eigenvector, sets that
+    eigenvector as the followed vector and follows it uphill (target index 1) for at most ``max_steps`` steps.  Returns
+    ``(saddles, polished)``: the two ``ModeFollowing`` handles; ``saddles.index == 1`` with ``status == MODEFOLLOW_CONVERGED``
+    marks the transition states, ``polished.energies`` holds the minima's energies."""
+    n3 = 3 * int(n_particles)
+    polished = polish_minima(minima, n_particles, grad_tol, polish_steps, 0.2, zero_tol, radial)
+    # the modes at the polished minima: those of the step that found them converged
+    lam, vec, x = polished.eigenvalues.astype(np.float64), polished.eigenvectors, polished.current_points
+    dirs = np.zeros((polished.batch, n3), dtype=minima.dtype)
+    for b in range(polished.batch):
+        nonzero = np.flatnonzero(np.abs(lam[b]) > float(zero_tol))
+        if len(nonzero) > int(start_mode):
+            dirs[b] = vec[b, nonzero[int(start_mode)]]
+    minima.upload((x + np.asarray(kick, dtype=minima.dtype) * dirs).reshape(minima.shape))
+    saddles = ModeFollowing(minima, n_particles, 1, max_step, zero_tol, grad_tol, radial)
+    saddles.set_start_mode(start_mode)
+    saddles.set_directions(dirs)
+    saddles.run(max_steps)
+    return saddles, polished
 
 
 # ------------------------------------------------------------------------------ profiling

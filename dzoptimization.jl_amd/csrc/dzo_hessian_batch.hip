@@ -27,6 +27,7 @@
 // are stored once at the end.  For a fixed column and row component the lanes' addresses a N + i are consecutive: every store
 // instruction of the pair loop is coalesced.  The kernel is bound by its writes, 9 N^2 elements per instance against N^2 pair
 // terms.  Nothing is accumulated in memory: an entry is written once, by one lane.
+#include "dzo_chain.h"
 #include "dzo_cluster.h"
 #include "dzo_pairwise.h"
 
@@ -220,6 +221,13 @@ template <typename T> static void hb_launch_hvp(hipStream_t s, int64_t batch, co
 template <typename T> static void hb_launch_hessian(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
     if (a.N <= 64) hipLaunchKernelGGL((hess_batch_wave_hessian_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((hess_batch_block_hessian_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+}
+
+// dzo_chain.h: the launch of dzo_pairwise_batch_hessian on `s`, checked arguments, no wait
+int32_t hb_enqueue_hessian(hipStream_t s, int32_t dtype, int N, int64_t batch, const void *points, void *hessians) {
+    DZO_DISPATCH(dtype, hb_launch_hessian<T>(s, batch, HessBatchArgs<T>{N, (int64_t)3 * N, (const T *)points, nullptr, (T *)hessians, nullptr}));
+    DZO_HIP(hipGetLastError());
+    return DZO_OK;
 }
 
 }  // namespace dzo

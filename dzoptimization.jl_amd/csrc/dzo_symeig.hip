@@ -15,6 +15,7 @@
 // its column phase, a pair per lane, and rotates eight pairs at a time, all loads ahead of the first store and no branch between
 // them: with one wave per SIMD nothing else hides the latency of the storage.  The pairs of a round are disjoint, so every
 // element has one writer per phase: two barriers per round, no atomics.  V is updated in the output array, with the column phase.
+#include "dzo_chain.h"
 #include "dzo_common.h"
 #include "dzo_symeig_plan.h"
 
@@ -246,6 +247,26 @@ static int32_t se_check_size(int64_t n, int32_t dtype) {
     DZO_REQUIRE(n >= 1, DZO_ERR_INVALID, "n must be at least 1 (got %lld)", (long long)n);
     DZO_REQUIRE(n <= DZO_SYMEIG_MAX_N, DZO_ERR_UNSUPPORTED, "n = %lld: one block iterates on an instance, up to n = %d", (long long)n,
                 DZO_SYMEIG_MAX_N);
+    return DZO_OK;
+}
+
+// dzo_chain.h: raises the LDS attribute of the kernel this (n, dtype) launches; once per handle, no launch
+int32_t se_prepare(int64_t n, int32_t dtype) {
+    const SymeigPlan plan = symeig_plan(n, dtype);
+    if (plan.lds_bytes > 48 * 1024)
+        DZO_HIP(hipFuncSetAttribute(dtype == DZO_F64 ? se_kernel<double>(plan.storage) : se_kernel<float>(plan.storage),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSymeigLdsLimit));
+    return DZO_OK;
+}
+
+// dzo_chain.h: the launch of dzo_symmetric_batch_eigen on `s`, checked arguments, no wait
+int32_t se_enqueue(hipStream_t s, int64_t n, int64_t batch, int32_t dtype, const void *matrices, void *work, void *eigenvalues, void *eigenvectors,
+                   int32_t *sweeps, int32_t max_sweeps) {
+    const SymeigPlan plan = symeig_plan(n, dtype);
+    const int limit = max_sweeps <= 0 ? DZO_SYMEIG_DEFAULT_SWEEPS : max_sweeps;
+    DZO_DISPATCH(dtype, se_launch<T>(s, batch, plan, SymeigArgs<T>{(int)n, (int)plan.ld, limit, (const T *)matrices, (T *)work, (T *)eigenvalues,
+                                                                  (T *)eigenvectors, sweeps}));
+    DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
 

@@ -31,7 +31,8 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        pairwise_radial_energy_delta,
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
        BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!,
-       pairwise_batch_hvp!, pairwise_batch_hessian!, symmetric_batch_eigen!, symeig_plan, hessian_spectrum
+       pairwise_batch_hvp!, pairwise_batch_hessian!, symmetric_batch_eigen!, symeig_plan, hessian_spectrum,
+       ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -503,6 +504,151 @@ function hessian_spectrum(points::HipVector{T}, n_particles::Integer) where {T}
     sweeps = symmetric_batch_eigen!(eigenvalues, hessians, n)
     any(<(0), sweeps) && error("hessian_spectrum: no convergence in instances $(findall(<(0), sweeps))")
     return Float64.(reshape(Array(eigenvalues), n, batch))
+end
+
+################################################################################ batched eigenvector following
+# (not exercised in the build container either; the Python class ModeFollowing binds the same entry points and IS tested)
+#
+# Eigenvector following (Cerjan-Miller / Wales; include/dzo.h states the step) of `batch` clusters at once: per step the dense
+# Hessians, their eigenvalues and eigenvectors and the step kernel, with no host wait in between.  target_index 0 polishes
+# minima, 1 searches transition states.  `points` is aliased and moved.
+
+const MODEFOLLOW_ACTIVE, MODEFOLLOW_CONVERGED, MODEFOLLOW_FAILED = 0, 1, 2
+# `what` of read_array (DZO_MODEFOLLOW_* of include/dzo.h)
+const MODEFOLLOW_POINTS, MODEFOLLOW_GRADIENTS, MODEFOLLOW_ENERGIES, MODEFOLLOW_GRMS, MODEFOLLOW_STATUS, MODEFOLLOW_INDEX,
+      MODEFOLLOW_ZEROS, MODEFOLLOW_FOLLOWED_MODE, MODEFOLLOW_STEP_LENGTHS, MODEFOLLOW_ITERATION_COUNTS, MODEFOLLOW_EIGENVALUES,
+      MODEFOLLOW_EIGENVECTORS, MODEFOLLOW_SWEEPS, MODEFOLLOW_FOLLOW = 0:13
+
+mutable struct ModeFollowing{T}
+    handle::Ptr{Cvoid}
+    points::HipVector{T}
+    n_particles::Int
+    batch::Int
+end
+
+"""`ModeFollowing(lj_energy, points, n_particles; target_index=0, max_step=0.2, zero_tol=1e-4, grad_tol=1e-10)`."""
+function ModeFollowing(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer; target_index::Integer=0, max_step::Real=0.2,
+                       zero_tol::Real=1e-4, grad_tol::Real=1e-10) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_modefollow_batch_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, target_index, Float64(max_step), Float64(zero_tol),
+                Float64(grad_tol), h))
+    mf = ModeFollowing{T}(h[], points, n_particles, batch)
+    finalizer(mf) do w
+        w.handle != C_NULL && ccall((:dzo_modefollow_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return mf
+end
+
+"""The mode an instance without a followed vector starts on (0: the lowest non-zero mode)."""
+set_start_mode!(mf::ModeFollowing, mode::Integer) =
+    (check(ccall((:dzo_modefollow_batch_set_start_mode, libdzo), Cint, (Ptr{Cvoid}, Cint), mf.handle, mode)); mf)
+
+"""An initial followed vector per instance: `directions` holds 3N elements per instance; copied."""
+function set_directions!(mf::ModeFollowing{T}, directions::HipVector{T}) where {T}
+    check(ccall((:dzo_modefollow_batch_set_directions, libdzo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), mf.handle, directions.ptr))
+    synchronize()
+    return mf
+end
+
+"""`step!(mf, steps; wait=true)`: `steps` steps of every ACTIVE instance.  Returns whether no instance is ACTIVE any more
+(`wait=true`, blocking) or `nothing` (enqueued only)."""
+function step!(mf::ModeFollowing, steps::Integer=1; wait::Bool=true)
+    if !wait
+        check(ccall((:dzo_modefollow_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), mf.handle, steps, C_NULL))
+        return nothing
+    end
+    flag = Ref{Cint}(0)
+    check(ccall((:dzo_modefollow_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), mf.handle, steps, flag))
+    return flag[] != 0
+end
+
+function count_active(mf::ModeFollowing)
+    n = Ref{Int64}(0)
+    check(ccall((:dzo_modefollow_batch_count_active, libdzo), Cint, (Ptr{Cvoid}, Ref{Int64}), mf.handle, n))
+    return Int(n[])
+end
+
+"""`read_array(mf, what)`: a blocking host copy of one of the MODEFOLLOW_* arrays, in its own element type; vectors and
+eigenvector matrices come back with the instance as the last dimension."""
+function read_array(mf::ModeFollowing{T}, what::Integer) where {T}
+    n, b = 3 * mf.n_particles, mf.batch
+    r = what in (MODEFOLLOW_POINTS, MODEFOLLOW_GRADIENTS, MODEFOLLOW_EIGENVALUES, MODEFOLLOW_FOLLOW) ? Array{T}(undef, n, b) :
+        what == MODEFOLLOW_EIGENVECTORS ? Array{T}(undef, n, n, b) :
+        what == MODEFOLLOW_ENERGIES ? Vector{T}(undef, b) :
+        what in (MODEFOLLOW_GRMS, MODEFOLLOW_STEP_LENGTHS) ? Vector{Float64}(undef, b) :
+        what == MODEFOLLOW_ITERATION_COUNTS ? Vector{Int64}(undef, b) : Vector{Int32}(undef, b)
+    check(ccall((:dzo_modefollow_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), mf.handle, what, r))
+    return r
+end
+
+"""Device address of one of the MODEFOLLOW_* arrays (no wait)."""
+function array_pointer(mf::ModeFollowing, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_modefollow_batch_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), mf.handle, what, p))
+    return p[]
+end
+
+"""`modefollow_apply!(points, eigenvalues, eigenvectors, n_particles; ...)`: ONE step of every instance from modes the caller
+supplies (`dzo_modefollow_batch_apply`); `points` is moved.  `target_index=1` needs `follow` (3N per instance) and `follow_set`
+(a `HipVector{Float32}` of `batch` elements used as four bytes per instance: zero bits = not set).  Returns the status of every
+instance as a `Vector{Int32}`.  Blocks."""
+function modefollow_apply!(points::HipVector{T}, eigenvalues::HipVector{T}, eigenvectors::HipVector{T}, n_particles::Integer;
+                           target_index::Integer=0, start_mode::Integer=0, max_step::Real=0.2, zero_tol::Real=1e-4, grad_tol::Real=0.0,
+                           follow::Union{Nothing,HipVector{T}}=nothing, follow_set::Union{Nothing,HipVector{Float32}}=nothing) where {T}
+    batch = div(length(points), 3 * n_particles)
+    status = HipVector{Float32}(undef, batch)               # four bytes per instance: read back as Int32
+    check(ccall((:dzo_modefollow_batch_apply, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Cdouble,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, eigenvalues.ptr, eigenvectors.ptr,
+                follow === nothing ? C_NULL : follow.ptr, follow_set === nothing ? C_NULL : follow_set.ptr, target_index, start_mode,
+                Float64(max_step), Float64(zero_tol), Float64(grad_tol), C_NULL, C_NULL, C_NULL, C_NULL, status.ptr, C_NULL, C_NULL, C_NULL,
+                C_NULL))
+    return collect(reinterpret(Int32, Array(status)))
+end
+
+function run_steps!(mf::ModeFollowing, max_steps::Integer, steps_per_call::Integer=10)
+    taken = 0
+    done = count_active(mf) == 0
+    while !done && taken < max_steps
+        k = min(steps_per_call, max_steps - taken)
+        done = step!(mf, k)
+        taken += k
+    end
+    return mf
+end
+
+"""`polish_minima(lj_energy, points, n_particles; grad_tol=1e-10, max_steps=50, ...)`: target index 0 on the points a quench
+left, in place, until `grms <= grad_tol`; returns the `ModeFollowing`."""
+function polish_minima(f::typeof(lj_energy), points::HipVector{T}, n_particles::Integer; grad_tol::Real=1e-10, max_steps::Integer=50,
+                       max_step::Real=0.2, zero_tol::Real=1e-4) where {T}
+    return run_steps!(ModeFollowing(f, points, n_particles; target_index=0, max_step=max_step, zero_tol=zero_tol, grad_tol=grad_tol), max_steps)
+end
+
+"""`find_saddles(lj_energy, minima, n_particles; start_mode=0, kick=0.05, ...)`: polishes the minima, displaces each by `kick`
+along its `start_mode`-th non-zero eigenvector, sets that eigenvector as the followed vector and follows it uphill (target index
+1).  Returns `(saddles, polished)`, two `ModeFollowing`; `minima` ends holding the saddle searches' points."""
+function find_saddles(f::typeof(lj_energy), minima::HipVector{T}, n_particles::Integer; start_mode::Integer=0, kick::Real=0.05,
+                      grad_tol::Real=1e-10, max_steps::Integer=300, max_step::Real=0.1, zero_tol::Real=1e-4, polish_steps::Integer=50) where {T}
+    polished = polish_minima(f, minima, n_particles; grad_tol=grad_tol, max_steps=polish_steps, zero_tol=zero_tol)
+    lam, modes, x = read_array(polished, MODEFOLLOW_EIGENVALUES), read_array(polished, MODEFOLLOW_EIGENVECTORS), read_array(polished, MODEFOLLOW_POINTS)
+    dirs = zeros(T, size(x))
+    for b in 1:polished.batch
+        nonzero = findall(v -> abs(v) > zero_tol, lam[:, b])
+        length(nonzero) > start_mode && (dirs[:, b] = modes[:, nonzero[start_mode + 1], b])
+    end
+    kicked = HipVector(vec(x .+ T(kick) .* dirs))
+    check(ccall((:dzo_memcpy_d2d, libdzo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), minima.ptr, kicked.ptr, sizeof(T) * length(minima)))
+    saddles = ModeFollowing(f, minima, n_particles; target_index=1, max_step=max_step, zero_tol=zero_tol, grad_tol=grad_tol)
+    set_start_mode!(saddles, start_mode)
+    set_directions!(saddles, HipVector(vec(dirs)))
+    return run_steps!(saddles, max_steps), polished
 end
 
 """`quench(lj_energy, points, n_particles; ...)`: run the batched optimizer on `points` (in place) until every instance is

@@ -571,6 +571,108 @@ int32_t dzo_symmetric_batch_eigen(int64_t n, int64_t batch, int32_t dtype, const
 int32_t dzo_symeig_plan(int64_t n, int32_t dtype, int32_t *storage, int64_t *ld, int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched eigenvector following (Cerjan-Miller / Wales) over many small Lennard-Jones clusters: the consumer of the two blocks
+ * above.  Target index 0 is a Newton-quality minimiser: it polishes the points a quench leaves at is_stuck until the gradient
+ * is at rounding level and the six rigid-body eigenvalues are zeros worth the name.  Target index 1 is a transition-state
+ * search: every mode is stepped downhill but one followed mode, which is stepped uphill.  Nothing in the reference follows
+ * modes: this block is the specification.  One 256-thread block per instance; 3N <= DZO_SYMEIG_MAX_N, so n_particles <=
+ * DZO_MODEFOLLOW_MAX_PARTICLES = 128.
+ *
+ * Layout.  points, gradients, projections and follow vectors are (3N, batch): instance b at element 3N b, [x | y | z] -- the
+ * layout of every cluster unit.  eigenvalues (3N, batch) and eigenvectors (3N, 3N, batch) are what dzo_symmetric_batch_eigen
+ * writes.  Records are one value per instance: energies T; grms and step lengths fp64; status, index, zeros, followed mode,
+ * sweeps int32; iteration counts int64.
+ *
+ * The step, per instance (T = the element type, n = 3N; every operation in T with one rounding, no contraction, IEEE division
+ * and square root, unless fp64 is named).  Inputs: the point; lam[0..n) ascending and V (column i belongs to lam[i]), of the
+ * Hessian AT THIS POINT; the followed vector w and whether it is set; target_index in {0, 1}, start_mode >= 0, max_step > 0,
+ * zero_tol >= 0 (rounded once to T), grad_tol >= 0 (fp64).  An instance whose status is not ACTIVE is left alone.
+ *  1. Evaluate.  E and g at the point, with the bits of dzo_pairwise_batch_energy_gradient (its routines and launch shapes).
+ *  2. Gradient norm.  grms = sqrt((g.g)/n) in fp64: thread t = 0 .. 255 adds the squares of elements t, t + 256 by fused
+ *     multiply-add from +0; the 64 values of a wave are added by the xor tree with offsets 32, 16, 8, 4, 2, 1; the four wave
+ *     sums are added in wave order from +0 (the ORDER OF THE SUMS of this block; it depends on n only).
+ *  3. Classify.  Mode i is a zero mode when |lam[i]| <= zero_tol; index = #{lam[i] < -zero_tol}; zeros = # of zero modes.
+ *  4. Freeze check.  E, any g or any lam non-finite, or sweeps = -1 from the eigensolver: status FAILED.  Otherwise
+ *     grms <= grad_tol (fp64): status CONVERGED.  In both cases the point is not moved, followed mode = -1, step length = 0,
+ *     and the instance is frozen for all later steps with these records.
+ *  5. Project.  F[i] = V[:,i].g in fp64: lane l = 0 .. 63 of a wave adds rows l, l + 64, ... by fused multiply-add from +0, then
+ *     the xor tree; rounded once to T.
+ *  6. Followed mode (target_index = 1 only).  w not set: the start_mode-th non-zero mode in ascending order (start_mode = 0 is
+ *     the lowest); fewer non-zero modes than that: status FAILED, not moved.  w set: the non-zero mode with the largest
+ *     |V[:,i].w| (the fp64 dot of step 5); ties go to the lowest i.  Then w = V[:,i*] as stored, sign included, and w is set.
+ *  7. Mode steps.  a = |lam[i]|, q = (F[i] + F[i]) / a, h[i] = s * q / (1 + sqrt(1 + q*q)) with s = +1 for the followed mode
+ *     and -1 for every other non-zero mode; h[i] = 0 for zero modes.  This is 2F / (a (1 + sqrt(1 + 4F^2/a^2))), bounded by 1
+ *     in magnitude for any a.  An overflowing q*q gives h = 0 by itself.  (A q that itself overflows, 2|F| / a beyond the
+ *     range of T, gives a NaN step: the next step's freeze check reports FAILED.  zero_tol > 0 keeps a away from that.)
+ *  8. Cap.  hn = sqrt(sum h[i]^2) in fp64 in the order of the sums.  If hn > max_step (fp64), every h[i] is multiplied by
+ *     T(max_step / hn), the quotient in fp64.
+ *  9. Move.  x[r] = x[r] + d[r], d[r] = sum_i V[r,i] h[i] over i = 0 .. n-1 ascending from +0, one FUSED multiply-add per
+ *     term (zero modes included: their terms add +-0).
+ * 10. Record E, grms, index, zeros, the followed mode i* (-1 with target_index 0), the step length after the cap (max_step
+ *     when the cap scaled the step, hn otherwise), status ACTIVE, iteration count += 1.  E, g and grms are those of the point
+ *     BEFORE the move.
+ * No floating-point atomics; one writer per element.  An instance computes the same bits alone or anywhere in any batch, and
+ * a handle in one call of k steps or k calls of one.
+ *
+ * dzo_modefollow_batch_apply is the step, once, from modes the CALLER supplies (from anywhere: nothing in it depends on the
+ * eigensolver); it sets every status to ACTIVE first.  Record outputs other than status_dev may be NULL; follow_dev and
+ * follow_set_dev (int32, non-zero = set) may be NULL with target_index 0.  Blocking.
+ * A handle ALIASES points_dev and owns Hessians, eigenvalues, eigenvectors, sweeps, follow vectors and the eigensolver's
+ * workspace.  create leaves the energies and gradients of the points as given; the other records are zero until the first
+ * step.  step enqueues, per step, dzo_pairwise_batch_hessian's launch, dzo_symmetric_batch_eigen's (with eigenvectors, default
+ * sweeps) and the step kernel on the library's stream: no host wait between the three or between steps, one at the end for
+ * all_done when it is not NULL.  Frozen instances still pass through the first two launches (same point, same bits).
+ *
+ * Errors follow dzo_pairwise_batch_hessian / dzo_symmetric_batch_eigen: unknown radial or dtype, sizes < 1, steps < 0, null
+ * pointers, unknown `what`, target_index outside {0, 1}, start_mode < 0, max_step <= 0, a negative tolerance DZO_ERR_INVALID;
+ * n_particles > 128 DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required DZO_ERR_ASSERT.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_MODEFOLLOW_MAX_PARTICLES 128
+/* status */
+#define DZO_MODEFOLLOW_ACTIVE 0
+#define DZO_MODEFOLLOW_CONVERGED 1
+#define DZO_MODEFOLLOW_FAILED 2
+/* `what` of get_ptr / read (T = the handle's element type) */
+#define DZO_MODEFOLLOW_POINTS 0            /* T, 3N batch: the caller's array */
+#define DZO_MODEFOLLOW_GRADIENTS 1         /* T, 3N batch: at the point before the last move */
+#define DZO_MODEFOLLOW_ENERGIES 2          /* T, batch: likewise */
+#define DZO_MODEFOLLOW_GRMS 3              /* fp64, batch */
+#define DZO_MODEFOLLOW_STATUS 4            /* int32, batch */
+#define DZO_MODEFOLLOW_INDEX 5             /* int32, batch: eigenvalues below -zero_tol */
+#define DZO_MODEFOLLOW_ZEROS 6             /* int32, batch: eigenvalues within zero_tol of 0 */
+#define DZO_MODEFOLLOW_FOLLOWED_MODE 7     /* int32, batch: i* of the last step, -1 when none */
+#define DZO_MODEFOLLOW_STEP_LENGTHS 8      /* fp64, batch: of the last step, after the cap */
+#define DZO_MODEFOLLOW_ITERATION_COUNTS 9  /* int64, batch: moves made */
+#define DZO_MODEFOLLOW_EIGENVALUES 10      /* T, 3N batch: of the last step's Hessian */
+#define DZO_MODEFOLLOW_EIGENVECTORS 11     /* T, (3N, 3N, batch) */
+#define DZO_MODEFOLLOW_SWEEPS 12           /* int32, batch: the eigensolver's */
+#define DZO_MODEFOLLOW_FOLLOW 13           /* T, 3N batch: the followed vectors w */
+typedef struct dzo_modefollow_batch_s *dzo_modefollow_batch_t;
+/* the step above, once, on every instance, from the caller's modes; points_dev is moved, follow_dev / follow_set_dev updated */
+int32_t dzo_modefollow_batch_apply(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                                   const void *eigenvalues_dev, const void *eigenvectors_dev, void *follow_dev,
+                                   int32_t *follow_set_dev, int32_t target_index, int32_t start_mode, double max_step,
+                                   double zero_tol, double grad_tol, void *energies_dev, void *gradients_dev,
+                                   void *projections_dev, double *grms_dev, int32_t *status_dev, int32_t *index_dev,
+                                   int32_t *zeros_dev, int32_t *followed_dev, double *step_lengths_dev);
+/* points_dev: (3N, batch), ALIASED.  start_mode 0, no followed vector set.  Blocking. */
+int32_t dzo_modefollow_batch_create(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                                    int32_t target_index, double max_step, double zero_tol, double grad_tol,
+                                    dzo_modefollow_batch_t *out);
+int32_t dzo_modefollow_batch_destroy(dzo_modefollow_batch_t h);
+/* the mode an instance without a followed vector starts on (step 6) */
+int32_t dzo_modefollow_batch_set_start_mode(dzo_modefollow_batch_t h, int32_t mode);
+/* an initial followed vector w per instance: dirs_dev (3N, batch) is copied and every instance's w is set.  No wait. */
+int32_t dzo_modefollow_batch_set_directions(dzo_modefollow_batch_t h, const void *dirs_dev);
+/* `steps` steps of every ACTIVE instance; all_done may be NULL (then no host wait) */
+int32_t dzo_modefollow_batch_step(dzo_modefollow_batch_t h, int32_t steps, int32_t *all_done);
+/* instances with status ACTIVE.  Blocking. */
+int32_t dzo_modefollow_batch_count_active(dzo_modefollow_batch_t h, int64_t *active);
+/* device address of an array above (no wait) / a blocking copy of it to host memory, in the array's own element type */
+int32_t dzo_modefollow_batch_get_ptr(dzo_modefollow_batch_t h, int32_t what, void **ptr_dev);
+int32_t dzo_modefollow_batch_read(dzo_modefollow_batch_t h, int32_t what, void *out_host);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
