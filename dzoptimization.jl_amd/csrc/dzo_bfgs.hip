@@ -899,12 +899,8 @@ static int32_t bfgs_quadratic_search(dzo_bfgs_s *o, const void *dir, double f0, 
     double xb = 0, fb = f0;                                      // :196
     if (f1 < fb) { xb = x1; fb = f1; }                           // :197-199
     if (f2 < fb) { xb = x2; fb = f2; }                           // :200-202
-    const double d1 = round_to_dtype(dt, f0 - f1), d2 = round_to_dtype(dt, f2 - f1);
-    const double sum = round_to_dtype(dt, d1 + d2);              // :203-205
-    if (d1 >= 0 && d2 >= 0 && sum > 0) {                         // :206
-        const double num = round_to_dtype(dt, round_to_dtype(dt, d1 + d1) + sum);
-        const double ratio = round_to_dtype(dt, num / round_to_dtype(dt, sum + sum));   // :207-208
-        const double xq = round_to_dtype(dt, ratio * x1);        // :209
+    double xq;
+    if (phi_quadratic_request(dt, f0, x1, f1, x2, f2, &xq)) {    // :203-209
         double fq;
         DZO_TRY(bfgs_phi(o, dir, xq, &fq));                      // :210
         if (fq < fb) { xb = xq; fb = fq; }                       // :211-213
@@ -916,124 +912,48 @@ static int32_t bfgs_quadratic_search(dzo_bfgs_s *o, const void *dir, double f0, 
 // ---------------------------------------------------------------------------------------------
 // The two line searches of a dense BFGS step (gradient direction :922-925, quasi-Newton direction
 // :929-932) are independent, so they are advanced side by side: each round evaluates the next
-// point of BOTH in one pass over A (quadratic_phi2_kernel) with one host sync.  PhiSearch is
-// bfgs_bracket + bfgs_quadratic_search turned into a resumable state machine: same decisions,
-// same values, same evaluation counts -- only the order in which the two searches' evaluations
-// reach the device changes.
+// points of BOTH in one pass over A (quadratic_phi6_kernel).  Each search is a PhiMachine
+// (dzo_phi_search.h: bfgs_bracket + bfgs_quadratic_search as a resumable state machine whose trial
+// points and gradients are indices); two drivers run the same machines:
+//   bfgs_dual_search   the machines on the HOST: one launch and one wait per round
+//   bfgs_dev_search    the machines on the DEVICE, advanced by each round's finish kernel: one wait per step
+// Both turn indices into buffers by the same tables (PhiBuffers) and end by the same rule (bfgs_search_result).
 // ---------------------------------------------------------------------------------------------
-struct PhiSearch {
-    const void *dir = nullptr;
-    void *scratch = nullptr, *ref_point = nullptr;
-    double f0 = 0, t0 = 0;
-    enum { FIRST, DOUBLING, SHRINKING, QUADRATIC, DONE, SEQUENTIAL } state = DONE;
-    double step = 0, fa = 0, req_t = 0, x1 = 0, f1 = 0, x2 = 0, f2 = 0, xb = 0, fb = 0;
-    int32_t increases = 0;
-    bool want = false, req_ref = false;
-    double t_best = 0, f_best = 0;
-    void *cur_point = nullptr;     // buffer holding the trial point of the last consumed evaluation
-    void *spec[2] = {nullptr, nullptr};
-    // gradient (A*x_t, a by-product of the evaluation) and round of: the last consumed evaluation, the
-    // point `step`, the bracket ends, the best point so far
-    const void *cur_grad = nullptr, *step_grad = nullptr, *g1 = nullptr, *g2 = nullptr, *best_grad = nullptr;
-    int cur_round = 0, step_round = 0, r1 = 0, r2 = 0, best_round = 0;
+static_assert(kPhiF32 == DZO_F32, "dzo_phi_search.h restates the dtype code");
+
+struct PhiBuffers {
+    void *pts[2][3];                               // [side][request slot]: the buffer that slot's trial point is written to
+    void *ref[2];                                  // [side]: the host-driven search's copy of its reference point (:136 / :155)
+    size_t vbytes;                                 // one entry of the gradient pool
 };
-
-static void phi_search_to_quadratic(dzo_bfgs_s *o, PhiSearch &q) {      // bfgs_quadratic_search after :195
-    const int32_t dt = o->dtype;
-    q.xb = 0; q.fb = q.f0; q.best_grad = nullptr;                // :196
-    if (q.f1 < q.fb) { q.xb = q.x1; q.fb = q.f1; q.best_grad = q.g1; q.best_round = q.r1; }   // :197-199
-    if (q.f2 < q.fb) { q.xb = q.x2; q.fb = q.f2; q.best_grad = q.g2; q.best_round = q.r2; }   // :200-202
-    const double d1 = round_to_dtype(dt, q.f0 - q.f1), d2 = round_to_dtype(dt, q.f2 - q.f1);
-    const double sum = round_to_dtype(dt, d1 + d2);              // :203-205
-    if (d1 >= 0 && d2 >= 0 && sum > 0) {                         // :206
-        const double num = round_to_dtype(dt, round_to_dtype(dt, d1 + d1) + sum);
-        const double ratio = round_to_dtype(dt, num / round_to_dtype(dt, sum + sum));   // :207-208
-        q.req_t = round_to_dtype(dt, ratio * q.x1);              // :209
-        q.want = true; q.req_ref = false;
-        q.state = PhiSearch::QUADRATIC;
-    } else {
-        q.t_best = q.xb; q.f_best = q.fb;
-        q.want = false;
-        q.state = PhiSearch::DONE;
-    }
+static PhiBuffers phi_buffers(const dzo_bfgs_s *o) {
+    return {{{o->scratch, o->spec_buf[0], o->spec_buf[1]}, {o->scratch2, o->spec_buf[2], o->spec_buf[3]}},
+            {o->ref_point, o->ref_point2}, (size_t)((o->n + 63) / 64 * 64) * dtype_size(o->dtype)};
 }
-
-static void phi_search_bracket_done(dzo_bfgs_s *o, PhiSearch &q, double x1, double f1, double x2, double f2,
-                                    const void *g1 = nullptr, int r1 = 0, const void *g2 = nullptr, int r2 = 0) {
-    q.x1 = x1; q.f1 = f1; q.x2 = x2; q.f2 = f2; q.g1 = g1; q.r1 = r1; q.g2 = g2; q.r2 = r2;
-    phi_search_to_quadratic(o, q);
-}
-
-static void phi_search_begin(dzo_bfgs_s *o, PhiSearch &q, const void *dir, double f0, double t0, void *scratch, void *ref_point) {
-    q = PhiSearch();
-    q.dir = dir; q.f0 = f0; q.t0 = t0; q.scratch = scratch; q.ref_point = ref_point; q.cur_point = scratch;
-    if (!finite_t(f0) || !(t0 > 0) || !finite_t(t0)) {           // :64-66 -> bracket (0, f0, 0, f0)
-        phi_search_bracket_done(o, q, 0, f0, 0, f0);
-        return;
-    }
-    q.state = PhiSearch::FIRST;
-    q.step = t0;
-    q.req_t = t0; q.want = true; q.req_ref = false;
-}
-
-// feed the result of the pending request; may enqueue a device copy (the :136 / :155 reference point)
-static int32_t phi_search_feed(dzo_bfgs_s *o, PhiSearch &q, double f, bool changed, bool nonzero, bool equal_ref) {
-    const int32_t dt = o->dtype;
-    const size_t bytes = (size_t)o->n * dtype_size(dt);
-    q.want = false;
-    switch (q.state) {
-    case PhiSearch::FIRST:
-        if (!nonzero) { phi_search_bracket_done(o, q, 0, q.f0, 0, q.f0); return DZO_OK; }   // :83-85 (the speculative value is dropped)
-        if (!changed) { q.state = PhiSearch::SEQUENTIAL; return DZO_OK; }                  // :91-101 tiny-step path: rare, done sequentially
-        o->evals += 1;
-        q.fa = f;                                                // :104
-        q.step_grad = q.cur_grad; q.step_round = q.cur_round;
-        if (q.fa <= q.f0) {                                      // :130
-            q.increases = 0;
-            DZO_HIP(hipMemcpyAsync(q.ref_point, q.cur_point, bytes, hipMemcpyDeviceToDevice, o->stream));   // :136
-            q.state = PhiSearch::DOUBLING;
-            q.req_t = round_to_dtype(dt, q.step + q.step); q.increases += 1;
-            q.want = true; q.req_ref = true;
-        } else {
-            q.state = PhiSearch::SHRINKING;
-            q.req_t = round_to_dtype(dt, 0.5 * q.step);
-            q.want = true; q.req_ref = false;
+// where the six requests of `round` write: slot e of a side its trial point to pts[side][e], its gradient (A*x_t, a
+// by-product of the evaluation) to the pool entry of (round, side, e)
+static void phi_round_outputs(const dzo_bfgs_s *o, const PhiBuffers &B, int round, PhiDirHost req[2]) {
+    for (int r = 0; r < 2; ++r)
+        for (int e = 0; e < 3; ++e) {
+            req[r].point_out[e] = B.pts[r][e];
+            req[r].grad_out[e] = (char *)o->grad_pool + (size_t)phi_pool_index(round, r, e) * B.vbytes;
         }
-        return DZO_OK;
-    case PhiSearch::DOUBLING: {                                  // :143-156
-        o->evals += 1;
-        const double dbl = q.req_t, fb = f;
-        bool stop = (o->max_increases > 0 && q.increases >= o->max_increases) || !finite_t(fb) || fb > q.fa;
-        if (!stop) stop = equal_ref;                             // :150
-        if (stop) { phi_search_bracket_done(o, q, q.step, q.fa, dbl, fb, q.step_grad, q.step_round, q.cur_grad, q.cur_round); return DZO_OK; }   // :151
-        q.step = dbl; q.fa = fb; q.step_grad = q.cur_grad; q.step_round = q.cur_round;
-        DZO_HIP(hipMemcpyAsync(q.ref_point, q.cur_point, bytes, hipMemcpyDeviceToDevice, o->stream));       // :155
-        q.req_t = round_to_dtype(dt, q.step + q.step); q.increases += 1;
-        q.want = true; q.req_ref = true;
-        return DZO_OK;
-    }
-    case PhiSearch::SHRINKING: {                                 // :157-171
-        o->evals += 1;
-        const double hs = q.req_t, fb = f;
-        if (fb <= q.f0) { phi_search_bracket_done(o, q, hs, fb, q.step, q.fa, q.cur_grad, q.cur_round, q.step_grad, q.step_round); return DZO_OK; }   // :166
-        if (hs == 0.0) { phi_search_bracket_done(o, q, 0, q.f0, 0, q.f0); return DZO_OK; }
-        q.step = hs; q.fa = fb; q.step_grad = q.cur_grad; q.step_round = q.cur_round;
-        q.req_t = round_to_dtype(dt, 0.5 * q.step);
-        q.want = true; q.req_ref = false;
-        return DZO_OK;
-    }
-    case PhiSearch::QUADRATIC:                                   // :210-213
-        o->evals += 1;
-        if (f < q.fb) { q.xb = q.req_t; q.fb = f; q.best_grad = q.cur_grad; q.best_round = q.cur_round; }
-        q.t_best = q.xb; q.f_best = q.fb;
-        q.state = PhiSearch::DONE;
-        return DZO_OK;
-    default:
-        return DZO_OK;
-    }
 }
 
-// both searches of a step; false in *done when the objective has no two-request kernel (nothing was evaluated)
+// a search that stopped asking, after `round` rounds: its step size and value, and into o->best_grad[side] the gradient at
+// the best point if phi_result still vouches for its pool entry.  The rare tiny-step path (:91-101) is finished with the
+// sequential code.
+static int32_t bfgs_search_result(dzo_bfgs_s *o, const PhiBuffers &B, const PhiMachine &q, int round, int side, const void *dir,
+                                  double *t, double *f) {
+    if (q.state == kPhiSequential) return bfgs_quadratic_search(o, dir, o->f, q.t0, t, f);
+    int grad_index;
+    phi_result(q, round, t, f, &grad_index);
+    if (grad_index >= 0) o->best_grad[side] = (char *)o->grad_pool + (size_t)grad_index * B.vbytes;
+    return DZO_OK;
+}
+
+// both searches of a step, driven from the host; false in *done when the objective has no two-direction kernel (nothing
+// was evaluated)
 static int32_t bfgs_dual_search(dzo_bfgs_s *o, const void *dir_a, double t0_a, const void *dir_b, double t0_b,
                                 double *t_a, double *f_a, double *t_b, double *f_b, bool *done) {
     const bool enabled = getenv("DZO_TUNE_BFGS_DUAL_SEARCH") ? atoi(getenv("DZO_TUNE_BFGS_DUAL_SEARCH")) != 0 : true;
@@ -1041,42 +961,25 @@ static int32_t bfgs_dual_search(dzo_bfgs_s *o, const void *dir_a, double t0_a, c
     if (!enabled || o->objective || o->constraint || !o->problem || o->problem->kind != DZO_PROBLEM_QUADRATIC ||
         o->problem->l2 != 0.0 || o->problem->cons_on)
         return DZO_OK;
-    PhiSearch q[2];
-    phi_search_begin(o, q[0], dir_a, o->f, t0_a, o->scratch, o->ref_point);
-    phi_search_begin(o, q[1], dir_b, o->f, t0_b, o->scratch2, o->ref_point2);
-    for (int r = 0; r < 2; ++r) { q[r].spec[0] = o->spec_buf[2 * r]; q[r].spec[1] = o->spec_buf[2 * r + 1]; }
     const int32_t dt = o->dtype;
-    const size_t vbytes = (size_t)((o->n + 63) / 64 * 64) * dtype_size(dt);
+    const PhiBuffers B = phi_buffers(o);
+    const void *dirs[2] = {dir_a, dir_b};
+    const double t0[2] = {t0_a, t0_b};
+    PhiMachine q[2];
+    PhiReqDev R;
+    for (int r = 0; r < 2; ++r) phi_begin(dt, q[r], o->f, t0[r]);
     int round = 0;
     o->best_grad[0] = o->best_grad[1] = nullptr;
     while (q[0].want || q[1].want) {
         round += 1;
-        // Per search: the evaluation it needs now (slot 0) plus the one or two it will most likely
-        // need next (slots 1, 2) -- the first doubling and the first halving after the first point,
-        // the next doubling / halving inside those loops.  All of them ride on the same pass over A;
-        // a speculative value is used only if the state machine then asks for exactly that point.
+        for (int r = 0; r < 2; ++r) phi_post(dt, o->sign, q[r], R, r);
         PhiDirHost req[2];
-        double spec_t[2][3];
-        bool spec_ref[2][3];
+        phi_round_outputs(o, B, round, req);
         for (int r = 0; r < 2; ++r) {
-            PhiSearch &sm = q[r];
-            req[r].dir = sm.dir;
-            for (int e = 0; e < 3; ++e) { spec_t[r][e] = 0; spec_ref[r][e] = false; }
-            if (!sm.want) { req[r].dir = q[1 - r].dir; continue; }
-            auto post = [&](int slot, double t, void *out, const void *ref, int ref_req, bool is_ref) {
-                req[r].ts[slot] = round_to_dtype(dt, o->sign * t);
-                req[r].point_out[slot] = out; req[r].ref[slot] = ref; req[r].ref_req[slot] = ref_req; req[r].active[slot] = true;
-                req[r].grad_out[slot] = (char *)o->grad_pool + (size_t)((round % 4) * 6 + r * 3 + slot) * vbytes;
-                spec_t[r][slot] = t; spec_ref[r][slot] = is_ref;
-            };
-            post(0, sm.req_t, sm.scratch, sm.req_ref ? sm.ref_point : nullptr, -1, sm.req_ref);
-            if (sm.state == PhiSearch::FIRST) {
-                post(1, round_to_dtype(dt, sm.req_t + sm.req_t), sm.spec[0], nullptr, 0, true);      // first doubling (:143), :150 against slot 0
-                post(2, round_to_dtype(dt, 0.5 * sm.req_t), sm.spec[1], nullptr, -1, false);         // first halving (:158)
-            } else if (sm.state == PhiSearch::DOUBLING) {
-                post(1, round_to_dtype(dt, sm.req_t + sm.req_t), sm.spec[0], nullptr, 0, true);
-            } else if (sm.state == PhiSearch::SHRINKING) {
-                post(1, round_to_dtype(dt, 0.5 * sm.req_t), sm.spec[0], nullptr, -1, false);
+            req[r].dir = q[r].want ? dirs[r] : dirs[1 - r];      // (an idle side reads the busy one's vector again)
+            for (int e = 0; e < 3; ++e) {
+                req[r].ts[e] = R.ts[r][e]; req[r].active[e] = R.active[r][e] != 0; req[r].ref_req[e] = R.ref_req[r][e];
+                req[r].ref[e] = R.use_ref[r][e] ? B.ref[r] : nullptr;
             }
         }
         o->ticket += 1.0;
@@ -1086,197 +989,45 @@ static int32_t bfgs_dual_search(dzo_bfgs_s *o, const void *dir_a, double t0_a, c
         DZO_TRY(wait_sealed(o->stream, o->host, 17, o->host + 17, o->ticket));
         const int32_t *hf = reinterpret_cast<const int32_t *>(o->host + 8);
         for (int r = 0; r < 2; ++r) {
-            PhiSearch &sm = q[r];
-            if (!req[r].active[0]) continue;
-            bool used[3] = {false, false, false};
-            int slot = 0;                                     // the primary request first, then matching speculative ones
-            for (;;) {
-                used[slot] = true;
-                sm.cur_point = req[r].point_out[slot];
-                sm.cur_grad = req[r].grad_out[slot]; sm.cur_round = round;
-                const int fq = (r * 3 + slot) * 3;
-                DZO_TRY(phi_search_feed(o, sm, round_to_dtype(dt, o->host[r * 3 + slot]), hf[fq] != 0, hf[fq + 1] != 0, hf[fq + 2] == 0));
-                if (!sm.want) break;
-                int next = -1;
-                for (int e = 1; e < 3; ++e)
-                    if (req[r].active[e] && !used[e] && spec_t[r][e] == sm.req_t && spec_ref[r][e] == sm.req_ref) next = e;
-                if (next < 0) break;
-                slot = next;
-            }
+            phi_consume(dt, o->max_increases, q[r], round_to_dtype(dt, o->host[r * 3 + 0]), round_to_dtype(dt, o->host[r * 3 + 1]),
+                        round_to_dtype(dt, o->host[r * 3 + 2]), hf + r * 9, phi_pool_index(round, r, 0), round, o->evals);
+            // A machine that goes on doubling took a new reference point in this round (:136 / :155): the trial point it
+            // consumed last, which the next launch overwrites -- this driver keeps a copy to compare with.  One copy a
+            // round: when two doublings were consumed, the first one's reference was never compared with anything.
+            if (q[r].state == kPhiDoubling)
+                DZO_HIP(hipMemcpyAsync(B.ref[r], B.pts[r][q[r].ref_buf], (size_t)o->n * dtype_size(dt), hipMemcpyDeviceToDevice, o->stream));
         }
     }
-    // the rare tiny-step path (:91-101) is finished with the sequential code
-    double tt[2], ff[2];
-    for (int r = 0; r < 2; ++r) {
-        if (q[r].state == PhiSearch::SEQUENTIAL) DZO_TRY(bfgs_quadratic_search(o, q[r].dir, o->f, q[r].t0, &tt[r], &ff[r]));
-        else { tt[r] = q[r].t_best; ff[r] = q[r].f_best; }
-    }
-    for (int r = 0; r < 2; ++r)        // gradient at the best point, if its pool entry has not been recycled since
-        if (q[r].state == PhiSearch::DONE && q[r].t_best != 0.0 && q[r].best_grad && round - q[r].best_round < 4)
-            o->best_grad[r] = q[r].best_grad;
-    *t_a = tt[0]; *f_a = ff[0]; *t_b = tt[1]; *f_b = ff[1];
+    DZO_TRY(bfgs_search_result(o, B, q[0], round, 0, dir_a, t_a, f_a));
+    DZO_TRY(bfgs_search_result(o, B, q[1], round, 1, dir_b, t_b, f_b));
     *done = true;
     return DZO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same two searches with the state machines ON THE DEVICE.  A host-driven round costs a round trip
-// (kernel -> pinned word -> host decision -> next launch reaches the GPU: 20-25 us against 36 us of
-// kernels per round at config 2), and a step has three of them: norms -> first round -> second round ->
-// accepted step.  Here the norm kernel's last thread begins both searches and posts the first round's
-// requests in device memory (PhiReqDev), every round's finish kernel feeds the six values to the two
-// machines and posts the next round's requests, and the host enqueues norm + rounds back to back and
-// waits ONCE, for the last enqueued round's summary; a round behind two finished searches does nothing.
-// PhiDev is PhiSearch with buffers as indices: a trial point is its request slot (0: scratch, 1, 2: the
-// two speculative buffers), a gradient its grad_pool entry.  Same arithmetic (doubles rounded to the
-// dtype where the host code rounds), same decisions, same evaluation counts: tested bit for bit against
-// the host-driven search.
+// The same two machines ON THE DEVICE.  A host-driven round costs a round trip (kernel -> pinned word ->
+// host decision -> next launch reaches the GPU: 20-25 us against 36 us of kernels per round at config 2),
+// and a step has three of them: norms -> first round -> second round -> accepted step.  Here the norm
+// kernel's last thread begins both searches and posts the first round's requests in device memory
+// (PhiReqDev), every round's finish kernel feeds the six values to the two machines and posts the next
+// round's requests, and the host enqueues norm + rounds back to back and waits ONCE, for the last enqueued
+// round's summary; a round behind two finished searches does nothing.  Tested bit for bit against the
+// host-driven search.
 // ---------------------------------------------------------------------------------------------
-struct PhiDev {
-    double f0, t0, step, fa, req_t, x1, f1, x2, f2, xb, fb, t_best, f_best;
-    double spec_t[3];
-    int32_t state, increases, want, req_ref;
-    int32_t spec_ref[3], active[3];
-    int32_t step_grad, g1, g2, best_grad;          // grad_pool entries (-1: none)
-    int32_t step_round, r1, r2, best_round;
-    int32_t ref_buf;                               // the trial-point buffer (= request slot) that holds the reference point (:136 / :155)
-};
 struct BfgsSearchDev {
-    PhiDev q[2];
+    PhiMachine q[2];
     PhiReqDev req;
     double norm[2];
     int64_t evals;
 };
-enum { kPhiFirst = 0, kPhiDoubling, kPhiShrinking, kPhiQuadratic, kPhiDone, kPhiSequential };
 constexpr int kSumBase = 24;                       // summary of the searches in the pinned host doubles, from here
 constexpr int kHostDoubles = 64;
-
-__device__ __forceinline__ double dev_rt(int32_t dt, double v) { return dt == DZO_F32 ? (double)(float)v : v; }   // round_to_dtype
-
-__device__ __forceinline__ void phi_dev_to_quadratic(int32_t dt, PhiDev &q) {                     // phi_search_to_quadratic
-    q.xb = 0; q.fb = q.f0; q.best_grad = -1; q.best_round = 0;
-    if (q.f1 < q.fb) { q.xb = q.x1; q.fb = q.f1; q.best_grad = q.g1; q.best_round = q.r1; }
-    if (q.f2 < q.fb) { q.xb = q.x2; q.fb = q.f2; q.best_grad = q.g2; q.best_round = q.r2; }
-    const double d1 = dev_rt(dt, q.f0 - q.f1), d2 = dev_rt(dt, q.f2 - q.f1);
-    const double sum = dev_rt(dt, d1 + d2);
-    if (d1 >= 0 && d2 >= 0 && sum > 0) {
-        const double num = dev_rt(dt, dev_rt(dt, d1 + d1) + sum);
-        const double ratio = dev_rt(dt, num / dev_rt(dt, sum + sum));
-        q.req_t = dev_rt(dt, ratio * q.x1);
-        q.want = 1; q.req_ref = 0;
-        q.state = kPhiQuadratic;
-    } else {
-        q.t_best = q.xb; q.f_best = q.fb;
-        q.want = 0;
-        q.state = kPhiDone;
-    }
-}
-
-__device__ __forceinline__ void phi_dev_bracket_done(int32_t dt, PhiDev &q, double x1, double f1, double x2, double f2, int g1 = -1, int r1 = 0,
-                                            int g2 = -1, int r2 = 0) {
-    q.x1 = x1; q.f1 = f1; q.x2 = x2; q.f2 = f2; q.g1 = g1; q.r1 = r1; q.g2 = g2; q.r2 = r2;
-    phi_dev_to_quadratic(dt, q);
-}
-
-__device__ __forceinline__ void phi_dev_begin(int32_t dt, PhiDev &q, double f0, double t0) {      // phi_search_begin
-    q.f0 = f0; q.t0 = t0;
-    q.step = q.fa = q.req_t = q.x1 = q.f1 = q.x2 = q.f2 = q.xb = q.fb = q.t_best = q.f_best = 0;
-    q.increases = 0; q.want = 0; q.req_ref = 0;
-    q.step_grad = q.g1 = q.g2 = q.best_grad = -1;
-    q.step_round = q.r1 = q.r2 = q.best_round = 0;
-    q.ref_buf = 0;
-    q.state = kPhiDone;
-    for (int e = 0; e < 3; ++e) { q.spec_t[e] = 0; q.spec_ref[e] = 0; q.active[e] = 0; }
-    if (!isfinite(f0) || !(t0 > 0) || !isfinite(t0)) { phi_dev_bracket_done(dt, q, 0, f0, 0, f0); return; }
-    q.state = kPhiFirst;
-    q.step = t0;
-    q.req_t = t0; q.want = 1; q.req_ref = 0;
-}
-
-// phi_search_feed; slot: where the consumed evaluation's trial point lies, cur_grad / cur_round: its gradient
-__device__ __forceinline__ void phi_dev_feed(int32_t dt, int32_t max_increases, PhiDev &q, double f, bool changed, bool nonzero, bool equal_ref,
-                                    int slot, int cur_grad, int cur_round, int64_t &evals) {
-    q.want = 0;
-    switch (q.state) {
-    case kPhiFirst:
-        if (!nonzero) { phi_dev_bracket_done(dt, q, 0, q.f0, 0, q.f0); return; }
-        if (!changed) { q.state = kPhiSequential; return; }
-        evals += 1;
-        q.fa = f;
-        q.step_grad = cur_grad; q.step_round = cur_round;
-        if (q.fa <= q.f0) {
-            q.increases = 0;
-            q.ref_buf = slot;
-            q.state = kPhiDoubling;
-            q.req_t = dev_rt(dt, q.step + q.step); q.increases += 1;
-            q.want = 1; q.req_ref = 1;
-        } else {
-            q.state = kPhiShrinking;
-            q.req_t = dev_rt(dt, 0.5 * q.step);
-            q.want = 1; q.req_ref = 0;
-        }
-        return;
-    case kPhiDoubling: {
-        evals += 1;
-        const double dbl = q.req_t, fb = f;
-        bool stop = (max_increases > 0 && q.increases >= max_increases) || !isfinite(fb) || fb > q.fa;
-        if (!stop) stop = equal_ref;
-        if (stop) { phi_dev_bracket_done(dt, q, q.step, q.fa, dbl, fb, q.step_grad, q.step_round, cur_grad, cur_round); return; }
-        q.step = dbl; q.fa = fb; q.step_grad = cur_grad; q.step_round = cur_round;
-        q.ref_buf = slot;
-        q.req_t = dev_rt(dt, q.step + q.step); q.increases += 1;
-        q.want = 1; q.req_ref = 1;
-        return;
-    }
-    case kPhiShrinking: {
-        evals += 1;
-        const double hs = q.req_t, fb = f;
-        if (fb <= q.f0) { phi_dev_bracket_done(dt, q, hs, fb, q.step, q.fa, cur_grad, cur_round, q.step_grad, q.step_round); return; }
-        if (hs == 0.0) { phi_dev_bracket_done(dt, q, 0, q.f0, 0, q.f0); return; }
-        q.step = hs; q.fa = fb; q.step_grad = cur_grad; q.step_round = cur_round;
-        q.req_t = dev_rt(dt, 0.5 * q.step);
-        q.want = 1; q.req_ref = 0;
-        return;
-    }
-    case kPhiQuadratic:
-        evals += 1;
-        if (f < q.fb) { q.xb = q.req_t; q.fb = f; q.best_grad = cur_grad; q.best_round = cur_round; }
-        q.t_best = q.xb; q.f_best = q.fb;
-        q.state = kPhiDone;
-        return;
-    default:
-        return;
-    }
-}
-
-// the requests of the next launch (the loop body of bfgs_dual_search that fills req[])
-__device__ __forceinline__ void phi_dev_post(int32_t dt, double sign, PhiDev &q, PhiReqDev &R, int side) {
-    for (int e = 0; e < 3; ++e) {
-        q.spec_t[e] = 0; q.spec_ref[e] = 0; q.active[e] = 0;
-        R.ts[side][e] = 0; R.active[side][e] = 0; R.ref_req[side][e] = -1; R.use_ref[side][e] = 0;
-    }
-    if (!q.want) return;
-    auto post = [&](int slot, double t, int use_ref, int ref_req, int is_ref) {
-        R.ts[side][slot] = dev_rt(dt, sign * t);
-        R.active[side][slot] = 1; R.use_ref[side][slot] = use_ref; R.ref_req[side][slot] = ref_req;
-        q.spec_t[slot] = t; q.spec_ref[slot] = is_ref; q.active[slot] = 1;
-    };
-    post(0, q.req_t, q.req_ref ? 1 + q.ref_buf : 0, -1, q.req_ref);
-    if (q.state == kPhiFirst) {
-        post(1, dev_rt(dt, q.req_t + q.req_t), 0, 0, 1);
-        post(2, dev_rt(dt, 0.5 * q.req_t), 0, -1, 0);
-    } else if (q.state == kPhiDoubling) {
-        post(1, dev_rt(dt, q.req_t + q.req_t), 0, 0, 1);
-    } else if (q.state == kPhiShrinking) {
-        post(1, dev_rt(dt, 0.5 * q.req_t), 0, -1, 0);
-    }
-}
 
 // what the host needs after its one wait: 5 doubles per search + the evaluation count
 //   [0] want | state << 8 | (best_grad + 1) << 16 | best_round << 32 (as an integer-valued double: < 2^53)
 //   [1] t_best  [2] f_best  [3] t0  [4] the direction's norm
 constexpr int kSumStride = 5;
-__device__ __forceinline__ unsigned long long phi_dev_summary(const PhiDev &q, double norm, double *o) {      // returns its share of the seal
+__device__ __forceinline__ unsigned long long phi_dev_summary(const PhiMachine &q, double norm, double *o) {      // returns its share of the seal
     const int64_t packed = (int64_t)q.want | ((int64_t)q.state << 8) | ((int64_t)(q.best_grad + 1) << 16) | ((int64_t)q.best_round << 32);
     const double v[kSumStride] = {(double)packed, q.t_best, q.f_best, q.t0, norm};
     unsigned long long seal = 0;
@@ -1336,10 +1087,10 @@ __global__ __launch_bounds__(kBlock) void norm2_pair_begin_kernel(int64_t n, con
     if (threadIdx.x == 0) {
         const double na = dt == DZO_F32 ? (double)sqrtf((float)ra) : sqrt(ra);
         const double nb = dt == DZO_F32 ? (double)sqrtf((float)rb) : sqrt(rb);
-        phi_dev_begin(dt, L.q[0], f0, dev_rt(dt, step_length / na));      // (in LDS: private copies of the structures end up in scratch memory)
-        phi_dev_begin(dt, L.q[1], f0, dev_rt(dt, step_length / nb));
-        phi_dev_post(dt, sign, L.q[0], L.req, 0);
-        phi_dev_post(dt, sign, L.q[1], L.req, 1);
+        phi_begin(dt, L.q[0], f0, phi_rt(dt, step_length / na));          // (in LDS: private copies of the structures end up in scratch memory)
+        phi_begin(dt, L.q[1], f0, phi_rt(dt, step_length / nb));
+        phi_post(dt, sign, L.q[0], L.req, 0);
+        phi_post(dt, sign, L.q[1], L.req, 1);
         L.norm[0] = na; L.norm[1] = nb;
         L.evals = 0;
     }
@@ -1347,13 +1098,11 @@ __global__ __launch_bounds__(kBlock) void norm2_pair_begin_kernel(int64_t n, con
     search_from_lds(S, &L);
 }
 
-template <typename V> __device__ __forceinline__ V sel3(int i, V a, V b, V c) { return i == 0 ? a : (i == 1 ? b : c); }
-
-// finish_phi6_kernel + the host loop body of bfgs_dual_search behind it: the round's six sums, both machines fed --
-// the primary request, then the speculative ones that match what the machine asks for next --, the next round's
-// requests posted, the summary and the ticket published.  The reference point of :136 / :155 is not copied anywhere:
-// it is the trial point the machine consumed last, which stays in its request's buffer until the next launch -- and
-// that launch reads a reference element before it writes any trial-point element of the same index (PhiDev::ref_buf).
+// finish_phi6_kernel + the host loop body of bfgs_dual_search behind it: the round's six sums, both machines fed
+// (phi_consume), the next round's requests posted (phi_post), the summary and the ticket published.  The reference point
+// of :136 / :155 is not copied anywhere: it is the trial point the machine consumed last, which stays in its request's
+// buffer until the next launch -- and that launch reads a reference element before it writes any trial-point element of
+// the same index (PhiMachine::ref_buf).
 __global__ __launch_bounds__(kBlock) void finish_phi6_advance_kernel(const double *__restrict__ partials, int64_t count, double scale,
                                                                      double *__restrict__ out, int32_t *__restrict__ flags, double ticket,
                                                                      BfgsSearchDev *__restrict__ S, int round, int32_t dt,
@@ -1385,7 +1134,7 @@ __global__ __launch_bounds__(kBlock) void finish_phi6_advance_kernel(const doubl
     }
     double sres[6];
     block_sum_multi<6>(v, lds6, sres);
-    // The two searches are independent machines (their own PhiDev, their own side of the request table): wave 0's first
+    // The two searches are independent machines (their own PhiMachine, their own side of the request table): wave 0's first
     // lane drives the one along the gradient, wave 1's the one along the BFGS direction -- side by side instead of one
     // after the other on a single lane walking structures in LDS, which was most of this kernel's 7.7 us.
     __shared__ double s_sum[6];
@@ -1397,33 +1146,16 @@ __global__ __launch_bounds__(kBlock) void finish_phi6_advance_kernel(const doubl
     __syncthreads();
     if (live && (threadIdx.x == 0 || threadIdx.x == 64)) {
         const int r = threadIdx.x >> 6;
-        PhiDev &sm = L.q[r];                                     // (worked on in LDS: private copies end up in scratch memory, 4x slower)
+        PhiMachine &sm = L.q[r];                                 // (worked on in LDS: private copies end up in scratch memory, 4x slower)
         int64_t evals = 0;
-        if (sm.active[0]) {
-            const double f3[3] = {dev_rt(dt, scale * s_sum[r * 3 + 0]), dev_rt(dt, scale * s_sum[r * 3 + 1]), dev_rt(dt, scale * s_sum[r * 3 + 2])};
-            int used = 0, slot = 0;
-            for (int turn = 0; turn < 3; ++turn) {           // (at most the three requests of this direction)
-                used |= 1 << slot;
-                const int changed = sel3(slot, hf_s[r * 9 + 0], hf_s[r * 9 + 3], hf_s[r * 9 + 6]);
-                const int nonzero = sel3(slot, hf_s[r * 9 + 1], hf_s[r * 9 + 4], hf_s[r * 9 + 7]);
-                const int differs = sel3(slot, hf_s[r * 9 + 2], hf_s[r * 9 + 5], hf_s[r * 9 + 8]);
-                phi_dev_feed(dt, max_increases, sm, sel3(slot, f3[0], f3[1], f3[2]), changed != 0, nonzero != 0, differs == 0,
-                             slot, (round % 4) * 6 + r * 3 + slot, round, evals);
-                if (!sm.want) break;
-                int next = -1;
-#pragma unroll
-                for (int e = 1; e < 3; ++e)
-                    if (sm.active[e] && !(used & (1 << e)) && sm.spec_t[e] == sm.req_t && sm.spec_ref[e] == sm.req_ref) next = e;
-                if (next < 0) break;
-                slot = next;
-            }
-        }
-        phi_dev_post(dt, sign, sm, L.req, r);
+        phi_consume(dt, max_increases, sm, phi_rt(dt, scale * s_sum[r * 3 + 0]), phi_rt(dt, scale * s_sum[r * 3 + 1]),
+                    phi_rt(dt, scale * s_sum[r * 3 + 2]), hf_s + r * 9, phi_pool_index(round, r, 0), round, evals);
+        phi_post(dt, sign, sm, L.req, r);
         s_evals[r] = evals;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        PhiDev *q = L.q;
+        PhiMachine *q = L.q;
         int64_t evals = L.evals;
         if (live) {
             evals += s_evals[0] + s_evals[1];
@@ -1458,8 +1190,7 @@ static int32_t bfgs_dev_search(dzo_bfgs_s *o, double step_length, double *grad_n
         o->problem->l2 != 0.0 || o->problem->cons_on || o->n > 65536 || o->problem->scratch_doubles < 6 * o->n)
         return DZO_OK;
     const int32_t dt = o->dtype;
-    const size_t es = dtype_size(dt);
-    const size_t vbytes = (size_t)((o->n + 63) / 64 * 64) * es;
+    const PhiBuffers B = phi_buffers(o);
     hipStream_t s = o->stream;
     const void *dirs[2] = {o->g, o->d};
     {
@@ -1467,18 +1198,14 @@ static int32_t bfgs_dev_search(dzo_bfgs_s *o, double step_length, double *grad_n
         DZO_DISPATCH(dt, hipLaunchKernelGGL(norm2_pair_begin_kernel<T>, dim3(1), dim3(kBlock), 0, s, o->n, (const T *)o->g, (const T *)o->d,
                                             o->dsearch, o->f, step_length, dt, o->sign));
     }
-    void *pts[2][3] = {{o->scratch, o->spec_buf[0], o->spec_buf[1]}, {o->scratch2, o->spec_buf[2], o->spec_buf[3]}};   // trial-point buffer of request slot e
     int round = 0;
     auto enqueue_round = [&](bool publish) -> int32_t {
         round += 1;
         PhiDirHost req[2];
+        phi_round_outputs(o, B, round, req);
         for (int r = 0; r < 2; ++r) {
             req[r].dir = dirs[r];
-            for (int e = 0; e < 3; ++e) {
-                req[r].point_out[e] = pts[r][e];
-                req[r].grad_out[e] = (char *)o->grad_pool + (size_t)((round % 4) * 6 + r * 3 + e) * vbytes;
-                req[r].active[e] = true;                         // (the kernel takes these three from the device's requests)
-            }
+            for (int e = 0; e < 3; ++e) req[r].active[e] = true;   // (the kernel takes these three from the device's requests)
         }
         o->ticket += 1.0;
         DZO_REQUIRE(problem_phi6_async(o->problem, s, o->x, req, o->phi_flags(), o->host_dev, o->ticket, &o->dsearch->req), DZO_ERR_HIP,
@@ -1500,22 +1227,16 @@ static int32_t bfgs_dev_search(dzo_bfgs_s *o, double step_length, double *grad_n
     *grad_norm = sum[4]; *bfgs_norm_v = sum[kSumStride + 4];
     o->evals += (int64_t)sum[2 * kSumStride];
     o->best_grad[0] = o->best_grad[1] = nullptr;
-    double tt[2], ff[2];
-    for (int r = 0; r < 2; ++r) {
-        const double *q = sum + kSumStride * r;
-        const int64_t packed = (int64_t)q[0];
-        const int state = (int)((packed >> 8) & 0xFF);
-        const double t0 = q[3];
-        if (state == kPhiSequential) {                           // the rare tiny-step path (:91-101): the sequential code
-            DZO_TRY(bfgs_quadratic_search(o, dirs[r], o->f, t0, &tt[r], &ff[r]));
-            continue;
-        }
-        tt[r] = q[1]; ff[r] = q[2];
-        const int bg = (int)((packed >> 16) & 0xFFFF) - 1, br = (int)(packed >> 32);
-        if (state == kPhiDone && tt[r] != 0.0 && bg >= 0 && round - br < 4)
-            o->best_grad[r] = (char *)o->grad_pool + (size_t)bg * vbytes;
+    double *tt[2] = {t_a, t_b}, *ff[2] = {f_a, f_b};
+    for (int r = 0; r < 2; ++r) {                                // the summary unpacked (phi_dev_summary) into what the result needs
+        const double *v = sum + kSumStride * r;
+        const int64_t packed = (int64_t)v[0];
+        PhiMachine q = {};
+        q.state = (int32_t)((packed >> 8) & 0xFF);
+        q.best_grad = (int32_t)((packed >> 16) & 0xFFFF) - 1; q.best_round = (int32_t)(packed >> 32);
+        q.t_best = v[1]; q.f_best = v[2]; q.t0 = v[3];
+        DZO_TRY(bfgs_search_result(o, B, q, round, r, dirs[r], tt[r], ff[r]));
     }
-    *t_a = tt[0]; *f_a = ff[0]; *t_b = tt[1]; *f_b = ff[1];
     *done = true;
     return DZO_OK;
 }

@@ -1,6 +1,7 @@
 // dzo_problems.h -- internal interface of the built-in objectives (see dzo_problems.hip).
 #pragma once
 #include "dzo_common.h"
+#include "dzo_phi_search.h"
 
 struct dzo_problem_s {
     int32_t kind = 0;
@@ -55,16 +56,9 @@ struct PhiDirHost {
     void *grad_out[3] = {nullptr, nullptr, nullptr};
     bool active[3] = {false, false, false};
 };
-// the requests of one launch as the DEVICE posts them (device-driven line searches of the dense BFGS step): step sizes
-// (signed, already rounded to the dtype), which of the six run, and what each one's :150 test compares with
-struct PhiReqDev {
-    double ts[2][3];
-    int32_t active[2][3];
-    int32_t ref_req[2][3];      // the request of the same direction in this launch to compare with, or -1
-    int32_t use_ref[2][3];      // [side][0]: 0 = no stored reference point, 1 + b = the direction's trial-point buffer b (point_out[b]) as it stands
-};
-// dreq: take step sizes / activity / references from there (the buffers still from req; req's ref pointers are not used) and
-// leave the finish to the caller
+// dreq (PhiReqDev, dzo_phi_search.h: the requests of one launch as the DEVICE posts them, device-driven line searches of the
+// dense BFGS step): take step sizes / activity / references from there (the buffers still from req; req's ref pointers are
+// not used) and leave the finish to the caller
 bool problem_phi6_async(dzo_problem_s *p, hipStream_t s, const void *x, const PhiDirHost req[2], int32_t *flags, double *result_dev, double ticket,
                         const PhiReqDev *dreq = nullptr);   // result_dev[20] <- ticket, last
 // Enqueue g = grad f(x) on `s`.

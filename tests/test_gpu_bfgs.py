@@ -389,17 +389,29 @@ def test_side_by_side_line_searches_equal_the_sequential_ones(n, monkeypatch):
 
 @pytest.mark.parametrize("n,dtype,step0,max_inc", [(16, np.float64, 1.0, 0), (200, np.float64, 1.0, 0), (513, np.float64, 1.0, 0),
                                                    (200, np.float32, 1.0, 0), (64, np.float64, 1e4, 0), (64, np.float64, 1e-7, 0),
-                                                   (200, np.float64, 1e-7, 3), (130, np.float32, 50.0, 2), (4096, np.float64, 1.0, 0)])
+                                                   (200, np.float64, 1e-7, 3), (130, np.float32, 50.0, 2), (4096, np.float64, 1.0, 0),
+                                                   (16, np.float64, 2.0 ** -30, 0)])
 def test_device_driven_line_searches_equal_the_host_driven_ones(n, dtype, step0, max_inc, monkeypatch):
     """bfgs_dev_search: the two searches' state machines run on the device (norm kernel begins them, every round's
     finish kernel feeds them and posts the next requests), the host waits once per step.  A re-scheduling again:
-    same points, values, step types and lengths, evaluation counts -- whatever number of rounds is enqueued ahead."""
+    same points, values, step types and lengths, evaluation counts -- whatever number of rounds is enqueued ahead.
+    The last case is the tiny-step hand-over (:91-101): x0 scaled up until the first trial point along the gradient is x0
+    itself, so both machines report Sequential and the step is finished by the sequential search -- compared with that
+    search alone (DUAL_SEARCH=0) as well."""
     A = orc.quadratic_matrix(n).astype(dtype)
     x0 = (orc.pcg_fill(n, 4) - 0.5).astype(dtype)
+    configs = [("0", "2", "1"), ("1", "2", "1"), ("1", "1", "1"), ("1", "4", "1")]
+    if step0 == 2.0 ** -30:
+        x0 = x0 * 2.0 ** 40
+        g = orc.Problem(orc.QUADRATIC, n, A=A).grad(x0)
+        t0 = step0 / np.sqrt(g @ g)                                          # fl(step0 / ||g||), to the rounding of the norm
+        assert np.all(g != 0) and all(np.array_equal(x0 - t * g, x0) for t in (t0 * (1 - 1e-9), t0, t0 * (1 + 1e-9)))
+        configs.append(("0", "2", "0"))
     runs = []
-    for dev, rounds in (("0", "2"), ("1", "2"), ("1", "1"), ("1", "4")):
+    for dev, rounds, dual in configs:
         monkeypatch.setenv("DZO_TUNE_BFGS_DEV_SEARCH", dev)
         monkeypatch.setenv("DZO_TUNE_BFGS_DEV_ROUNDS", rounds)
+        monkeypatch.setenv("DZO_TUNE_BFGS_DUAL_SEARCH", dual)
         opt = dzo.BFGSOptimizer(dzo.Problem(dzo.QUADRATIC, n, A=A, dtype=dtype), None, dzo.DeviceArray.from_host(x0), step0)
         if max_inc:
             opt.set_max_increases(max_inc)
