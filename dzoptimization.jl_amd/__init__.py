@@ -192,6 +192,10 @@ ABI = {
     "dzo_lbfgs_batch_set_max_halvings": [_vp, _i64], "dzo_lbfgs_batch_step": [_vp, _i32, _P(_i32)],
     "dzo_lbfgs_batch_count_active": [_vp, _P(_i64)], "dzo_lbfgs_batch_get_ptr": [_vp, _i32, _P(_vp)],
     "dzo_lbfgs_batch_read": [_vp, _i32, _vp], "dzo_pairwise_batch_energy_gradient": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
+    "dzo_basin_hopping_create": [_i32, _i64, _i64, _i32, _vp, _P(_dbl), _P(_dbl), _dbl, _dbl, _i32, _i32, C.c_uint64, _P(_vp)],
+    "dzo_basin_hopping_destroy": [_vp], "dzo_basin_hopping_set_max_halvings": [_vp, _i64], "dzo_basin_hopping_hop": [_vp, _i64, _i32],
+    "dzo_basin_hopping_set_record": [_vp, _i64], "dzo_basin_hopping_get_ptr": [_vp, _i32, _P(_vp)],
+    "dzo_basin_hopping_read": [_vp, _i32, _vp], "dzo_basin_hopping_set": [_vp, _i32, _vp],
     "dzo_adgd_batch_create": [_i32, _i64, _i64, _i32, _vp, _dbl, _P(_vp)], "dzo_adgd_batch_destroy": [_vp],
     "dzo_adgd_batch_set_max_halvings": [_vp, _i64], "dzo_adgd_batch_step": [_vp, _i32, _P(_i32)],
     "dzo_adgd_batch_count_active": [_vp, _P(_i64)], "dzo_adgd_batch_get_ptr": [_vp, _i32, _P(_vp)],
@@ -728,6 +732,107 @@ class BatchedLBFGS(_BatchedOptimizer):
 
     step_directions = property(lambda self: self.read(LBFGS_BATCH_DIRECTIONS))
     history_counts = property(lambda self: self.read(LBFGS_BATCH_HISTORY_COUNTS))
+
+
+# ------------------------------------------------------------------------------ batched basin hopping over Lennard-Jones clusters
+BASIN_HOPPING_MAX_PARTICLES = 1024
+(BASIN_HOPPING_POINTS, BASIN_HOPPING_ENERGIES, BASIN_HOPPING_BEST_POINTS, BASIN_HOPPING_BEST_ENERGIES, BASIN_HOPPING_RADII,
+ BASIN_HOPPING_INV_TEMPS, BASIN_HOPPING_NUM_ACCEPT, BASIN_HOPPING_NUM_REJECT, BASIN_HOPPING_RNG_STATES, BASIN_HOPPING_HOP_COUNTS,
+ BASIN_HOPPING_QUENCH_ITERATIONS, BASIN_HOPPING_QUENCH_UNFINISHED, BASIN_HOPPING_REC_NORMALS, BASIN_HOPPING_REC_UNIFORM,
+ BASIN_HOPPING_REC_TRIAL_ENERGY, BASIN_HOPPING_REC_QUENCH_ITERATIONS, BASIN_HOPPING_REC_CODE) = range(17)
+
+
+class BasinHopping(_HandleArrays):
+    """Basin hopping (Monte Carlo over the quenched landscape) of many walkers over Lennard-Jones clusters: ``hop(k)`` runs k
+    hops -- perturb every particle, quench with the batched L-BFGS, Metropolis test on the quenched energies -- of every walker
+    at the walker's own pace, ``hops_per_launch`` hops per launch.  ``points`` is a DeviceArray of ``3 * n_particles * batch``
+    elements (the quench's layout); it is aliased and always holds the walkers' current minima.  ``inverse_temperatures`` and
+    ``perturbation_radii`` are host sequences, one per walker.  The rule is in include/dzo.h.
+
+    The constructor and ``hop(wait=False)`` do not block; every property that reads device state does."""
+    _read_fn, _ptr_fn = "dzo_basin_hopping_read", "dzo_basin_hopping_get_ptr"
+
+    def __init__(self, points, n_particles, inverse_temperatures, perturbation_radii, constraining_radius, initial_step_length=0.01,
+                 history_length=10, quench_steps=400, base_seed=0, radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.points = points
+        self.dtype = points.dtype
+        self.n_particles = int(n_particles)
+        beta = np.ascontiguousarray(inverse_temperatures, dtype=np.float64)
+        rad = np.ascontiguousarray(perturbation_radii, dtype=np.float64)
+        assert beta.ndim == 1 and beta.shape == rad.shape
+        self.batch = int(beta.size)
+        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        self.constraining_radius = float(constraining_radius)
+        self.history_length, self.quench_steps = int(history_length), int(quench_steps)
+        self.record_capacity = 0
+        h = C.c_void_p()
+        _check(lib().dzo_basin_hopping_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr,
+                                              beta.ctypes.data_as(_P(_dbl)), rad.ctypes.data_as(_P(_dbl)), self.constraining_radius,
+                                              float(initial_step_length), self.history_length, self.quench_steps,
+                                              int(base_seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            lib().dzo_basin_hopping_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_max_halvings(self, v):
+        _check(lib().dzo_basin_hopping_set_max_halvings(self.h, int(v)))
+
+    def hop(self, num_hops, adapt=True, hops_per_launch=8, wait=True):
+        """``num_hops`` hops of every walker in ``ceil(num_hops / hops_per_launch)`` launches (a launch lasts as long as its
+        slowest walker's quenches: keep it short).  With ``adapt`` the radii are adapted once, at the end of the last launch,
+        on that launch's counts.  ``wait=False`` enqueues only."""
+        num_hops, per = int(num_hops), int(hops_per_launch)
+        assert num_hops >= 0 and per >= 1
+        done = 0
+        while done < num_hops:
+            k = min(per, num_hops - done)
+            done += k
+            _check(lib().dzo_basin_hopping_hop(self.h, k, int(bool(adapt) and done == num_hops)))
+        if wait:
+            synchronize()
+
+    def set_record(self, capacity_hops):
+        _check(lib().dzo_basin_hopping_set_record(self.h, int(capacity_hops)))
+        self.record_capacity = int(capacity_hops)
+
+    def _shape(self, what):
+        b, n, cap = self.batch, self.n_particles, self.record_capacity
+        vec, sc, cnt = ((b, 3 * n), self.dtype), ((b,), self.dtype), ((b,), np.int64)
+        return {BASIN_HOPPING_POINTS: vec, BASIN_HOPPING_ENERGIES: sc, BASIN_HOPPING_BEST_POINTS: vec, BASIN_HOPPING_BEST_ENERGIES: sc,
+                BASIN_HOPPING_RADII: sc, BASIN_HOPPING_INV_TEMPS: sc, BASIN_HOPPING_NUM_ACCEPT: cnt, BASIN_HOPPING_NUM_REJECT: cnt,
+                BASIN_HOPPING_RNG_STATES: ((b,), np.uint64), BASIN_HOPPING_HOP_COUNTS: cnt, BASIN_HOPPING_QUENCH_ITERATIONS: cnt,
+                BASIN_HOPPING_QUENCH_UNFINISHED: cnt, BASIN_HOPPING_REC_NORMALS: ((b, cap, n, 3), self.dtype),
+                BASIN_HOPPING_REC_UNIFORM: ((b, cap), self.dtype), BASIN_HOPPING_REC_TRIAL_ENERGY: ((b, cap), self.dtype),
+                BASIN_HOPPING_REC_QUENCH_ITERATIONS: ((b, cap), np.int32), BASIN_HOPPING_REC_CODE: ((b, cap), np.int8)}[what]
+
+    def _set(self, what, values):
+        shape, dtype = self._shape(what)
+        a = np.ascontiguousarray(values, dtype=dtype)
+        assert a.shape == shape
+        _check(lib().dzo_basin_hopping_set(self.h, int(what), a.ctypes.data))
+
+    current_points = property(lambda self: self.read(BASIN_HOPPING_POINTS))
+    energies = property(lambda self: self.read(BASIN_HOPPING_ENERGIES))
+    best_points = property(lambda self: self.read(BASIN_HOPPING_BEST_POINTS))
+    best_energies = property(lambda self: self.read(BASIN_HOPPING_BEST_ENERGIES))
+    inverse_temperatures = property(lambda self: self.read(BASIN_HOPPING_INV_TEMPS))
+    perturbation_radii = property(lambda self: self.read(BASIN_HOPPING_RADII), lambda self, v: self._set(BASIN_HOPPING_RADII, v))
+    rng_states = property(lambda self: self.read(BASIN_HOPPING_RNG_STATES), lambda self, v: self._set(BASIN_HOPPING_RNG_STATES, v))
+    num_accept = property(lambda self: self.read(BASIN_HOPPING_NUM_ACCEPT))
+    num_reject = property(lambda self: self.read(BASIN_HOPPING_NUM_REJECT))
+    hop_counts = property(lambda self: self.read(BASIN_HOPPING_HOP_COUNTS))
+    quench_iterations = property(lambda self: self.read(BASIN_HOPPING_QUENCH_ITERATIONS))
+    quench_unfinished = property(lambda self: self.read(BASIN_HOPPING_QUENCH_UNFINISHED))
 
 
 # ------------------------------------------------------------------------------ batched AdGD over Lennard-Jones clusters

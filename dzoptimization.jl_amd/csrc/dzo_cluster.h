@@ -1,5 +1,5 @@
 // dzo_cluster.h -- what the units that run MANY small Lennard-Jones clusters at once share: dzo_lbfgs_batch.hip, dzo_adgd_batch.hip,
-// dzo_hessian_batch.hip and dzo_tempering.hip.  One definition each, the same bits in all of them.  Every name here starts with
+// dzo_hessian_batch.hip, dzo_tempering.hip and dzo_basin_hopping.hip.  One definition each, the same bits in all of them.  Every name here starts with
 // cl_ (functions), Cl (types), kCl (constants) or CL_ (the one macro).  The two launch shapes, WAVE (N <= 64, one wave per
 // instance) and BLOCK (up to 1024 particles, one 256-thread block per instance), are described in dzo_lbfgs_batch.hip.
 // A .hip that uses dynamic LDS declares its own `extern __shared__` array.

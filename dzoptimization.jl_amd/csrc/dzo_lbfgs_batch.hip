@@ -13,6 +13,8 @@
 //     broadcast), the trial gradient in registers.  The history ring is in LDS where it fits the 160 KiB, else in a
 //     handle-owned global slab.
 //
+// The step loop of either shape and the constructor's first direction are the device functions of dzo_quench_core.h (the
+// kernels here are load -> run -> store around them; dzo_basin_hopping.hip runs them once per hop).
 // The shapes' shared pieces (the evaluation of a trial, the block sums and dots, the owner loop, the handle's host core) are in
 // dzo_cluster.h; dzo_adgd_batch.hip is the second optimizer on them.  The evaluation and count-active kernels and their launchers
 // are defined here for both.  Per pair the arithmetic is dzo_pairwise.hip's: pw_pair of dzo_pairwise.h (the self term removed
@@ -20,6 +22,7 @@
 // j = 0 .. N-1 in T, rows are added in fp64 by the fixed trees of dzo_common.h, one rounding back to T; dots accumulate in fp64
 // in a fixed order that depends on N only.  No floating-point atomic.  The recursion is the chain form of :430-451.
 #include "dzo_cluster.h"
+#include "dzo_quench_core.h"
 
 #include <cmath>
 #include <new>
@@ -53,14 +56,9 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void quench_w
     if (lane == 0) a.f[b] = E;
     if (a.g && live) { a.g[base + lane] = gx; a.g[base + N + lane] = gy; a.g[base + 2 * N + lane] = gz; }
     if (!a.init) return;
-    const double gg = wave_sum_all(cl_dot3(gx, gy, gz, gx, gy, gz));
-    const bool stuck = gg == 0.0;                            // iszero(norm), :382
-    const T sc = (T)(-((double)a.step_length / ::sqrt(gg))); // :387
-    if (live) {
-        a.d[base + lane] = stuck ? T(0) : sc * gx;
-        a.d[base + N + lane] = stuck ? T(0) : sc * gy;
-        a.d[base + 2 * N + lane] = stuck ? T(0) : sc * gz;
-    }
+    T px, py, pz;
+    const bool stuck = qc_wave_first_direction<T>(a.step_length, gx, gy, gz, px, py, pz);   // :381-387
+    if (live) { a.d[base + lane] = px; a.d[base + N + lane] = py; a.d[base + 2 * N + lane] = pz; }
     if (lane == 0) a.stuck[b] = stuck ? 1 : 0;
 }
 
@@ -73,87 +71,36 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void quench_w
     const int64_t base = (int64_t)3 * N * b;
     const bool live = lane < N;
     auto ld = [&](const T *p, int c) { return live ? p[base + c * N + lane] : T(0); };
-    T x = ld(a.x, 0), y = ld(a.x, 1), z = ld(a.x, 2);
-    T gx = ld(a.g, 0), gy = ld(a.g, 1), gz = ld(a.g, 2);
-    T px = ld(a.d, 0), py = ld(a.d, 1), pz = ld(a.d, 2);
-    T sx = ld(a.dx, 0), sy = ld(a.dx, 1), sz = ld(a.dx, 2);
-    T yx = ld(a.dg, 0), yy = ld(a.dg, 1), yz = ld(a.dg, 2);
-    T E = a.f[b], dE = a.df[b];
-    int64_t it = a.iters[b];
-    int hc = a.hcount[b], halv = a.halv[b], head = 0;
+    QcWave<T> w;
+    w.x = ld(a.x, 0); w.y = ld(a.x, 1); w.z = ld(a.x, 2);
+    w.gx = ld(a.g, 0); w.gy = ld(a.g, 1); w.gz = ld(a.g, 2);
+    w.px = ld(a.d, 0); w.py = ld(a.d, 1); w.pz = ld(a.d, 2);
+    w.sx = ld(a.dx, 0); w.sy = ld(a.dx, 1); w.sz = ld(a.dx, 2);
+    w.yx = ld(a.dg, 0); w.yy = ld(a.dg, 1); w.yz = ld(a.dg, 2);
+    w.E = a.f[b]; w.dE = a.df[b];
+    w.it = a.iters[b];
+    w.hc = a.hcount[b]; w.halv = a.halv[b]; w.head = 0;
+    const int hc0 = w.hc;
     // LDS: rho[m] | alpha[m] | S ring | Y ring; element (slot p, component c) of this lane at (p * 3 + c) * 64 + lane
     double *rho = quench_smem, *alpha = rho + m;
     T *hS = reinterpret_cast<T *>(alpha + m), *hY = hS + m * 3 * 64;
     const int64_t hbase = (int64_t)3 * N * m * b;
-    for (int k = 0; k < hc; ++k) {
+    for (int k = 0; k < hc0; ++k) {
         rho[k] = a.rho[(int64_t)m * b + k];                  // every lane the same value to the same address
         for (int c = 0; c < 3; ++c) {
             hS[(k * 3 + c) * 64 + lane] = live ? a.S[hbase + (int64_t)3 * N * k + c * N + lane] : T(0);
             hY[(k * 3 + c) * 64 + lane] = live ? a.Y[hbase + (int64_t)3 * N * k + c * N + lane] : T(0);
         }
     }
-    bool stuck = false;
-    for (int s = 0; s < a.steps && !stuck; ++s) {
-        if (it > 0) {                                        // compute_lbfgs_step_direction!, :430-451
-            T qx = gx, qy = gy, qz = gz;
-            for (int k = 0; k < hc; ++k) {
-                const int p = head + k < m ? head + k : head + k - m;
-                const T *sp = hS + p * 3 * 64 + lane, *yp = hY + p * 3 * 64 + lane;
-                const T al = (T)(wave_sum_all(cl_dot3(sp[0], sp[64], sp[128], qx, qy, qz)) / rho[p]);   // :440
-                alpha[p] = (double)al;
-                qx = dfma<T>(-al, yp[0], qx); qy = dfma<T>(-al, yp[64], qy); qz = dfma<T>(-al, yp[128], qz);   // :441
-            }
-            if (hc > 0) {
-                const T *yp = hY + head * 3 * 64 + lane;
-                const T gm = (T)(-(rho[head] / wave_sum_all(cl_dot3(yp[0], yp[64], yp[128], yp[0], yp[64], yp[128]))));   // :444
-                qx *= gm; qy *= gm; qz *= gm;
-            }
-            for (int k = hc - 1; k >= 0; --k) {
-                const int p = head + k < m ? head + k : head + k - m;
-                const T *sp = hS + p * 3 * 64 + lane, *yp = hY + p * 3 * 64 + lane;
-                const T beta = (T)(wave_sum_all(cl_dot3(yp[0], yp[64], yp[128], qx, qy, qz)) / rho[p]);   // :447
-                const T cf = -((T)alpha[p] + beta);
-                qx = dfma<T>(cf, sp[0], qx); qy = dfma<T>(cf, sp[64], qy); qz = dfma<T>(cf, sp[128], qz);   // :448
-            }
-            px = qx; py = qy; pz = qz;
-        }
-        // take_backtracking_step!, :107-154, from t = 1
-        const T x0 = x, y0 = y, z0 = z;                      // :118
-        T t = T(1);
-        int h = 0;
-        for (;;) {
-            const T xt = dfma<T>(t, px, x0), yt = dfma<T>(t, py, y0), zt = dfma<T>(t, pz, z0);   // :124
-            if (__all(is_equal(xt, x0) && is_equal(yt, y0) && is_equal(zt, z0))) { stuck = true; break; }   // :128
-            T Et, tx, ty, tz;
-            cl_wave_eval<T, F>(N, lane, xt, yt, zt, Et, tx, ty, tz);
-            if (Et < E) {                                    // :139
-                dE = Et - E; E = Et;                         // :142-144
-                sx = xt - x0; sy = yt - y0; sz = zt - z0;    // :145
-                yx = tx - gx; yy = ty - gy; yz = tz - gz;    // :478-480
-                x = xt; y = yt; z = zt;
-                gx = tx; gy = ty; gz = tz;
-                break;
-            }
-            t *= T(0.5);                                     // :152 (the point was never overwritten: :151)
-            if (++h >= a.max_halvings) { stuck = true; break; }
-        }
-        halv = h;
-        if (stuck) { sx = x0; sy = y0; sz = z0; break; }     // delta_point keeps the copy of :118
-        head = head == 0 ? m - 1 : head - 1;                 // pushfirst!, :482-496
-        T *sp = hS + head * 3 * 64 + lane, *yp = hY + head * 3 * 64 + lane;
-        sp[0] = sx; sp[64] = sy; sp[128] = sz;
-        yp[0] = yx; yp[64] = yy; yp[128] = yz;
-        rho[head] = wave_sum_all(cl_dot3(sx, sy, sz, yx, yy, yz));   // :505
-        if (hc < m) ++hc;
-        ++it;                                                // :507
-    }
+    const bool stuck = qc_wave_run<T, F>(N, m, lane, a.steps, a.max_halvings, w, rho, alpha, hS, hY);
+    const int hc = w.hc, head = w.head;
     if (live) {
         auto st = [&](T *p, int c, T v) { p[base + c * N + lane] = v; };
-        st(a.x, 0, x); st(a.x, 1, y); st(a.x, 2, z);
-        st(a.g, 0, gx); st(a.g, 1, gy); st(a.g, 2, gz);
-        st(a.d, 0, px); st(a.d, 1, py); st(a.d, 2, pz);
-        st(a.dx, 0, sx); st(a.dx, 1, sy); st(a.dx, 2, sz);
-        st(a.dg, 0, yx); st(a.dg, 1, yy); st(a.dg, 2, yz);
+        st(a.x, 0, w.x); st(a.x, 1, w.y); st(a.x, 2, w.z);
+        st(a.g, 0, w.gx); st(a.g, 1, w.gy); st(a.g, 2, w.gz);
+        st(a.d, 0, w.px); st(a.d, 1, w.py); st(a.d, 2, w.pz);
+        st(a.dx, 0, w.sx); st(a.dx, 1, w.sy); st(a.dx, 2, w.sz);
+        st(a.dg, 0, w.yx); st(a.dg, 1, w.yy); st(a.dg, 2, w.yz);
         for (int k = 0; k < hc; ++k) {
             const int p = head + k < m ? head + k : head + k - m;
             for (int c = 0; c < 3; ++c) {
@@ -164,10 +111,10 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void quench_w
     }
     if (lane < hc) a.rho[(int64_t)m * b + lane] = rho[head + lane < m ? head + lane : head + lane - m];
     if (lane == 0) {
-        a.f[b] = E; a.df[b] = dE;
+        a.f[b] = w.E; a.df[b] = w.dE;
         a.stuck[b] = stuck ? 1 : 0;
-        a.iters[b] = it;
-        a.hcount[b] = hc; a.halv[b] = halv;
+        a.iters[b] = w.it;
+        a.hcount[b] = hc; a.halv[b] = w.halv;
     }
 }
 
@@ -183,28 +130,15 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void quen
     T E, gx[kClPer], gy[kClPer], gz[kClPer];
     cl_block_eval<T, F>(N, tid, X, red, par, E, gx, gy, gz);
     if (tid == 0) a.f[b] = E;
-    double part = 0;
-#pragma unroll
-    for (int q = 0; q < kClPer; ++q) {
-        const int i = tid + kBlock * q;
-        if (i < N) {
-            if (a.g) { a.g[base + i] = gx[q]; a.g[base + N + i] = gy[q]; a.g[base + 2 * N + i] = gz[q]; }
-            part += cl_dot3(gx[q], gy[q], gz[q], gx[q], gy[q], gz[q]);
-        }
-    }
+    if (a.g) { CL_FOR_OWN(i, a.g[base + i] = gx[q]; a.g[base + N + i] = gy[q]; a.g[base + 2 * N + i] = gz[q];) }
     if (!a.init) return;
-    const double gg = cl_block_sum(part, red, par);
-    const bool stuck = gg == 0.0;
-    const T sc = (T)(-((double)a.step_length / ::sqrt(gg)));
-#pragma unroll
-    for (int q = 0; q < kClPer; ++q) {
-        const int i = tid + kBlock * q;
-        if (i < N) {
-            a.d[base + i] = stuck ? T(0) : sc * gx[q];
-            a.d[base + N + i] = stuck ? T(0) : sc * gy[q];
-            a.d[base + 2 * N + i] = stuck ? T(0) : sc * gz[q];
-        }
-    }
+    bool stuck;
+    const T sc = qc_block_first_scale<T>(N, tid, a.step_length, gx, gy, gz, red, par, stuck);   // :381-387
+    CL_FOR_OWN(i, {
+        a.d[base + i] = stuck ? T(0) : sc * gx[q];
+        a.d[base + N + i] = stuck ? T(0) : sc * gy[q];
+        a.d[base + 2 * N + i] = stuck ? T(0) : sc * gz[q];
+    })
     if (tid == 0) a.stuck[b] = stuck ? 1 : 0;
 }
 
@@ -226,92 +160,16 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
     double *const grho_ = pw_pin_ptr(a.rho + (int64_t)m * b);
     int32_t *const gstuck_ = pw_pin_ptr(a.stuck + b), *const ghc_ = pw_pin_ptr(a.hcount + b), *const ghalv_ = pw_pin_ptr(a.halv + b);
     int64_t *const git_ = pw_pin_ptr(a.iters + b);
-    int hc = *ghc_, halv = *ghalv_, head = 0, par = 0;
-    int64_t it = *git_;
-    T E = *gf_, dE = *gdf_;
+    QcBlock<T> w{X, G, D, DX, DG, hS, hY, rho, alpha, red, *gf_, *gdf_, *git_, *ghc_, *ghalv_, 0, 0};
+    const int hc0 = w.hc;
     CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) {
         const int e = c * N + i;
         X[e] = gx_[e]; G[e] = gg_[e]; D[e] = gd_[e]; DX[e] = gdx_[e]; DG[e] = gdg_[e];
-        for (int k = 0; k < hc; ++k) { hS[k * n3 + e] = gS_[(int64_t)n3 * k + e]; hY[k * n3 + e] = gY_[(int64_t)n3 * k + e]; }
+        for (int k = 0; k < hc0; ++k) { hS[k * n3 + e] = gS_[(int64_t)n3 * k + e]; hY[k * n3 + e] = gY_[(int64_t)n3 * k + e]; }
     })
-    for (int k = 0; k < hc; ++k) rho[k] = grho_[k];   // every thread the same value to the same address
-    bool stuck = false;
-    for (int s = 0; s < a.steps && !stuck; ++s) {
-        if (it > 0) {                                        // compute_lbfgs_step_direction!, :430-451, on D
-            CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) D[c * N + i] = G[c * N + i];)
-            for (int k = 0; k < hc; ++k) {
-                const int p = head + k < m ? head + k : head + k - m;
-                const T *sp = hS + p * n3, *yp = hY + p * n3;
-                double part = 0;
-                CL_FOR_OWN(i, part += cl_dot3(sp[i], sp[N + i], sp[2 * N + i], D[i], D[N + i], D[2 * N + i]);)
-                const T al = (T)(cl_block_sum(part, red, par) / rho[p]);
-                alpha[p] = (double)al;
-                CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) D[c * N + i] = dfma<T>(-al, yp[c * N + i], D[c * N + i]);)
-            }
-            if (hc > 0) {
-                const T *yp = hY + head * n3;
-                double part = 0;
-                CL_FOR_OWN(i, part += cl_dot3(yp[i], yp[N + i], yp[2 * N + i], yp[i], yp[N + i], yp[2 * N + i]);)
-                const T gm = (T)(-(rho[head] / cl_block_sum(part, red, par)));
-                CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) D[c * N + i] *= gm;)
-            }
-            for (int k = hc - 1; k >= 0; --k) {
-                const int p = head + k < m ? head + k : head + k - m;
-                const T *sp = hS + p * n3, *yp = hY + p * n3;
-                double part = 0;
-                CL_FOR_OWN(i, part += cl_dot3(yp[i], yp[N + i], yp[2 * N + i], D[i], D[N + i], D[2 * N + i]);)
-                const T beta = (T)(cl_block_sum(part, red, par) / rho[p]);
-                const T cf = -((T)alpha[p] + beta);
-                CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) D[c * N + i] = dfma<T>(cf, sp[c * N + i], D[c * N + i]);)
-            }
-        }
-        // take_backtracking_step!, :107-154: DX keeps the old point (:118), X is the trial (:124)
-        CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) DX[c * N + i] = X[c * N + i];)
-        T t = T(1);
-        int h = 0;
-        bool accepted = false;
-        T tx[kClPer], ty[kClPer], tz[kClPer];
-        for (;;) {
-            bool same = true;
-            CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) {
-                const T v = dfma<T>(t, D[c * N + i], DX[c * N + i]);
-                X[c * N + i] = v;
-                same = same && is_equal(v, DX[c * N + i]);
-            })
-            if (__syncthreads_and(same ? 1 : 0)) { stuck = true; break; }   // :128; the barrier also publishes the trial point
-            T Et;
-            cl_block_eval<T, F>(N, tid, X, red, par, Et, tx, ty, tz);       // its barrier: every thread has read X
-            if (Et < E) { dE = Et - E; E = Et; accepted = true; break; }   // :139-144
-            t *= T(0.5);                                                    // :152
-            if (++h >= a.max_halvings) { stuck = true; break; }
-        }
-        halv = h;
-        if (!accepted) {                                     // :151 / the copy of :118 stays in DX
-            CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) X[c * N + i] = DX[c * N + i];)
-            break;
-        }
-        head = head == 0 ? m - 1 : head - 1;                 // pushfirst!, :482-496
-        T *sp = hS + head * n3, *yp = hY + head * n3;
-        double part = 0;
-#pragma unroll
-        for (int q = 0; q < kClPer; ++q) {
-            const int i = tid + kBlock * q;
-            if (i < N) {
-                const T tg[3] = {tx[q], ty[q], tz[q]};
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int e = c * N + i;
-                    const T dxv = X[e] - DX[e], dgv = tg[c] - G[e];   // :145, :478-480
-                    DX[e] = dxv; DG[e] = dgv; G[e] = tg[c];
-                    sp[e] = dxv; yp[e] = dgv;
-                }
-                part += cl_dot3(DX[i], DX[N + i], DX[2 * N + i], DG[i], DG[N + i], DG[2 * N + i]);
-            }
-        }
-        rho[head] = cl_block_sum(part, red, par);            // :505
-        if (hc < m) ++hc;
-        ++it;
-    }
+    for (int k = 0; k < hc0; ++k) rho[k] = grho_[k];   // every thread the same value to the same address
+    const bool stuck = qc_block_run<T, F>(N, m, tid, a.steps, a.max_halvings, w);
+    const int hc = w.hc, head = w.head;
     CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) {
         const int e = c * N + i;
         gx_[e] = X[e]; gg_[e] = G[e]; gd_[e] = D[e]; gdx_[e] = DX[e]; gdg_[e] = DG[e];
@@ -326,10 +184,10 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
     })
     if (tid < hc) grho_[tid] = rho[head + tid < m ? head + tid : head + tid - m];
     if (tid == 0) {
-        *gf_ = E; *gdf_ = dE;
+        *gf_ = w.E; *gdf_ = w.dE;
         *gstuck_ = stuck ? 1 : 0;
-        *git_ = it;
-        *ghc_ = hc; *ghalv_ = halv;
+        *git_ = w.it;
+        *ghc_ = hc; *ghalv_ = w.halv;
     }
 }
 

@@ -17,6 +17,7 @@
 // The random-number rule is stated in include/dzo.h; it is the specification and tests/tempering_twin.py replays it.
 #include "dzo_cluster.h"
 #include "dzo_pairwise.h"
+#include "dzo_pcg.h"
 
 #include <cmath>
 #include <new>
@@ -25,41 +26,15 @@ namespace dzo {
 
 constexpr int kTemperMaxN = DZO_TEMPERING_MAX_PARTICLES;
 
-// ------------------------------------------------------------------------------ PCG32 XSH-RR (legacy/PCG.jl:7-22)
-constexpr uint64_t kPcgMul = 0x5851F42D4C957F2DULL, kPcgInc = 0x14057B7EF767814FULL;
-__host__ __device__ __forceinline__ uint64_t pcg_advance(uint64_t s) { return kPcgMul * s + kPcgInc; }
-__device__ __forceinline__ uint32_t pcg_extract(uint64_t s) {
-    const uint32_t v = (uint32_t)(((s >> 18) ^ s) >> 27);
-    const uint32_t r = (uint32_t)(s >> 59);
-    return (v >> r) | (v << ((32u - r) & 31u));             // bitrotate(v, -r)
-}
-__device__ __forceinline__ uint32_t pcg_draw(uint64_t &s) {
-    const uint32_t v = pcg_extract(s);
-    s = pcg_advance(s);
-    return v;
-}
-
-constexpr double kTwoM32 = 2.3283064365386962890625e-10;    // 2^-32
-
-template <typename T> __device__ __forceinline__ T mc_exp(T v);
-template <> __device__ __forceinline__ double mc_exp<double>(double v) { return ::exp(v); }
-template <> __device__ __forceinline__ float mc_exp<float>(float v) { return ::expf(v); }
-
 template <typename T> struct McDraws { int j; T nx, ny, nz, u; };
 
-// the six draws of one Monte Carlo step (include/dzo.h)
+// the six draws of one Monte Carlo step (include/dzo.h); the generator and the Box-Muller formulas are dzo_pcg.h's
 template <typename T> __device__ __forceinline__ McDraws<T> mc_draw(uint64_t &s, int N) {
     const uint32_t d0 = pcg_draw(s), d1 = pcg_draw(s), d2 = pcg_draw(s), d3 = pcg_draw(s), d4 = pcg_draw(s), d5 = pcg_draw(s);
     McDraws<T> d;
     d.j = (int)(((uint64_t)d0 * (uint64_t)N) >> 32);
-    const double u1 = ((double)d1 + 0.5) * kTwoM32, u2 = ((double)d2 + 0.5) * kTwoM32;   // exact
-    const double u3 = ((double)d3 + 0.5) * kTwoM32, u4 = ((double)d4 + 0.5) * kTwoM32;
-    const double r1 = ::sqrt(-2.0 * ::log(u1)), r2 = ::sqrt(-2.0 * ::log(u3));
-    const double c1 = ::cospi(2.0 * u2), s1 = ::sinpi(2.0 * u2), c2 = ::cospi(2.0 * u4);
-    d.nx = (T)(r1 * c1);
-    d.ny = (T)(r1 * s1);
-    d.nz = (T)(r2 * c2);
-    d.u = (T)((double)d5 * kTwoM32);
+    pcg_normals<T>(d1, d2, d3, d4, d.nx, d.ny, d.nz);
+    d.u = pcg_uniform<T>(d5);
     return d;
 }
 
@@ -121,10 +96,7 @@ template <typename T> struct McEnd {
         fac = pw_pin(a.fac);
     }
     __device__ __forceinline__ void store(T radius, int64_t acc, int64_t rej, uint64_t s) const {
-        T r = radius;
-        if (3 * acc < rej) r = radius / fac;
-        else if (3 * acc > rej) { const T v = radius * fac; r = v < T(1) ? v : T(1); }
-        *radius_out = r;
+        *radius_out = mc_adapted_radius<T>(radius, acc, rej, fac);
         *rng_out = s;
         *acc_out = acc;
         *rej_out = rej;
@@ -284,7 +256,7 @@ __global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd,
     cl_block_sum2(sa, sb, red);
     const T energy_a = (T)(0.5 * sa), energy_b = (T)(0.5 * sb);
     const T log_prob = (energy_a - energy_b) * (inv_temps[ka] - inv_temps[kb]);
-    const T u = (T)((double)pcg_draw(s) * kTwoM32);          // always consumed
+    const T u = pcg_uniform<T>(pcg_draw(s));                  // always consumed
     const bool accept = log_prob >= T(0) || u <= mc_exp<T>(log_prob);
     if (tid == 0) {
         rng[ka] = s;
@@ -367,13 +339,6 @@ static void tp_free(dzo_tempering_s *h) {
 }
 
 static int32_t tp_alloc(void **p, size_t bytes) { return device_alloc(p, bytes, "the tempering state", false); }
-
-// _fac = ten successive square roots of two in T (:21-24); the host's sqrt is correctly rounded
-template <typename T> static double tp_fac() {
-    T f = T(2);
-    for (int i = 0; i < 10; ++i) f = std::sqrt(f);
-    return (double)f;
-}
 
 template <typename T> static int32_t tp_temper_t(dzo_tempering_s *h, hipStream_t s, int64_t num_steps, void *energies, int64_t ld) {
     TemperArgs<T> a;
@@ -469,7 +434,7 @@ int32_t dzo_tempering_create(int32_t radial, int64_t n_particles, int64_t n_repl
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     h->device = c.device; h->dtype = dtype; h->N = (int)n_particles; h->R = n_replicas; h->replicas = replicas_dev;
     h->constraining_radius = constraining_radius;
-    h->fac = dtype == DZO_F64 ? tp_fac<double>() : tp_fac<float>();
+    h->fac = dtype == DZO_F64 ? mc_fac<double>() : mc_fac<float>();
     const size_t es = dtype_size(dtype), R = (size_t)n_replicas;
     int32_t rc = DZO_OK;
     if ((rc = tp_alloc(&h->inv_temps, es * R)) || (rc = tp_alloc(&h->radii, es * R)) || (rc = tp_alloc(&h->analysis, es * 5 * R)) ||

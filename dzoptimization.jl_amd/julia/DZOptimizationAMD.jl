@@ -32,7 +32,8 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
        BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!,
        pairwise_batch_hvp!, pairwise_batch_hessian!, symmetric_batch_eigen!, symeig_plan, hessian_spectrum,
-       ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array
+       ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array,
+       BasinHopping, hop!, set_record!, set_array!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -504,6 +505,104 @@ function hessian_spectrum(points::HipVector{T}, n_particles::Integer) where {T}
     sweeps = symmetric_batch_eigen!(eigenvalues, hessians, n)
     any(<(0), sweeps) && error("hessian_spectrum: no convergence in instances $(findall(<(0), sweeps))")
     return Float64.(reshape(Array(eigenvalues), n, batch))
+end
+
+################################################################################ batched basin hopping
+# (not exercised in the build container either; the Python class BasinHopping binds the same entry points and IS tested)
+#
+# Basin hopping (Wales & Doye 1997; include/dzo.h states the rule) of `batch` walkers at once: `hop!(bh, k)` runs k hops --
+# perturb every particle, quench with the batched L-BFGS, Metropolis test on the quenched energies -- of every walker at the
+# walker's own pace.  `points` is aliased and always holds the walkers' current minima.
+
+# `what` of read_array / set_array! (DZO_BASIN_HOPPING_* of include/dzo.h)
+const BASIN_HOPPING_POINTS, BASIN_HOPPING_ENERGIES, BASIN_HOPPING_BEST_POINTS, BASIN_HOPPING_BEST_ENERGIES, BASIN_HOPPING_RADII,
+      BASIN_HOPPING_INV_TEMPS, BASIN_HOPPING_NUM_ACCEPT, BASIN_HOPPING_NUM_REJECT, BASIN_HOPPING_RNG_STATES, BASIN_HOPPING_HOP_COUNTS,
+      BASIN_HOPPING_QUENCH_ITERATIONS, BASIN_HOPPING_QUENCH_UNFINISHED, BASIN_HOPPING_REC_NORMALS, BASIN_HOPPING_REC_UNIFORM,
+      BASIN_HOPPING_REC_TRIAL_ENERGY, BASIN_HOPPING_REC_QUENCH_ITERATIONS, BASIN_HOPPING_REC_CODE = 0:16
+
+mutable struct BasinHopping{T}
+    handle::Ptr{Cvoid}
+    points::HipVector{T}
+    n_particles::Int
+    batch::Int
+    record_capacity::Int
+end
+
+"""`BasinHopping(lj_energy, points, n_particles, inverse_temperatures, perturbation_radii, constraining_radius;
+initial_step_length=0.01, history_length=10, quench_steps=400, seed=0)`.  Does not wait for the quench of `points`."""
+function BasinHopping(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, inverse_temperatures::AbstractVector,
+                      perturbation_radii::AbstractVector, constraining_radius::Real; initial_step_length::Real=0.01,
+                      history_length::Integer=10, quench_steps::Integer=400, seed::Integer=0) where {T}
+    ensure_init()
+    batch = length(inverse_temperatures)
+    @assert length(perturbation_radii) == batch
+    @assert length(points) == 3 * n_particles * batch
+    beta = Vector{Cdouble}(inverse_temperatures); radii = Vector{Cdouble}(perturbation_radii)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_basin_hopping_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cint, Cint, UInt64, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, beta, radii, Float64(constraining_radius),
+                Float64(initial_step_length), history_length, quench_steps, UInt64(seed), h))
+    bh = BasinHopping{T}(h[], points, n_particles, batch, 0)
+    finalizer(bh) do w
+        w.handle != C_NULL && ccall((:dzo_basin_hopping_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return bh
+end
+
+"""The bound on the halvings of one quench step (default 4096)."""
+set_max_halvings!(bh::BasinHopping, max_halvings::Integer) =
+    (check(ccall((:dzo_basin_hopping_set_max_halvings, libdzo), Cint, (Ptr{Cvoid}, Int64), bh.handle, max_halvings)); bh)
+
+"""`hop!(bh, num_hops; adapt=true, hops_per_launch=8, wait=true)`: `cld(num_hops, hops_per_launch)` launches; the radii are
+adapted (scripts/MonteCarlo.jl:77-81) at the end of the last one when `adapt` is set."""
+function hop!(bh::BasinHopping, num_hops::Integer; adapt::Bool=true, hops_per_launch::Integer=8, wait::Bool=true)
+    done = 0
+    while done < num_hops
+        k = min(hops_per_launch, num_hops - done)
+        done += k
+        check(ccall((:dzo_basin_hopping_hop, libdzo), Cint, (Ptr{Cvoid}, Int64, Cint), bh.handle, k, (adapt && done == num_hops) ? 1 : 0))
+    end
+    wait && synchronize()
+    return bh
+end
+
+"""Record the draws and decisions of the hop calls that follow, up to `capacity_hops` hops per launch; 0 switches it off."""
+function set_record!(bh::BasinHopping, capacity_hops::Integer)
+    check(ccall((:dzo_basin_hopping_set_record, libdzo), Cint, (Ptr{Cvoid}, Int64), bh.handle, capacity_hops))
+    bh.record_capacity = capacity_hops
+    return bh
+end
+
+"""`read_array(bh, what)`: a blocking host copy of one of the BASIN_HOPPING_* arrays, in its own element type, the walker as
+the last dimension."""
+function read_array(bh::BasinHopping{T}, what::Integer) where {T}
+    n, b, cap = bh.n_particles, bh.batch, bh.record_capacity
+    r = what in (BASIN_HOPPING_POINTS, BASIN_HOPPING_BEST_POINTS) ? Array{T}(undef, 3 * n, b) :
+        what in (BASIN_HOPPING_ENERGIES, BASIN_HOPPING_BEST_ENERGIES, BASIN_HOPPING_RADII, BASIN_HOPPING_INV_TEMPS) ? Vector{T}(undef, b) :
+        what == BASIN_HOPPING_RNG_STATES ? Vector{UInt64}(undef, b) :
+        what == BASIN_HOPPING_REC_NORMALS ? Array{T}(undef, 3, n, cap, b) :
+        what in (BASIN_HOPPING_REC_UNIFORM, BASIN_HOPPING_REC_TRIAL_ENERGY) ? Array{T}(undef, cap, b) :
+        what == BASIN_HOPPING_REC_QUENCH_ITERATIONS ? Array{Int32}(undef, cap, b) :
+        what == BASIN_HOPPING_REC_CODE ? Array{Int8}(undef, cap, b) : Vector{Int64}(undef, b)
+    check(ccall((:dzo_basin_hopping_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), bh.handle, what, r))
+    return r
+end
+
+"""`set_array!(bh, what, values)`: BASIN_HOPPING_RADII (a vector of T) or BASIN_HOPPING_RNG_STATES (of UInt64); blocks."""
+function set_array!(bh::BasinHopping{T}, what::Integer, values::AbstractVector) where {T}
+    v = what == BASIN_HOPPING_RNG_STATES ? Vector{UInt64}(values) : Vector{T}(values)
+    @assert length(v) == bh.batch
+    check(ccall((:dzo_basin_hopping_set, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), bh.handle, what, v))
+    return bh
+end
+
+"""Device address of one of the BASIN_HOPPING_* arrays (no wait)."""
+function array_pointer(bh::BasinHopping, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_basin_hopping_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), bh.handle, what, p))
+    return p[]
 end
 
 ################################################################################ batched eigenvector following

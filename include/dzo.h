@@ -397,6 +397,97 @@ int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, 
                                            const void *points_dev, void *energies_dev, void *gradients_dev);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched basin hopping over Lennard-Jones clusters (Wales & Doye 1997): Monte Carlo over the QUENCHED landscape, the
+ * composition of the tempering move (scripts/MonteCarlo.jl:49-55, applied to every particle), the quench above
+ * (src/DZOptimization.jl:321-509) and the Metropolis test (scripts/MonteCarlo.jl:63-70) on the quenched energies.  Each walker
+ * is an instance of the batch.  One launch runs num_hops hops of EVERY walker at the walker's own pace; nothing crosses the
+ * host between hops, and no walker waits for another's quench.
+ *
+ * Layout.  points_dev is the quench's (3N, batch): walker b at element 3N b, [x(0..N) | y | z].  The handle ALIASES it; it
+ * always holds the walkers' current minima.
+ *
+ * Launch shapes.  n_particles <= 64: one wave per walker, lane i holds particle i; current minimum and quench state in
+ * registers, the history ring in LDS.  65 .. 1024 (DZO_BASIN_HOPPING_MAX_PARTICLES): one 256-thread block per walker; the five
+ * quench vectors plus the current minimum in LDS, the ring in LDS where (2 history_length + 6) 3N elements and the scalars
+ * (16 history_length + 64 bytes) fit 159 KiB, else in device memory.  More: DZO_ERR_UNSUPPORTED.
+ *
+ * THE SPECIFICATION of what create and a hop compute.
+ *   create   rounds inverse_temperatures and perturbation_radii to T and seeds walker b's PCG32 stream as tempering does:
+ *            state = advance(0x14057B7EF767814F + base_seed + b).  It then enqueues the quench (below) of the caller's points.
+ *            That quench consumes no draws, is always kept, and sets ENERGIES and BEST_*; it is not counted in
+ *            QUENCH_ITERATIONS / QUENCH_UNFINISHED.  create does not wait for it.
+ *   a hop    of walker b starts from stream state s and always consumes exactly 4N + 1 draws, whatever it decides: the
+ *            state afterwards is pcg_jump(s, 4N + 1), s' = A_k s + C_k (the LCG skip).
+ *            Particle i takes draws 4i .. 4i+3 as d1 .. d4 of the tempering rule and makes n_x, n_y, n_z by its formulas: fp64
+ *            Box-Muller, each normal rounded to T, the fourth normal unused.  Draw 4N is the acceptance uniform
+ *            u = d 2^-32, rounded to T.
+ *            The trial coordinate is old + radius * n: a product and a sum in T.  A particle whose trial position fails
+ *            x^2 + y^2 + z^2 < R^2 (in T, left to right; R = constraining_radius rounded to T) keeps its old position in the
+ *            trial.
+ *   quench   is exactly dzo_lbfgs_batch_create on the trial (initial_step_length, history_length) followed by
+ *            dzo_lbfgs_batch_step(quench_steps) under the handle's max_halvings: the quenched point, its energy E_q, the
+ *            iteration count and is_stuck have the bits of those calls.
+ *   decision delta = E_q - E in T.  Accept iff E_q is finite and (delta <= 0 || u <= exp(-beta * delta)), exp in T.  On
+ *            acceptance the quenched point and E_q become the walker's.  BEST_* is replaced whenever E_q is finite and
+ *            E_q < BEST_ENERGY, accepted or not.  A start whose energy is not a number (two coincident particles) keeps
+ *            that energy: every comparison with it is false, so no hop is accepted and BEST_* never changes; a quench
+ *            that ends at a non-finite energy is code 2.
+ *   adapt    when adapt != 0, at the end of the call the radius follows scripts/MonteCarlo.jl:77-81 on this call's counts,
+ *            with the same _fac (ten successive square roots of 2 in T) and the same cap of 1.  When adapt == 0 the radii
+ *            stay.
+ * Reproducibility.  No floating-point atomics.  A walker computes the same bits alone or anywhere in any batch.  hop(a)
+ * followed by hop(b) equals hop(a + b) when adapt == 0.
+ *
+ * Errors follow the quench and tempering entries: unknown radial or dtype, sizes < 1, quench_steps < 1, history_length < 1,
+ * a constraining_radius that is not > 0, num_hops < 0, null pointers, a record capacity smaller than num_hops while recording
+ * DZO_ERR_INVALID; n_particles > 1024 or history_length > 32 DZO_ERR_UNSUPPORTED; a host pointer for points_dev, or
+ * initial_step_length <= 0, DZO_ERR_ASSERT (:363-364, :380).  create and hop enqueue on the library's stream and do not
+ * block; read, set and set_record do.  A launch lasts num_hops quenches of its slowest walker: keep num_hops small (a
+ * handful) and call again, so that the device stays responsive.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_BASIN_HOPPING_MAX_PARTICLES 1024
+/* `what` of get_ptr / read / set: element type and shape (T = the handle's element type) */
+#define DZO_BASIN_HOPPING_POINTS 0                  /* T, 3N batch: the caller's array, the current minima */
+#define DZO_BASIN_HOPPING_ENERGIES 1                /* T, batch: their energies */
+#define DZO_BASIN_HOPPING_BEST_POINTS 2             /* T, 3N batch, handle-owned: the lowest minimum each walker has quenched to */
+#define DZO_BASIN_HOPPING_BEST_ENERGIES 3           /* T, batch */
+#define DZO_BASIN_HOPPING_RADII 4                   /* T, batch: perturbation radii; settable */
+#define DZO_BASIN_HOPPING_INV_TEMPS 5               /* T, batch */
+#define DZO_BASIN_HOPPING_NUM_ACCEPT 6              /* int64, batch: of the last hop call */
+#define DZO_BASIN_HOPPING_NUM_REJECT 7              /* int64, batch: of the last hop call (codes 0 and 2) */
+#define DZO_BASIN_HOPPING_RNG_STATES 8              /* uint64, batch: the PCG32 states; settable (checkpoint / resume) */
+#define DZO_BASIN_HOPPING_HOP_COUNTS 9              /* int64, batch: hops since create */
+#define DZO_BASIN_HOPPING_QUENCH_ITERATIONS 10      /* int64, batch: L-BFGS iterations of all hops since create */
+#define DZO_BASIN_HOPPING_QUENCH_UNFINISHED 11      /* int64, batch: quenches of hops that ended not stuck */
+#define DZO_BASIN_HOPPING_REC_NORMALS 12            /* T, (3, N, capacity, batch): n_x, n_y, n_z of particle p of hop i at [3 (p + N (i + capacity b)) + c] */
+#define DZO_BASIN_HOPPING_REC_UNIFORM 13            /* T, (capacity, batch): the acceptance uniform */
+#define DZO_BASIN_HOPPING_REC_TRIAL_ENERGY 14       /* T, (capacity, batch): E_q */
+#define DZO_BASIN_HOPPING_REC_QUENCH_ITERATIONS 15  /* int32, (capacity, batch) */
+#define DZO_BASIN_HOPPING_REC_CODE 16               /* int8, (capacity, batch): 0 rejected by the Metropolis test, 1 accepted, 2 rejected because the quenched energy is not finite */
+typedef struct dzo_basin_hopping_s *dzo_basin_hopping_t;
+/* inverse_temperatures and perturbation_radii are HOST arrays of batch doubles.  constraining_radius > 0, may be infinite. */
+int32_t dzo_basin_hopping_create(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                                 const double *inverse_temperatures, const double *perturbation_radii,
+                                 double constraining_radius, double initial_step_length, int32_t history_length,
+                                 int32_t quench_steps, uint64_t base_seed, dzo_basin_hopping_t *out);
+int32_t dzo_basin_hopping_destroy(dzo_basin_hopping_t h);
+/* the bound on the halvings of one quench step, as dzo_lbfgs_batch_set_max_halvings (default 4096); at least 1 */
+int32_t dzo_basin_hopping_set_max_halvings(dzo_basin_hopping_t h, int64_t max_halvings);
+/* num_hops hops of every walker, one launch; enqueues, does not block */
+int32_t dzo_basin_hopping_hop(dzo_basin_hopping_t h, int64_t num_hops, int32_t adapt);
+/* Record the draws and decisions of the hop calls that follow (up to capacity_hops hops per call; longer calls are
+ * DZO_ERR_INVALID while recording); 0 switches recording off.  Every call overwrites the record from hop 0. */
+int32_t dzo_basin_hopping_set_record(dzo_basin_hopping_t h, int64_t capacity_hops);
+/* device address of an array above (no wait) / a blocking copy of it to host memory / host memory copied into it (blocking;
+ * DZO_BASIN_HOPPING_RADII and DZO_BASIN_HOPPING_RNG_STATES only).  Host arrays are in the array's own element type.
+ * Checkpoint / resume: read POINTS, RADII and RNG_STATES; create a handle at those points and set the two arrays.  A walker
+ * goes on identically where the constructor's quench leaves its point as it is (a minimum found in fp64 does; in fp32 a stuck
+ * point can still move by a decrease at rounding level, and the walker goes on from there). */
+int32_t dzo_basin_hopping_get_ptr(dzo_basin_hopping_t h, int32_t what, void **ptr_dev);
+int32_t dzo_basin_hopping_read(dzo_basin_hopping_t h, int32_t what, void *out_host);
+int32_t dzo_basin_hopping_set(dzo_basin_hopping_t h, int32_t what, const void *in_host);
+
+/* ---------------------------------------------------------------------------------------
  * Batched AdGDOptimizer over many small Lennard-Jones clusters (src/DZOptimization.jl:179-312 with constraint_function! =
  * nothing, objective = the pairwise radial energy above): the sibling of dzo_lbfgs_batch_* without a history ring.  One
  * launch runs `steps` calls of step!() (:274-312) of EVERY instance; nothing crosses the host between steps or trials.
