@@ -204,6 +204,7 @@ ABI = {
     "dzo_pairwise_batch_hessian": [_i32, _i64, _i64, _i32, _vp, _vp],
     "dzo_symmetric_batch_eigen": [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32],
     "dzo_symeig_plan": [_i64, _i32, _P(_i32), _P(_i64), _P(_i64)],
+    "dzo_pairwise_batch_lowest_mode": [_i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _dbl, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
     "dzo_modefollow_batch_apply": [_i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp],
     "dzo_modefollow_batch_create": [_i32, _i64, _i64, _i32, _vp, _i32, _dbl, _dbl, _dbl, _P(_vp)], "dzo_modefollow_batch_destroy": [_vp],
@@ -982,6 +983,50 @@ def hessian_spectrum(points, n_particles, vectors=False, radial=RADIAL_LENNARD_J
         raise DzoError(6, "hessian_spectrum: no convergence in instances %s" % np.flatnonzero(sweeps < 0).tolist())
     ev = w.to_host().reshape(batch, 3 * n).astype(np.float64)
     return (ev, v.to_host().reshape(batch, 3 * n, 3 * n)) if vectors else ev
+
+
+# ------------------------------------------------------------------------------ batched lowest Hessian mode (Lanczos)
+LOWMODE_MAX_PARTICLES = 1024
+LOWMODE_MAX_KRYLOV = 32
+LOWMODE_CONVERGED, LOWMODE_UNFINISHED, LOWMODE_FAILED = 0, 1, 2
+# relative residual an instance is asked to reach by default: 16 times the smallest the CPU twin of the iteration still reaches
+# within 20 cycles on the 38-atom octahedron and on a 257-atom cluster (DESIGN.md has the two numbers per element type)
+LOWMODE_DEFAULT_RES_TOL = {np.dtype(np.float64): 4.3e-15, np.dtype(np.float32): 7.0e-7}
+
+
+class LowestModes:
+    """What ``lowest_modes`` returns: ``eigenvalues`` (host, ``(batch,)`` in the element type), ``vectors`` (a DeviceArray
+    ``(batch, 3N)``, unit norm), ``residuals`` (host, fp64), ``status``, ``cycles`` and ``products`` (host, int32)."""
+
+    def __init__(self, eigenvalues, vectors, residuals, info):
+        self.eigenvalues, self.vectors, self.residuals = eigenvalues, vectors, residuals
+        self.status, self.cycles, self.products = info[:, 0].copy(), info[:, 1].copy(), info[:, 2].copy()
+
+
+def lowest_modes(points, n_particles, project_rigid=True, krylov=32, max_cycles=40, res_tol=None, start=None, seed=0,
+                 radial=RADIAL_LENNARD_JONES):
+    """The lowest eigenpair of the Hessian of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b
+    ``[x | y | z]``) by restarted Lanczos inside one launch (``dzo_pairwise_batch_lowest_mode``, include/dzo.h): Hessian-vector
+    products only, up to 1024 particles.  With ``project_rigid`` net translation and rotation are projected out, so that the
+    eigenvalue is the lowest vibration (a minimum has it positive, a saddle negative); without, it is the lowest eigenvalue
+    of the Hessian itself.  ``krylov`` Lanczos vectors per cycle (2 .. 32), at most ``max_cycles`` cycles; an instance is
+    CONVERGED when the residual of its Ritz pair is at most ``res_tol`` times the largest eigenvalue estimate seen
+    (None: ``LOWMODE_DEFAULT_RES_TOL`` of the element type).  ``start``: a DeviceArray of start vectors laid out like
+    ``points``, or None to draw them in the kernel from ``seed``.  Returns a ``LowestModes``."""
+    n = int(n_particles)
+    batch = points.size // (3 * n) if n > 0 else 0
+    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    assert start is None or (start.size == points.size and start.dtype == points.dtype), "start must be laid out like points"
+    if res_tol is None:
+        res_tol = LOWMODE_DEFAULT_RES_TOL[np.dtype(points.dtype)]
+    w = DeviceArray((batch,), points.dtype)
+    v = DeviceArray((batch, 3 * n), points.dtype)
+    r = DeviceArray((batch,), np.float64)
+    info = DeviceArray((batch, 3), np.int32)
+    _check(lib().dzo_pairwise_batch_lowest_mode(radial, n, batch, _dt(points.dtype), points.ptr, 1 if project_rigid else 0, int(krylov),
+                                                int(max_cycles), float(res_tol), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                start.ptr if start is not None else None, w.ptr, v.ptr, r.ptr, info.ptr))
+    return LowestModes(w.to_host(), v, r.to_host(), info.to_host().reshape(batch, 3))
 
 
 # ------------------------------------------------------------------------------ batched eigenvector following

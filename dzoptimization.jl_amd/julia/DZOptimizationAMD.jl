@@ -32,6 +32,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
        BatchedLBFGSOptimizer, BatchedAdGDOptimizer, current_step_sizes, count_active, objective_values, iteration_counts, stuck_flags, quench, pairwise_batch_energy_gradient!,
        pairwise_batch_hvp!, pairwise_batch_hessian!, symmetric_batch_eigen!, symeig_plan, hessian_spectrum,
+       lowest_modes, LOWMODE_CONVERGED, LOWMODE_UNFINISHED, LOWMODE_FAILED,
        ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array,
        BasinHopping, hop!, set_record!, set_array!
 
@@ -505,6 +506,30 @@ function hessian_spectrum(points::HipVector{T}, n_particles::Integer) where {T}
     sweeps = symmetric_batch_eigen!(eigenvalues, hessians, n)
     any(<(0), sweeps) && error("hessian_spectrum: no convergence in instances $(findall(<(0), sweeps))")
     return Float64.(reshape(Array(eigenvalues), n, batch))
+end
+
+const LOWMODE_CONVERGED, LOWMODE_UNFINISHED, LOWMODE_FAILED = Int32(0), Int32(1), Int32(2)
+
+"""`lowest_modes(points, n_particles; project_rigid=true, krylov=32, max_cycles=40, res_tol=nothing, start=nothing, seed=0)`:
+the lowest eigenpair of the Hessian of every instance by restarted Lanczos inside one launch (include/dzo.h, "Batched lowest
+Hessian mode"): Hessian-vector products only, up to 1024 particles.  `project_rigid`: net translation and rotation are projected
+out.  `res_tol === nothing`: 4.3e-15 for Float64, 7.0e-7 for Float32 (DESIGN.md).  `start`: start vectors laid out like `points`,
+or `nothing` to draw them in the kernel from `seed`.  Returns `(eigenvalues::Vector{T}, vectors::HipVector{T}, residuals::Vector{Float64},
+status, cycles, products)`, the last three `Vector{Int32}`.  Blocks."""
+function lowest_modes(points::HipVector{T}, n_particles::Integer; project_rigid::Bool=true, krylov::Integer=32, max_cycles::Integer=40,
+                      res_tol::Union{Nothing,Real}=nothing, start::Union{Nothing,HipVector{T}}=nothing, seed::Integer=0) where {T}
+    batch = div(length(points), 3 * n_particles)
+    tol = res_tol === nothing ? (T === Float64 ? 4.3e-15 : 7.0e-7) : Float64(res_tol)
+    eigenvalues = HipVector{T}(undef, batch)
+    vectors = HipVector{T}(undef, 3 * n_particles * batch)
+    residuals = HipVector{Float64}(undef, batch)
+    info = HipVector{Float32}(undef, 3 * batch)              # four bytes per record: read back as Int32
+    check(ccall((:dzo_pairwise_batch_lowest_mode, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cint, Cint, Cint, Cdouble, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, project_rigid ? 1 : 0, krylov, max_cycles, tol,
+                UInt64(seed), start === nothing ? C_NULL : start.ptr, eigenvalues.ptr, vectors.ptr, residuals.ptr, info.ptr))
+    records = reshape(collect(reinterpret(Int32, Array(info))), 3, batch)
+    return Array(eigenvalues), vectors, Array(residuals), records[1, :], records[2, :], records[3, :]
 end
 
 ################################################################################ batched basin hopping

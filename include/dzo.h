@@ -764,6 +764,90 @@ int32_t dzo_modefollow_batch_get_ptr(dzo_modefollow_batch_t h, int32_t what, voi
 int32_t dzo_modefollow_batch_read(dzo_modefollow_batch_t h, int32_t what, void *out_host);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched lowest Hessian mode of many small Lennard-Jones clusters by restarted Lanczos inside ONE launch: "is this point a
+ * minimum, and if not, which way is down?" for up to DZO_LOWMODE_MAX_PARTICLES = 1024 particles, from Hessian-vector products
+ * alone -- the consumer of accelerated_pairwise_radial_hvp! (src/ExampleFunctions.jl:427-468).  No dense Hessian is formed.
+ * Nothing in the reference iterates on that product: this block is the specification.  Stateless and blocking; each instance
+ * runs at its own pace inside the launch.
+ *
+ * Layout.  points, start and vectors are (3N, batch): instance b at element 3N b, [x | y | z] -- the layout of every cluster
+ * unit.  eigenvalues are T, (batch); residuals fp64, (batch), may be NULL; info is int32, (3, batch), may be NULL: status at
+ * 3 b, cycles at 3 b + 1, products at 3 b + 2.  start_dev may be NULL: the start is then drawn in the kernel.
+ *
+ * Launch shapes.  n_particles <= 64: one wave per instance, lane i holds particle i and its entries of the current vector in
+ * registers, the Lanczos basis (3 * 64 * K elements) lives in dynamic LDS.  65 .. 1024: one 256-thread block per instance,
+ * thread t owns particles t + 256 q, point and current vector staged in LDS, the basis in a per-call device workspace of
+ * 3N * K * batch elements (a thread reads back only what it wrote itself), freed before the call returns.
+ *
+ * Arithmetic (T = the element type; n = 3N; every operation rounded once, no contraction, IEEE division and square root;
+ * "fp64" names the operations done in double precision on values converted exactly from T).
+ *  a. Sums.  Every sum over the particles is in fp64 in THE ORDER OF THE SUMS, which depends on N only: N <= 64: lane i holds
+ *     the term of particle i (+0 beyond N), added by the xor tree with offsets 32, 16, 8, 4, 2, 1.  Above: thread t adds the
+ *     terms of particles t, t + 256, ... in that order from +0 (+0 for a particle beyond N), the 64 values of a wave are
+ *     added by the same tree, the four wave sums are added in wave order from +0.  (For N <= 64 the single wave sum is added
+ *     to +0 likewise.)  A dot a.b has the term a_x b_x, then fma(a_y, b_y, .), then fma(a_z, b_z, .) per particle, as in
+ *     dzo_pairwise_batch_hvp.
+ *  b. Product.  H v is dzo_pairwise_batch_hvp's products of the point with the direction v: the same pair term, the same row
+ *     loop, the same order, hence the same bits.
+ *  c. Projector (project_rigid != 0; otherwise P is the identity and steps c and d are skipped).  Once per instance, all fp64,
+ *     plain products and sums: centroid c_a = (sum_i r_a,i) / N; rho_i = r_i - c; the unit-mass inertia tensor
+ *     Gxx = sum(rho_y rho_y + rho_z rho_z), Gyy = sum(rho_x rho_x + rho_z rho_z), Gzz = sum(rho_x rho_x + rho_y rho_y),
+ *     Gxy = -sum(rho_x rho_y), Gxz = -sum(rho_x rho_z), Gyz = -sum(rho_y rho_z).  Cofactors A00 = Gyy Gzz - Gyz Gyz,
+ *     A01 = Gxz Gyz - Gxy Gzz, A02 = Gxy Gyz - Gxz Gyy, A11 = Gxx Gzz - Gxz Gxz, A12 = Gxy Gxz - Gxx Gyz,
+ *     A22 = Gxx Gyy - Gxy Gxy; det = Gxx A00 + Gxy A01 + Gxz A02 (left to right); tr = Gxx + Gyy + Gzz.  The instance is
+ *     FAILED (cycles = products = 0, eigenvalue and residual NaN) unless det > 2^-36 (tr tr) tr, a test that a singular G
+ *     (collinear particles: det is rounding noise, some 2^-50 tr^3) and a non-finite one both fail.  Otherwise I_ab = A_ab / det.
+ *  d. P v (result in T): m_a = (sum_i v_a,i) / N; L = sum_i rho_i x v_i, per particle Lx: rho_y v_z - rho_z v_y, Ly:
+ *     rho_z v_x - rho_x v_z, Lz: rho_x v_y - rho_y v_x (two products and a difference); omega_a = I_ax Lx + I_ay Ly + I_az Lz
+ *     (left to right); (P v)_x,i = T((v_x,i - m_x) - (omega_y rho_z,i - omega_z rho_y,i)), y: omega_z rho_x - omega_x rho_z,
+ *     z: omega_x rho_y - omega_y rho_x.
+ *  e. normalise(v): s = sqrt(v.v) (fp64), r = 1 / s, v_e = T(v_e r).  The operator is A v = P (H v) on vectors that are
+ *     themselves P of something: A = P H P up to the rounding of the projection.
+ *  f. Start.  u = start[b], or drawn: particle i takes draws 4 i .. 4 i + 3 of the PCG32 stream whose state after seeding is
+ *     advance(0x14057B7EF767814F + base_seed + b) (the rule of basin hopping) as d1 .. d4 of the tempering rule: three
+ *     normals (x, y, z) by Box-Muller in fp64, each rounded to T.  u = P u, then normalise; s zero or non-finite: FAILED.
+ *  g. A cycle on the unit vector u = q_0, with K = min(krylov, dimension of the range of P) (n - 6 with project_rigid, n
+ *     without), for j = 0 .. K - 1:
+ *       w = A q_j (products += 1); h_k = q_k.w for k = 0 .. j, all from this w (CLASSICAL Gram-Schmidt); alpha_j = h_j.
+ *       j = K - 1 > 0: the cycle ends here.
+ *       w_e = T(((w_e - h_0 q_0,e) - h_1 q_1,e) - ...), fp64, one product and one difference per k.
+ *       j = 0: alpha_1 = alpha_0, beta_1 = sqrt(w.w): the Rayleigh quotient of u and the norm of w - alpha_1 u, its residual.
+ *         scale = max(scale, |alpha_1|) (scale starts at 0; a NaN never enters).  beta_1 <= res_tol scale: CONVERGED with
+ *         eigenvalue T(alpha_1), vector u, residual beta_1.  Otherwise, in cycle max_cycles: UNFINISHED with the same three.
+ *       A second pass: h_k = q_k.w, w updated as above.  beta_j = sqrt(w.w); unless beta_j > 0 the cycle ends with j + 1 steps
+ *       (an exact zero or a NaN).  w_e = T(w_e (1 / beta_j)).
+ *       Clean-up, at most four passes: w = P w; h_k = q_k.w and the update as above; s = sqrt(w.w); unless s > 0 the cycle
+ *       ends with j + 1 steps; w_e = T(w_e (1 / s)); a pass with s > 0.7 is the last.  (Once the Krylov space has closed, w is
+ *       amplified rounding noise and carries rigid-body components: without this pass the 13-atom icosahedron never
+ *       converges.)  q_(j+1) = w.
+ *  h. Ritz pair of the k x k tridiagonal (k = the steps of the cycle; diagonal alpha_0 .. alpha_(k-1), off-diagonal
+ *     beta_0 .. beta_(k-2)) in fp64: cyclic Jacobi by the round order, angles and apply rules of dzo_symmetric_batch_eigen's
+ *     items 3-5 with T = double and V = I at the start.  At the start of every sweep: off_c = the sum over rows r != c
+ *     ascending of a[r,c]^2 from +0, dia_c = a[c,c]^2; off2 and dia2 are their sums over c by the xor tree of 64 lanes (+0
+ *     beyond k); the iteration ends when off2 <= 2^-104 (off2 + dia2), or after 30 sweeps.  theta = the smallest diagonal
+ *     entry (the lowest index among equals), y its column of V.  scale = max(scale, |theta|).
+ *     u_e = T(((0 + y_0 q_0,e) + y_1 q_1,e) + ...) in fp64; u = P u; normalise; s zero or non-finite: FAILED.  Next cycle.
+ * No floating-point atomics, every output element is written once.  Nothing loops without a bound: at most max_cycles K
+ * products.  An instance computes the same bits alone or anywhere in any batch for a given start vector, drawn or supplied.
+ *
+ * Errors are those of dzo_pairwise_batch_hessian: unknown radial or dtype, sizes < 1, a null points_dev, eigenvalues_dev or
+ * vectors_dev DZO_ERR_INVALID; n_particles > 1024 DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required
+ * DZO_ERR_ASSERT.  krylov outside 2 .. DZO_LOWMODE_MAX_KRYLOV, max_cycles < 1, a negative or non-finite res_tol, project_rigid
+ * with n_particles < 3 DZO_ERR_INVALID; no memory for the workspace DZO_ERR_NOMEM.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_LOWMODE_MAX_PARTICLES 1024
+#define DZO_LOWMODE_MAX_KRYLOV 32
+/* status */
+#define DZO_LOWMODE_CONVERGED 0
+#define DZO_LOWMODE_UNFINISHED 1
+#define DZO_LOWMODE_FAILED 2
+/* the lowest eigenpair of P H P (project_rigid != 0: net translation and rotation removed) or of H at every points[b] */
+int32_t dzo_pairwise_batch_lowest_mode(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype,
+                                       const void *points_dev, int32_t project_rigid, int32_t krylov, int32_t max_cycles,
+                                       double res_tol, uint64_t base_seed, const void *start_dev, void *eigenvalues_dev,
+                                       void *vectors_dev, double *residuals_dev, int32_t *info_dev);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
