@@ -211,6 +211,13 @@ ABI = {
     "dzo_modefollow_batch_set_start_mode": [_vp, _i32], "dzo_modefollow_batch_set_directions": [_vp, _vp],
     "dzo_modefollow_batch_step": [_vp, _i32, _P(_i32)], "dzo_modefollow_batch_count_active": [_vp, _P(_i64)],
     "dzo_modefollow_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_modefollow_batch_read": [_vp, _i32, _vp],
+    "dzo_hybridef_batch_apply": [_i32, _i64, _i64, _i32, _vp, _vp, _vp, _dbl, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp],
+    "dzo_hybridef_batch_create": [_i32, _i64, _i64, _i32, _vp, _vp, _dbl, _i32, _i32, _dbl, _dbl, _i32, _i32, _dbl, _dbl, _dbl, C.c_uint64,
+                                  _P(_vp)],
+    "dzo_hybridef_batch_destroy": [_vp], "dzo_hybridef_batch_set_directions": [_vp, _vp],
+    "dzo_hybridef_batch_step": [_vp, _i32, _P(_i32)], "dzo_hybridef_batch_count_active": [_vp, _P(_i64)],
+    "dzo_hybridef_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_hybridef_batch_read": [_vp, _i32, _vp],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -1188,6 +1195,150 @@ def find_saddles(minima, n_particles, start_mode=0, kick=0.05, grad_tol=1e-10, m
     saddles.set_directions(dirs)
     saddles.run(max_steps)
     return saddles, polished
+
+
+# ------------------------------------------------------------------------------ batched hybrid eigenvector following
+HYBRIDEF_MAX_PARTICLES = 1024
+HYBRIDEF_ACTIVE, HYBRIDEF_CONVERGED, HYBRIDEF_FAILED = 0, 1, 2
+(HYBRIDEF_POINTS, HYBRIDEF_GRADIENTS, HYBRIDEF_ENERGIES, HYBRIDEF_GRMS, HYBRIDEF_STATUS, HYBRIDEF_EIGENVALUES, HYBRIDEF_MODES,
+ HYBRIDEF_MODE_RESIDUALS, HYBRIDEF_PROJECTIONS, HYBRIDEF_UPHILL_STEPS, HYBRIDEF_TANGENT_STEPS, HYBRIDEF_ITERATION_COUNTS, HYBRIDEF_PRODUCTS,
+ HYBRIDEF_EVALUATIONS) = range(14)
+
+
+def hybridef_apply(points, eigenvalues, modes, n_particles, max_step=0.1, tangent_steps=10, tangent_steps_convex=2, tangent_cap=0.05,
+                   tangent_first=0.01, zero_tol=1e-4, grad_tol=0.0, radial=RADIAL_LENNARD_JONES):
+    """``dzo_hybridef_batch_apply``: ONE step of hybrid eigenvector following (include/dzo.h) of every instance from a mode the
+    caller supplies.  ``points`` (DeviceArray, ``3 * n_particles * batch`` elements) is moved in place; ``eigenvalues``
+    ``(batch,)`` and ``modes`` ``(batch, 3N)`` (unit vectors) are DeviceArrays or host arrays, which are uploaded.  Returns a
+    dict of host arrays: ``energies``, ``gradients``, ``projections`` (F), ``uphill_steps`` (h), ``grms``, ``status``,
+    ``tangent_steps``."""
+    n = int(n_particles)
+    n3 = 3 * n
+    batch = points.size // n3 if n > 0 else 0
+    assert points.size == n3 * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    lam, vec = _as_dev(eigenvalues, points.dtype), _as_dev(modes, points.dtype)
+    assert lam.dtype == points.dtype and vec.dtype == points.dtype, "points and modes must have one element type"
+    assert lam.size == batch and vec.size == n3 * batch, "a mode holds one eigenvalue and 3N elements per instance"
+    e, g = DeviceArray(batch, points.dtype), DeviceArray((batch, n3), points.dtype)
+    f, h = DeviceArray(batch, points.dtype), DeviceArray(batch, points.dtype)
+    grms, st, ts = DeviceArray(batch, np.float64), DeviceArray(batch, np.int32), DeviceArray(batch, np.int32)
+    _check(lib().dzo_hybridef_batch_apply(radial, n, batch, _dt(points.dtype), points.ptr, lam.ptr, vec.ptr, float(max_step), int(tangent_steps),
+                                          int(tangent_steps_convex), float(tangent_cap), float(tangent_first), float(zero_tol), float(grad_tol),
+                                          e.ptr, g.ptr, f.ptr, h.ptr, grms.ptr, st.ptr, ts.ptr))
+    return dict(energies=e.to_host(), gradients=g.to_host(), projections=f.to_host(), uphill_steps=h.to_host(), grms=grms.to_host(),
+                status=st.to_host(), tangent_steps=ts.to_host())
+
+
+class HybridModeFollowing(_HandleArrays):
+    """Hybrid eigenvector following (Munro & Wales 1999; include/dzo.h states the step) of many Lennard-Jones clusters at once,
+    up to 1024 particles: a transition-state search from Hessian-vector products and gradients alone.  ``step(k)`` enqueues, k
+    times, the refinement of the lowest mode from the previous step's vector (``krylov`` Lanczos vectors, ``mode_cycles``
+    cycles, stopped early at a relative residual of ``mode_tol``) and the step kernel -- uphill along the mode, then
+    ``tangent_steps`` Barzilai-Borwein gradient steps orthogonal to it (``tangent_steps_convex`` while the mode's eigenvalue is
+    not negative) -- with no host wait in between.  ``points`` is a DeviceArray of ``3 * n_particles * batch`` elements (the
+    tempering replica layout), aliased and moved; ``directions`` ``(batch, 3N)`` are the first modes (None: drawn in the kernel
+    from ``seed``).  An instance ends CONVERGED (``grms <= grad_tol``) or FAILED and is then left alone.  CONVERGED says that
+    the point is stationary; ``eigenvalues < -zero_tol`` says that it is a saddle, and only the spectrum (``hessian_spectrum``,
+    ``hessian_eigenvalues``) tells its index: the method can end on a saddle of higher index."""
+    _prefix = "dzo_hybridef_batch_"
+    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
+
+    def __init__(self, points, n_particles, directions=None, max_step=0.1, tangent_steps=10, tangent_steps_convex=2, tangent_cap=0.05,
+                 tangent_first=0.01, krylov=8, mode_cycles=1, mode_tol=1e-3, zero_tol=1e-4, grad_tol=1e-10, seed=0,
+                 radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.points = points
+        self.dtype = points.dtype
+        self.n_particles = int(n_particles)
+        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
+        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        d = None if directions is None else _as_dev(directions, self.dtype)
+        assert d is None or (d.size == points.size and d.dtype == self.dtype), "directions must be laid out like points"
+        h = C.c_void_p()
+        _check(lib().dzo_hybridef_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, d.ptr if d is not None else None,
+                                               float(max_step), int(tangent_steps), int(tangent_steps_convex), float(tangent_cap),
+                                               float(tangent_first), int(krylov), int(mode_cycles), float(mode_tol), float(zero_tol),
+                                               float(grad_tol), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            lib().dzo_hybridef_batch_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_directions(self, directions):
+        """The mode the next refinement of every instance starts from: a DeviceArray or host array ``(batch, 3N)``."""
+        d = _as_dev(directions, self.dtype)
+        assert d.size == 3 * self.n_particles * self.batch and d.dtype == self.dtype
+        _check(lib().dzo_hybridef_batch_set_directions(self.h, d.ptr))
+        synchronize()                                       # `d` may be a temporary
+
+    def step(self, steps=1, wait=True):
+        """``steps`` steps of every ACTIVE instance.  ``wait=True``: blocks and returns whether no instance is ACTIVE any more;
+        ``wait=False``: enqueues only and returns None."""
+        if not wait:
+            _check(lib().dzo_hybridef_batch_step(self.h, int(steps), None))
+            return None
+        flag = C.c_int32(0)
+        _check(lib().dzo_hybridef_batch_step(self.h, int(steps), C.byref(flag)))
+        return bool(flag.value)
+
+    def run(self, max_steps, steps_per_call=20):
+        """Steps until no instance is ACTIVE, at most ``max_steps`` per instance.  Returns the steps enqueued."""
+        done, taken = self.count_active() == 0, 0
+        while not done and taken < max_steps:
+            k = min(int(steps_per_call), int(max_steps) - taken)
+            done = self.step(k)
+            taken += k
+        return taken
+
+    def count_active(self):
+        n = C.c_int64(0)
+        _check(lib().dzo_hybridef_batch_count_active(self.h, C.byref(n)))
+        return int(n.value)
+
+    def _shape(self, what):
+        b, n3 = self.batch, 3 * self.n_particles
+        vec, sc, i32, i64, f64 = ((b, n3), self.dtype), ((b,), self.dtype), ((b,), np.int32), ((b,), np.int64), ((b,), np.float64)
+        return {HYBRIDEF_POINTS: vec, HYBRIDEF_GRADIENTS: vec, HYBRIDEF_ENERGIES: sc, HYBRIDEF_GRMS: f64, HYBRIDEF_STATUS: i32,
+                HYBRIDEF_EIGENVALUES: sc, HYBRIDEF_MODES: vec, HYBRIDEF_MODE_RESIDUALS: f64, HYBRIDEF_PROJECTIONS: sc, HYBRIDEF_UPHILL_STEPS: sc,
+                HYBRIDEF_TANGENT_STEPS: i32, HYBRIDEF_ITERATION_COUNTS: i64, HYBRIDEF_PRODUCTS: i64, HYBRIDEF_EVALUATIONS: i64}[what]
+
+    current_points = property(lambda self: self.read(HYBRIDEF_POINTS))
+    current_gradients = property(lambda self: self.read(HYBRIDEF_GRADIENTS))
+    energies = property(lambda self: self.read(HYBRIDEF_ENERGIES))
+    grms = property(lambda self: self.read(HYBRIDEF_GRMS))
+    status = property(lambda self: self.read(HYBRIDEF_STATUS))
+    eigenvalues = property(lambda self: self.read(HYBRIDEF_EIGENVALUES))
+    modes = property(lambda self: self.read(HYBRIDEF_MODES))
+    mode_residuals = property(lambda self: self.read(HYBRIDEF_MODE_RESIDUALS))
+    projections = property(lambda self: self.read(HYBRIDEF_PROJECTIONS))
+    uphill_steps = property(lambda self: self.read(HYBRIDEF_UPHILL_STEPS))
+    tangent_steps = property(lambda self: self.read(HYBRIDEF_TANGENT_STEPS))
+    iteration_counts = property(lambda self: self.read(HYBRIDEF_ITERATION_COUNTS))
+    products = property(lambda self: self.read(HYBRIDEF_PRODUCTS))
+    evaluations = property(lambda self: self.read(HYBRIDEF_EVALUATIONS))
+
+
+def find_saddles_hybrid(minima, n_particles, kick=0.05, grad_tol=1e-10, max_steps=300, max_step=0.1, zero_tol=1e-4, start_res_tol=1e-6,
+                        seed=0, radial=RADIAL_LENNARD_JONES, **options):
+    """Transition-state searches from the minima in ``minima`` (a DeviceArray, moved in place) without a dense Hessian, for up
+    to 1024 particles: takes the lowest mode of every minimum (``lowest_modes`` to the loose relative residual
+    ``start_res_tol``), displaces every point by ``kick`` along its vector, sets that vector as the first mode and runs a
+    ``HybridModeFollowing`` (which takes ``options``) for at most ``max_steps`` steps.  Returns the handle:
+    ``status == HYBRIDEF_CONVERGED`` with ``eigenvalues < -zero_tol`` marks the saddles found."""
+    modes = lowest_modes(minima, n_particles, True, LOWMODE_MAX_KRYLOV, 40, start_res_tol, None, seed, radial)
+    axpy_(float(kick), modes.vectors, minima)
+    search = HybridModeFollowing(minima, n_particles, modes.vectors, max_step=max_step, zero_tol=zero_tol, grad_tol=grad_tol, seed=seed,
+                                 radial=radial, **options)
+    search.run(max_steps)
+    return search
 
 
 # ------------------------------------------------------------------------------ profiling

@@ -22,6 +22,15 @@ template <typename T> __device__ __forceinline__ double cl_dot3(T ax, T ay, T az
     return __builtin_fma((double)az, (double)bz, p);
 }
 
+// |v|, the IEEE square root, and "neither infinite nor NaN" in the element type (the mode-following units)
+template <typename T> __device__ __forceinline__ T cl_abs(T v);
+template <> __device__ __forceinline__ double cl_abs<double>(double v) { return __builtin_fabs(v); }
+template <> __device__ __forceinline__ float cl_abs<float>(float v) { return __builtin_fabsf(v); }
+template <typename T> __device__ __forceinline__ T cl_sqrt(T v);
+template <> __device__ __forceinline__ double cl_sqrt<double>(double v) { return __builtin_sqrt(v); }
+template <> __device__ __forceinline__ float cl_sqrt<float>(float v) { return __builtin_sqrtf(v); }
+template <typename T> __device__ __forceinline__ bool cl_finite(T v) { return cl_abs(v) < (T)__builtin_inf(); }   // false for NaN
+
 // a block-wide sum in EVERY thread, fixed order (wave trees, then the four waves in wave order).  `red` holds 2 * kWaves doubles
 // used alternately, so that one barrier per sum is enough (a wave can be at most one sum ahead of the slowest).
 __device__ __forceinline__ double cl_block_sum(double v, double *red, int &par) {

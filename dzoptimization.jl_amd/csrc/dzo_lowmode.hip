@@ -18,6 +18,7 @@
 // wave sums in wave order through LDS -- the order of cl_block_sum, for up to 32 values behind one barrier.  The Ritz pair of the
 // small tridiagonal is a cyclic Jacobi iteration in fp64 on a K x K matrix in LDS, dealt over all threads of the block.
 // Every decision is taken from values that every thread reads from the same LDS words: the control flow is block-uniform.
+#include "dzo_chain.h"
 #include "dzo_cluster.h"
 #include "dzo_pairwise.h"
 #include "dzo_pcg.h"
@@ -491,6 +492,35 @@ template <typename T> static void lm_launch(hipStream_t s, int64_t batch, size_t
     else hipLaunchKernelGGL((lowmode_block_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), lds, s, a);
 }
 
+// ------------------------------------------------------------------------------ the asynchronous path (dzo_chain.h)
+// K of item g: krylov, but no more than the dimension of the range of P
+static int lm_krylov(int N, int krylov, int project_rigid) {
+    const int64_t range = project_rigid ? 3 * (int64_t)N - 6 : 3 * (int64_t)N;
+    return (int)(krylov < range ? krylov : range);
+}
+
+// gfx950 has 160 KiB of LDS per CU; dynamic requests above the default need the attribute.  It belongs to the kernel: raised to
+// the limit, so that no later call lowers it
+int32_t lm_prepare(int32_t dtype, int N, int krylov, int project_rigid) {
+    if (lm_lds_bytes(N, lm_krylov(N, krylov, project_rigid), dtype) > 48 * 1024) {
+        DZO_HIP(hipFuncSetAttribute(dtype == DZO_F64 ? lm_kernel<double>(N > 64) : lm_kernel<float>(N > 64), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)kClLdsMax));
+    }
+    return DZO_OK;
+}
+
+int32_t lm_enqueue(hipStream_t s, int32_t dtype, int N, int64_t batch, const void *points, int32_t project_rigid, int32_t krylov, int32_t max_cycles,
+                   double res_tol, uint64_t base_seed, const void *start, void *basis, void *eigenvalues, void *vectors, double *residuals,
+                   int32_t *info) {
+    const int K = lm_krylov(N, krylov, project_rigid);
+    const size_t lds = lm_lds_bytes(N, K, dtype);
+    DZO_DISPATCH(dtype, lm_launch<T>(s, batch, lds,
+                                     LowmodeArgs<T>{N, K, max_cycles, project_rigid != 0, res_tol, base_seed, (const T *)points, (const T *)start,
+                                                    (T *)basis, (T *)eigenvalues, (T *)vectors, residuals, info}));
+    DZO_HIP(hipGetLastError());
+    return DZO_OK;
+}
+
 }  // namespace dzo
 
 using namespace dzo;
@@ -513,13 +543,10 @@ int32_t dzo_pairwise_batch_lowest_mode(int32_t radial, int64_t n_particles, int6
     DZO_TRY(require_same_backend(where, cite, eigenvalues_dev, "eigenvalues", vectors_dev, "vectors"));
     DZO_TRY(require_same_backend(where, cite, residuals_dev, "residuals", info_dev, "info"));
     const int N = (int)n_particles;
-    const int64_t range = project_rigid ? 3 * n_particles - 6 : 3 * n_particles;
-    const int K = (int)(krylov < range ? krylov : range);
-    const size_t lds = lm_lds_bytes(N, K, dtype);
     Context &c = ctx();
     void *work = nullptr;
     if (N > 64) {
-        const size_t bytes = (size_t)3 * N * K * (size_t)batch * dtype_size(dtype);
+        const size_t bytes = (size_t)3 * N * lm_krylov(N, krylov, project_rigid) * (size_t)batch * dtype_size(dtype);
         const hipError_t e = hipMalloc(&work, bytes);
         if (e == hipErrorOutOfMemory) {
             set_error("dzo_pairwise_batch_lowest_mode: out of device memory for the Lanczos basis (%zu bytes)", bytes);
@@ -528,26 +555,16 @@ int32_t dzo_pairwise_batch_lowest_mode(int32_t radial, int64_t n_particles, int6
         }
         DZO_HIP(e);
     }
-    hipError_t e = hipSuccess;
-    // gfx950 has 160 KiB of LDS per CU; dynamic requests above the default need the attribute.  It belongs to the kernel:
-    // raised to the limit, so that no later call lowers it
-    if (lds > 48 * 1024)
-        e = hipFuncSetAttribute(dtype == DZO_F64 ? lm_kernel<double>(N > 64) : lm_kernel<float>(N > 64), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kClLdsMax);
-    if (e == hipSuccess) {
+    int32_t rc = lm_prepare(dtype, N, krylov, project_rigid);
+    if (rc == DZO_OK) {
         DZO_TIMED("lowmode", c.stream);
-        if (dtype == DZO_F64)
-            lm_launch<double>(c.stream, batch, lds,
-                              LowmodeArgs<double>{N, K, max_cycles, project_rigid != 0, res_tol, base_seed, (const double *)points_dev, (const double *)start_dev,
-                                                  (double *)work, (double *)eigenvalues_dev, (double *)vectors_dev, residuals_dev, info_dev});
-        else
-            lm_launch<float>(c.stream, batch, lds,
-                             LowmodeArgs<float>{N, K, max_cycles, project_rigid != 0, res_tol, base_seed, (const float *)points_dev, (const float *)start_dev,
-                                                (float *)work, (float *)eigenvalues_dev, (float *)vectors_dev, residuals_dev, info_dev});
-        e = hipGetLastError();
+        rc = lm_enqueue(c.stream, dtype, N, batch, points_dev, project_rigid, krylov, max_cycles, res_tol, base_seed, start_dev, work, eigenvalues_dev,
+                        vectors_dev, residuals_dev, info_dev);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    hipError_t e = hipSuccess;
+    if (rc == DZO_OK) e = hipStreamSynchronize(c.stream);
     if (work) (void)hipFree(work);
+    if (rc != DZO_OK) return rc;
     DZO_HIP(e);
     return DZO_OK;
 }

@@ -49,14 +49,6 @@ template <typename T> struct ModefollowArgs {
     int64_t *iters;            // (batch); may be null
 };
 
-template <typename T> __device__ __forceinline__ T mf_abs(T v);
-template <> __device__ __forceinline__ double mf_abs<double>(double v) { return __builtin_fabs(v); }
-template <> __device__ __forceinline__ float mf_abs<float>(float v) { return __builtin_fabsf(v); }
-template <typename T> __device__ __forceinline__ T mf_sqrt(T v);
-template <> __device__ __forceinline__ double mf_sqrt<double>(double v) { return __builtin_sqrt(v); }
-template <> __device__ __forceinline__ float mf_sqrt<float>(float v) { return __builtin_sqrtf(v); }
-template <typename T> __device__ __forceinline__ bool mf_finite(T v) { return mf_abs(v) < (T)__builtin_inf(); }   // false for NaN
-
 template <typename T> struct ModefollowRecord {
     T E;
     double grms, steplen;
@@ -123,13 +115,13 @@ template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_
     // 2. - 4. gradient norm, the classes of the modes, the freeze check
     const T zt = a.zero_tol;
     double gpart = 0, negs = 0, zers = 0;
-    bool bad = !mf_finite(E);
+    bool bad = !cl_finite(E);
     for (int e = tid; e < n; e += kBlock) {
         const T gv = G[e], lv = L[e];
         gpart = __builtin_fma((double)gv, (double)gv, gpart);
-        bad = bad || !mf_finite(gv) || !mf_finite(lv);
+        bad = bad || !cl_finite(gv) || !cl_finite(lv);
         negs += lv < -zt ? 1.0 : 0.0;
-        zers += mf_abs(lv) <= zt ? 1.0 : 0.0;
+        zers += cl_abs(lv) <= zt ? 1.0 : 0.0;
         if (a.g) a.g[base + e] = gv;
     }
     if (a.sweeps && a.sweeps[b] < 0) bad = true;
@@ -180,18 +172,18 @@ template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_
     int istar = -1;
     if (follow) {
         for (int i = tid; i < n; i += kBlock) {
-            if (mf_abs(L[i]) <= zt) continue;
+            if (cl_abs(L[i]) <= zt) continue;
             bool win;
             if (!wset) {
                 int rank = 0;
-                for (int j = 0; j < i; ++j) rank += mf_abs(L[j]) <= zt ? 0 : 1;
+                for (int j = 0; j < i; ++j) rank += cl_abs(L[j]) <= zt ? 0 : 1;
                 win = rank == a.start_mode;
             } else {
                 const double oi = ov[i];
                 win = oi == oi;
                 for (int j = 0; j < n; ++j) {
                     const double oj = ov[j];
-                    const bool nz = !(mf_abs(L[j]) <= zt);
+                    const bool nz = !(cl_abs(L[j]) <= zt);
                     win = win && !(nz && (oj > oi || (oj == oi && j < i)));
                 }
             }
@@ -211,9 +203,9 @@ template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_
     // 7. the mode steps
     double hpart = 0;
     for (int i = tid; i < n; i += kBlock) {
-        const T al = mf_abs(L[i]), f = F[i];
+        const T al = cl_abs(L[i]), f = F[i];
         const T q = (f + f) / al;
-        const T hq = q / (T(1) + mf_sqrt(T(1) + q * q));
+        const T hq = q / (T(1) + cl_sqrt(T(1) + q * q));
         const T hs = i == istar ? hq : -hq;
         const T h = al <= zt ? T(0) : hs;
         H[i] = h;

@@ -34,6 +34,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        pairwise_batch_hvp!, pairwise_batch_hessian!, symmetric_batch_eigen!, symeig_plan, hessian_spectrum,
        lowest_modes, LOWMODE_CONVERGED, LOWMODE_UNFINISHED, LOWMODE_FAILED,
        ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array,
+       HybridModeFollowing, hybridef_apply!, find_saddles_hybrid, HYBRIDEF_ACTIVE, HYBRIDEF_CONVERGED, HYBRIDEF_FAILED,
        BasinHopping, hop!, set_record!, set_array!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
@@ -773,6 +774,136 @@ function find_saddles(f::typeof(lj_energy), minima::HipVector{T}, n_particles::I
     set_start_mode!(saddles, start_mode)
     set_directions!(saddles, HipVector(vec(dirs)))
     return run_steps!(saddles, max_steps), polished
+end
+
+################################################################################ batched hybrid eigenvector following
+# (not exercised in the build container either; the Python class HybridModeFollowing binds the same entry points and IS tested)
+#
+# Hybrid eigenvector following (Munro & Wales 1999; include/dzo.h states the step) of `batch` clusters of up to 1024 particles
+# at once: per step the lowest mode is refined from the previous step's vector by a few Hessian-vector products, then the point
+# steps uphill along it and relaxes orthogonally to it by a few gradient steps.  No dense Hessian.  `points` is aliased and moved.
+
+const HYBRIDEF_ACTIVE, HYBRIDEF_CONVERGED, HYBRIDEF_FAILED = 0, 1, 2
+# `what` of read_array (DZO_HYBRIDEF_* of include/dzo.h)
+const HYBRIDEF_POINTS, HYBRIDEF_GRADIENTS, HYBRIDEF_ENERGIES, HYBRIDEF_GRMS, HYBRIDEF_STATUS, HYBRIDEF_EIGENVALUES, HYBRIDEF_MODES,
+      HYBRIDEF_MODE_RESIDUALS, HYBRIDEF_PROJECTIONS, HYBRIDEF_UPHILL_STEPS, HYBRIDEF_TANGENT_STEPS, HYBRIDEF_ITERATION_COUNTS,
+      HYBRIDEF_PRODUCTS, HYBRIDEF_EVALUATIONS = 0:13
+
+mutable struct HybridModeFollowing{T}
+    handle::Ptr{Cvoid}
+    points::HipVector{T}
+    n_particles::Int
+    batch::Int
+end
+
+"""`HybridModeFollowing(lj_energy, points, n_particles; directions=nothing, max_step=0.1, tangent_steps=10, tangent_steps_convex=2,
+tangent_cap=0.05, tangent_first=0.01, krylov=8, mode_cycles=1, mode_tol=1e-3, zero_tol=1e-4, grad_tol=1e-10, seed=0)`.
+`directions`: the first modes, laid out like `points`, or `nothing` to draw them in the kernel from `seed`."""
+function HybridModeFollowing(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer; directions::Union{Nothing,HipVector{T}}=nothing,
+                             max_step::Real=0.1, tangent_steps::Integer=10, tangent_steps_convex::Integer=2, tangent_cap::Real=0.05,
+                             tangent_first::Real=0.01, krylov::Integer=8, mode_cycles::Integer=1, mode_tol::Real=1e-3, zero_tol::Real=1e-4,
+                             grad_tol::Real=1e-10, seed::Integer=0) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_hybridef_batch_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Cint, Cdouble, Cdouble, Cint, Cint, Cdouble, Cdouble, Cdouble,
+                 UInt64, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, directions === nothing ? C_NULL : directions.ptr,
+                Float64(max_step), tangent_steps, tangent_steps_convex, Float64(tangent_cap), Float64(tangent_first), krylov, mode_cycles,
+                Float64(mode_tol), Float64(zero_tol), Float64(grad_tol), UInt64(seed), h))
+    hf = HybridModeFollowing{T}(h[], points, n_particles, batch)
+    finalizer(hf) do w
+        w.handle != C_NULL && ccall((:dzo_hybridef_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return hf
+end
+
+"""The mode the next refinement of every instance starts from: `directions` holds 3N elements per instance; copied."""
+function set_directions!(hf::HybridModeFollowing{T}, directions::HipVector{T}) where {T}
+    check(ccall((:dzo_hybridef_batch_set_directions, libdzo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), hf.handle, directions.ptr))
+    synchronize()
+    return hf
+end
+
+"""`step!(hf, steps; wait=true)`: `steps` steps of every ACTIVE instance.  Returns whether no instance is ACTIVE any more
+(`wait=true`, blocking) or `nothing` (enqueued only)."""
+function step!(hf::HybridModeFollowing, steps::Integer=1; wait::Bool=true)
+    if !wait
+        check(ccall((:dzo_hybridef_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), hf.handle, steps, C_NULL))
+        return nothing
+    end
+    flag = Ref{Cint}(0)
+    check(ccall((:dzo_hybridef_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), hf.handle, steps, flag))
+    return flag[] != 0
+end
+
+function count_active(hf::HybridModeFollowing)
+    n = Ref{Int64}(0)
+    check(ccall((:dzo_hybridef_batch_count_active, libdzo), Cint, (Ptr{Cvoid}, Ref{Int64}), hf.handle, n))
+    return Int(n[])
+end
+
+"""`read_array(hf, what)`: a blocking host copy of one of the HYBRIDEF_* arrays, in its own element type; vectors come back with
+the instance as the last dimension."""
+function read_array(hf::HybridModeFollowing{T}, what::Integer) where {T}
+    n, b = 3 * hf.n_particles, hf.batch
+    r = what in (HYBRIDEF_POINTS, HYBRIDEF_GRADIENTS, HYBRIDEF_MODES) ? Array{T}(undef, n, b) :
+        what in (HYBRIDEF_ENERGIES, HYBRIDEF_EIGENVALUES, HYBRIDEF_PROJECTIONS, HYBRIDEF_UPHILL_STEPS) ? Vector{T}(undef, b) :
+        what in (HYBRIDEF_GRMS, HYBRIDEF_MODE_RESIDUALS) ? Vector{Float64}(undef, b) :
+        what in (HYBRIDEF_ITERATION_COUNTS, HYBRIDEF_PRODUCTS, HYBRIDEF_EVALUATIONS) ? Vector{Int64}(undef, b) : Vector{Int32}(undef, b)
+    check(ccall((:dzo_hybridef_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), hf.handle, what, r))
+    return r
+end
+
+"""Device address of one of the HYBRIDEF_* arrays (no wait)."""
+function array_pointer(hf::HybridModeFollowing, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_hybridef_batch_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), hf.handle, what, p))
+    return p[]
+end
+
+"""`hybridef_apply!(points, eigenvalues, modes, n_particles; ...)`: ONE step of every instance from a mode the caller supplies
+(`dzo_hybridef_batch_apply`): `eigenvalues` holds one value and `modes` a unit vector of 3N elements per instance; `points` is
+moved.  Returns the status of every instance as a `Vector{Int32}`.  Blocks."""
+function hybridef_apply!(points::HipVector{T}, eigenvalues::HipVector{T}, modes::HipVector{T}, n_particles::Integer; max_step::Real=0.1,
+                         tangent_steps::Integer=10, tangent_steps_convex::Integer=2, tangent_cap::Real=0.05, tangent_first::Real=0.01,
+                         zero_tol::Real=1e-4, grad_tol::Real=0.0) where {T}
+    batch = div(length(points), 3 * n_particles)
+    status = HipVector{Float32}(undef, batch)               # four bytes per instance: read back as Int32
+    check(ccall((:dzo_hybridef_batch_apply, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, eigenvalues.ptr, modes.ptr, Float64(max_step),
+                tangent_steps, tangent_steps_convex, Float64(tangent_cap), Float64(tangent_first), Float64(zero_tol), Float64(grad_tol),
+                C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, status.ptr, C_NULL))
+    return collect(reinterpret(Int32, Array(status)))
+end
+
+function run_steps!(hf::HybridModeFollowing, max_steps::Integer, steps_per_call::Integer=20)
+    taken = 0
+    done = count_active(hf) == 0
+    while !done && taken < max_steps
+        k = min(steps_per_call, max_steps - taken)
+        done = step!(hf, k)
+        taken += k
+    end
+    return hf
+end
+
+"""`find_saddles_hybrid(lj_energy, minima, n_particles; kick=0.05, ...)`: takes the lowest mode of every minimum (`lowest_modes`
+to the loose relative residual `start_res_tol`), displaces every point by `kick` along its vector, sets that vector as the first
+mode and runs a `HybridModeFollowing` for at most `max_steps` steps.  Returns it; `minima` ends holding the searches' points."""
+function find_saddles_hybrid(f::typeof(lj_energy), minima::HipVector{T}, n_particles::Integer; kick::Real=0.05, grad_tol::Real=1e-10,
+                             max_steps::Integer=300, max_step::Real=0.1, zero_tol::Real=1e-4, start_res_tol::Real=1e-6, seed::Integer=0,
+                             options...) where {T}
+    vectors = lowest_modes(minima, n_particles; res_tol=start_res_tol, seed=seed)[2]
+    axpy!(kick, vectors, minima)
+    search = HybridModeFollowing(f, minima, n_particles; directions=vectors, max_step=max_step, zero_tol=zero_tol, grad_tol=grad_tol, seed=seed,
+                                 options...)
+    return run_steps!(search, max_steps)
 end
 
 """`quench(lj_energy, points, n_particles; ...)`: run the batched optimizer on `points` (in place) until every instance is

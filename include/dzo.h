@@ -848,6 +848,117 @@ int32_t dzo_pairwise_batch_lowest_mode(int32_t radial, int64_t n_particles, int6
                                        void *vectors_dev, double *residuals_dev, int32_t *info_dev);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched hybrid eigenvector following (Munro & Wales 1999) over many Lennard-Jones clusters: a transition-state search
+ * that never forms a Hessian, the consumer of the start_dev argument of the block above.  Per step the lowest mode is refined
+ * from the previous step's vector by a few Hessian-vector products; the point then steps uphill along that mode and relaxes
+ * in the subspace orthogonal to it by a few gradient evaluations.  Up to DZO_HYBRIDEF_MAX_PARTICLES = 1024 particles, where
+ * the dense search stops at 128.  Nothing in the reference follows modes: this block is the specification.
+ *
+ * Layout.  points, gradients and modes are (3N, batch): instance b at element 3N b, [x | y | z] -- the layout of every
+ * cluster unit.  Records are one value per instance: energies, eigenvalues, projections F and uphill steps h in T; grms and
+ * mode residuals fp64; status and tangent steps int32; iteration counts, products and evaluations int64.
+ *
+ * Launch shapes of the step kernel.  n_particles <= 64: one wave per instance, lane i holds particle i.  65 .. 1024: one
+ * 256-thread block per instance, thread t owns particles t + 256 q.  Point, mode, gradient and the previous tangent point and
+ * projected gradient live in registers.
+ *
+ * The step, per instance (T = the element type, n = 3N; every operation in T with one rounding, no contraction, IEEE division
+ * and square root, unless fp64 is named; "fp64" names operations in double precision on values converted exactly from T).
+ * Every sum over the particles is in fp64 in THE ORDER OF THE SUMS of the block above (its item a), a dot a.b with its three
+ * terms per particle.  Inputs: the point x; a unit vector u and a value lam, the lowest mode of the Hessian AT THIS POINT
+ * with net translation and rotation projected out, and that mode's status; max_step > 0, tangent_cap > 0, tangent_first > 0,
+ * grad_tol >= 0 (all fp64), zero_tol >= 0 (rounded once to T), tangent_steps >= 0, tangent_steps_convex >= 0.  An instance
+ * whose status is not ACTIVE is left alone.
+ *  1. Evaluate.  E and g at x, with the bits of dzo_pairwise_batch_energy_gradient (its routines and launch shapes).
+ *     grms = sqrt((g.g)/n) in fp64.
+ *  2. Freeze check.  E, g.g (which any non-finite g makes non-finite) or lam non-finite, or the mode's status FAILED: status
+ *     FAILED.  Otherwise grms <= grad_tol (fp64): status CONVERGED.  In both cases the point is not moved, F = h = 0,
+ *     tangent steps = 0, and the instance is frozen for all later steps with these records.
+ *  3. Uphill step.  F = T(u.g), the dot in fp64.  a = |lam|.  If a <= zero_tol, h = 0; otherwise q = (F + F) / a and
+ *     h = q / (1 + sqrt(1 + q*q)) -- 2F / (a (1 + sqrt(1 + 4F^2/a^2))), bounded by 1 in magnitude -- which is invariant to
+ *     the sign of u: F and h change sign with it, h u does not.  If |h| > max_step (compared in fp64), h = +-T(max_step).
+ *     x_e = fma(h, u_e, x_e), one FUSED multiply-add per element.
+ *  4. Tangent relaxation: tangent_steps iterations when lam < -zero_tol, otherwise tangent_steps_convex (a search still
+ *     inside the basin of its minimum is not to be pulled back).  For t = 0, 1, ...: g' = the gradient at x as in item 1;
+ *     c = u.g' (fp64); p_e = T(g'_e - c u_e), the product and the difference in fp64; pp = p.p (fp64).  If
+ *     sqrt(pp / n) <= grad_tol the loop ends.  alpha = tangent_first at t = 0; for t > 0, with s = x - x_prev and
+ *     y = p - p_prev (both in T), alpha = (s.s) / (s.y) in fp64 if s.y > 0, else tangent_first: the Barzilai-Borwein
+ *     length.  dn = alpha sqrt(pp) (fp64); if dn > tangent_cap, alpha = alpha (tangent_cap / dn) in fp64.  x_prev = x,
+ *     p_prev = p, x_e = fma(-T(alpha), p_e, x_e).
+ *  5. Record, all of the point BEFORE the move: E, g and grms; lam, u and the mode's residual; F and h; the tangent
+ *     iterations that moved the point; products += the mode's products and evaluations += 1 + the gradients of item 4
+ *     (both cumulative; a step that freezes counts what it spent); status ACTIVE; iteration count += 1.
+ * No floating-point atomics; one writer per element; nothing loops without a bound.  An instance computes the same bits alone
+ * or anywhere in any batch, and a handle in one call of k steps or k calls of one.
+ * CONVERGED says only that the point is stationary: lam tells whether it is a saddle (lam < -zero_tol), and only the full
+ * spectrum tells its index.  The method can end on a saddle of higher index; that is known behaviour, not an error.
+ *
+ * dzo_hybridef_batch_apply is the step, once, from a mode (u, lam) the CALLER supplies (from anywhere: nothing in it depends
+ * on the Lanczos iteration); it sets every status to ACTIVE first.  Record outputs other than status_dev may be NULL.  Blocking.
+ * A handle ALIASES points_dev and owns the modes of record u, a second mode buffer, the records and, above 64 particles, the
+ * Lanczos workspace of 3N * krylov * batch elements.  create copies dirs_dev (3N, batch) into u, or, with dirs_dev NULL, lets
+ * the first refinement draw its start in the kernel from base_seed (item f of the block above); it leaves the energies and
+ * gradients of the points as given, the other records zero until the first step.  step enqueues, per step, two launches on
+ * the library's stream: dzo_pairwise_batch_lowest_mode's kernel with project_rigid = 1, K = krylov, res_tol = mode_tol and
+ * start = u, writing into the second buffer; then the step kernel, which reads the mode from there and, for the instances it
+ * found ACTIVE, copies it into u (so a frozen instance keeps its mode of record to the bit).  The mode launch runs
+ * mode_cycles + 1 cycles at most: a cycle of that iteration ends with the Ritz vector, and the first product of the next
+ * measures its eigenvalue and residual, so mode_cycles cycles of krylov products refine and one product measures; a mode
+ * whose residual passes mode_tol at the first product costs that one product.  Its status UNFINISHED is normal here; only
+ * FAILED matters.  No host wait between the two launches or between steps, one at the end for all_done when it is not NULL.
+ * Frozen instances still pass through the mode launch.
+ *
+ * Errors follow dzo_pairwise_batch_lowest_mode: unknown radial or dtype, batch < 1, n_particles < 3 (rigid projection
+ * needs 3 particles), steps < 0, null pointers, unknown `what`, max_step, tangent_cap or tangent_first <= 0, a negative
+ * count or tolerance, krylov outside 2 .. DZO_LOWMODE_MAX_KRYLOV, mode_cycles < 1, a non-finite mode_tol DZO_ERR_INVALID;
+ * n_particles > 1024 DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required DZO_ERR_ASSERT; no memory for
+ * the state DZO_ERR_NOMEM.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_HYBRIDEF_MAX_PARTICLES 1024
+/* status */
+#define DZO_HYBRIDEF_ACTIVE 0
+#define DZO_HYBRIDEF_CONVERGED 1
+#define DZO_HYBRIDEF_FAILED 2
+/* `what` of get_ptr / read (T = the handle's element type) */
+#define DZO_HYBRIDEF_POINTS 0              /* T, 3N batch: the caller's array */
+#define DZO_HYBRIDEF_GRADIENTS 1           /* T, 3N batch: at the point before the last move */
+#define DZO_HYBRIDEF_ENERGIES 2            /* T, batch: likewise */
+#define DZO_HYBRIDEF_GRMS 3                /* fp64, batch */
+#define DZO_HYBRIDEF_STATUS 4              /* int32, batch */
+#define DZO_HYBRIDEF_EIGENVALUES 5         /* T, batch: lam of the last step */
+#define DZO_HYBRIDEF_MODES 6               /* T, 3N batch: u of the last step */
+#define DZO_HYBRIDEF_MODE_RESIDUALS 7      /* fp64, batch: of the mode launch of the last step */
+#define DZO_HYBRIDEF_PROJECTIONS 8         /* T, batch: F */
+#define DZO_HYBRIDEF_UPHILL_STEPS 9        /* T, batch: h after the cap */
+#define DZO_HYBRIDEF_TANGENT_STEPS 10      /* int32, batch: tangent iterations of the last step that moved the point */
+#define DZO_HYBRIDEF_ITERATION_COUNTS 11   /* int64, batch: moves made */
+#define DZO_HYBRIDEF_PRODUCTS 12           /* int64, batch: Hessian-vector products, cumulative */
+#define DZO_HYBRIDEF_EVALUATIONS 13        /* int64, batch: gradient evaluations, cumulative */
+typedef struct dzo_hybridef_batch_s *dzo_hybridef_batch_t;
+/* the step above, once, on every instance, from the caller's modes; points_dev is moved */
+int32_t dzo_hybridef_batch_apply(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                                 const void *eigenvalues_dev, const void *modes_dev, double max_step, int32_t tangent_steps,
+                                 int32_t tangent_steps_convex, double tangent_cap, double tangent_first, double zero_tol,
+                                 double grad_tol, void *energies_dev, void *gradients_dev, void *projections_dev,
+                                 void *uphill_steps_dev, double *grms_dev, int32_t *status_dev, int32_t *tangent_counts_dev);
+/* points_dev: (3N, batch), ALIASED.  dirs_dev: (3N, batch) first modes, copied, or NULL.  Blocking. */
+int32_t dzo_hybridef_batch_create(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                                  const void *dirs_dev, double max_step, int32_t tangent_steps, int32_t tangent_steps_convex,
+                                  double tangent_cap, double tangent_first, int32_t krylov, int32_t mode_cycles,
+                                  double mode_tol, double zero_tol, double grad_tol, uint64_t base_seed,
+                                  dzo_hybridef_batch_t *out);
+int32_t dzo_hybridef_batch_destroy(dzo_hybridef_batch_t h);
+/* the mode the next refinement of every instance starts from: dirs_dev (3N, batch) is copied into u.  No wait. */
+int32_t dzo_hybridef_batch_set_directions(dzo_hybridef_batch_t h, const void *dirs_dev);
+/* `steps` steps of every ACTIVE instance; all_done may be NULL (then no host wait) */
+int32_t dzo_hybridef_batch_step(dzo_hybridef_batch_t h, int32_t steps, int32_t *all_done);
+/* instances with status ACTIVE.  Blocking. */
+int32_t dzo_hybridef_batch_count_active(dzo_hybridef_batch_t h, int64_t *active);
+/* device address of an array above (no wait) / a blocking copy of it to host memory, in the array's own element type */
+int32_t dzo_hybridef_batch_get_ptr(dzo_hybridef_batch_t h, int32_t what, void **ptr_dev);
+int32_t dzo_hybridef_batch_read(dzo_hybridef_batch_t h, int32_t what, void *out_host);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
