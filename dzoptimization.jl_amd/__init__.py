@@ -218,6 +218,8 @@ ABI = {
     "dzo_hybridef_batch_destroy": [_vp], "dzo_hybridef_batch_set_directions": [_vp, _vp],
     "dzo_hybridef_batch_step": [_vp, _i32, _P(_i32)], "dzo_hybridef_batch_count_active": [_vp, _P(_i64)],
     "dzo_hybridef_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_hybridef_batch_read": [_vp, _i32, _vp],
+    "dzo_structure_batch_fingerprint": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
+    "dzo_structure_batch_classify": [_i64, _i64, _i32, _vp, _dbl, _vp, _P(_i32)],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
     "dzo_memcpy_d2h": [_vp, _vp, _i64], "dzo_memcpy_d2d": [_vp, _vp, _i64],
     "dzo_axpy": [_i64, _i32, _dbl, _vp, _vp], "dzo_axpby": [_i64, _i32, _dbl, _vp, _dbl, _vp],
@@ -1339,6 +1341,158 @@ def find_saddles_hybrid(minima, n_particles, kick=0.05, grad_tol=1e-10, max_step
                                  radial=radial, **options)
     search.run(max_steps)
     return search
+
+
+# ------------------------------------------------------------------------------ structure fingerprints, classification, pathways
+STRUCTURE_MAX_PARTICLES = 1024
+STRUCTURE_MAX_BATCH = 16384
+
+
+def structure_fingerprints(points, n_particles, radial=RADIAL_LENNARD_JONES):
+    """The fingerprint of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b ``[x | y | z]``) in one
+    launch (``dzo_structure_batch_fingerprint``, include/dzo.h): the per-particle energies sorted ascending, then the squared
+    distances from the centroid sorted ascending.  It does not change under rotation, translation, reflection or a relabelling
+    of the particles beyond rounding; it does not tell a structure from its mirror image.  Returns ``(fingerprints, energies)``:
+    a DeviceArray ``(batch, 2 * n_particles)`` and the total energies (host array, the bits of
+    ``pairwise_batch_energy_gradient``)."""
+    n = int(n_particles)
+    batch = points.size // (3 * n) if n > 0 else 0
+    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    fp = DeviceArray((batch, 2 * n), points.dtype)
+    e = DeviceArray((batch,), points.dtype)
+    _check(lib().dzo_structure_batch_fingerprint(radial, n, batch, _dt(points.dtype), points.ptr, fp.ptr, e.ptr))
+    return fp, e.to_host()
+
+
+def classify_structures(fingerprints, tol):
+    """Greedy leader labels of the rows of ``fingerprints`` (a DeviceArray ``(batch, length)``) on the device
+    (``dzo_structure_batch_classify``): rows a and b match iff ``|a_i - b_i| <= tol * max(1, |a_i|, |b_i|)`` for every i, in
+    fp64; row k takes the label of the first representative before it that it matches, or becomes a representative with
+    label k; a row with a non-finite element gets -1.  Returns ``(labels, representatives)``: host int32 ``(batch,)`` and the
+    indices of the representatives, ascending.  Rows placed first keep their own labels as long as they are distinct: put
+    known structures there to match against a database."""
+    assert len(fingerprints.shape) == 2, "fingerprints must be a (batch, length) DeviceArray"
+    batch, length = fingerprints.shape
+    labels = DeviceArray((batch,), np.int32)
+    count = C.c_int32(0)
+    _check(lib().dzo_structure_batch_classify(length, batch, _dt(fingerprints.dtype), fingerprints.ptr, float(tol), labels.ptr, C.byref(count)))
+    labels = labels.to_host()
+    representatives = np.flatnonzero(labels == np.arange(batch))
+    assert len(representatives) == count.value
+    return labels, representatives
+
+
+def unique_structures(points, n_particles, tol, radial=RADIAL_LENNARD_JONES):
+    """The distinct structures among the instances of ``points``: ``structure_fingerprints`` then ``classify_structures``.
+    Returns ``(labels, representatives, counts, energies)``: the label of every instance, the indices of the distinct
+    structures, how many instances carry each of those labels, and the energies of the distinct structures.  ``tol`` has no
+    default: see ``connect_saddles``."""
+    fp, e = structure_fingerprints(points, n_particles, radial)
+    labels, reps = classify_structures(fp, tol)
+    counts = np.array([(labels == r).sum() for r in reps], dtype=np.int64)
+    return labels, reps, counts, e[reps]
+
+
+class Pathways:
+    """What ``connect_saddles`` returns.  ``minima``: DeviceArray ``(n_minima, 3N)`` of the distinct end points, the known ones
+    first; ``minimum_energies`` (host, ``(n_minima,)``); ``saddle_energies`` (host, ``(batch,)``); ``edges`` (host int32
+    ``(batch, 2)``: the minimum below the saddle on the + and on the - side of its mode, -1 where that end was not stuck and at
+    rest after ``max_steps`` or has a non-finite fingerprint); ``barriers`` (host ``(batch, 2)``: saddle energy minus minimum energy, NaN
+    where the edge is -1); ``degenerate`` (host bool: both ends carry the same label); ``ends`` (DeviceArray ``(2 batch, 3N)``,
+    the + ends then the - ends); ``end_stuck`` (host bool ``(2 batch,)``); ``labels`` (of ``[known_minima | ends]``)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def triples(self):
+        """``[(minimum, saddle, minimum)]`` of the saddles with both ends identified."""
+        return [(int(a), k, int(b)) for k, (a, b) in enumerate(self.edges) if a >= 0 and b >= 0]
+
+
+def quench_to_rest(points, n_particles, history_length=10, initial_step_length=0.01, steps_per_launch=50, max_steps=2000,
+                   radial=RADIAL_LENNARD_JONES):
+    """Quenches ``points`` (moved in place) with ``BatchedLBFGS`` handles until the points are at rest.  ``is_stuck`` alone does
+    not say that: the reference's L-BFGS has no curvature safeguard, and a pair (s, y) with s.y < 0, which is what a start next
+    to a saddle gives, turns its direction uphill, so that the backtracking search halves the step to nothing and the
+    instance is stuck on a slope (measured on LJ7: every end 0.02 from a saddle stuck with |g| = 0.2).  So when every instance
+    is stuck a FRESH handle (empty history: its first step is the plain gradient step) takes over, and an instance is at rest
+    when it is stuck and a fresh handle has not lowered its energy by a single bit.  At most ``max_steps`` steps are taken
+    by any instance over all handles (a handle counts as one step at least).  Returns the host bool array "at rest"."""
+    n = int(n_particles)
+    batch = points.size // (3 * n)
+    taken, before = 0, None
+    at_rest = np.zeros(batch, dtype=bool)
+    while taken < max_steps and not at_rest.all():
+        opt = BatchedLBFGS(points, n, initial_step_length, history_length, radial)
+        done, launched = opt.count_active() == 0, 0
+        while not done and launched < max_steps - taken:
+            k = min(int(steps_per_launch), int(max_steps) - taken - launched)
+            done = opt.step(k)
+            launched += k
+        energies, stuck = opt.current_objective_values, opt.is_stuck
+        taken += max(1, int(opt.iteration_counts.max()))
+        opt.close()
+        if before is not None:
+            at_rest = stuck & (energies.view(np.int64 if energies.itemsize == 8 else np.int32)
+                               == before.view(np.int64 if before.itemsize == 8 else np.int32))
+        before = energies
+    return at_rest
+
+
+def connect_saddles(saddles, modes, n_particles, displacement, tol, known_minima=None, history_length=10, initial_step_length=0.01,
+                    steps_per_launch=50, max_steps=2000, radial=RADIAL_LENNARD_JONES):
+    """Which two minima every transition state joins.  ``saddles`` and ``modes`` are DeviceArrays of ``3 * n_particles * batch``
+    elements (for instance the points and ``HYBRIDEF_MODES`` of ``find_saddles_hybrid``); neither is changed.  The 2 batch points
+    ``saddle +- displacement * mode`` are formed on the device, quenched together by ``quench_to_rest`` (``BatchedLBFGS`` until
+    every instance is stuck, again from a fresh handle until none moves any more, ``max_steps`` steps at most), and then ``[known_minima | ends]`` is fingerprinted and classified with ``tol``
+    (``known_minima``: a DeviceArray of ``3 * n_particles * K`` elements, or None).  Returns a ``Pathways``.
+
+    ``displacement`` and ``tol`` have no default: their right values depend on the element type and the system (the precedent
+    is ``morse_index``'s ``zero_tol``).  ``tol`` must sit between the largest fingerprint distance of copies of one minimum
+    (what the quench leaves, not rounding alone) and the smallest distance of two different minima; ``displacement`` must leave
+    the saddle's flat top without jumping a neighbouring barrier.  Measured for 38 atoms (the ``structure-readme`` block of
+    README.md, profiles/structure_bench.json): in fp64 copies of one minimum at rest are at most 9.2e-7 apart and two minima of
+    different energy at least 2.0e-2, so anything from 1e-5 to 1e-3 serves; in fp32 the two figures are NOT a factor 100 apart
+    (instances that energy and spectrum call one minimum are up to 1.2e-1 apart, minima of different energy as close as 8.1e-3),
+    so no ``tol`` identifies fp32 minima of that size reliably: bring them to rest in fp64 first.  Of the displacements 1e-3 .. 1e-1, 3e-2 and 1e-1 gave every saddle two different ends in fp64."""
+    n = int(n_particles)
+    n3 = 3 * n
+    batch = saddles.size // n3 if n > 0 else 0
+    assert saddles.size == n3 * batch and batch >= 1, "saddles must hold 3 * n_particles * batch elements"
+    assert modes.size == saddles.size and modes.dtype == saddles.dtype, "modes must be laid out like saddles"
+    dtype, es = saddles.dtype, saddles.dtype.itemsize
+    known = 0
+    if known_minima is not None:
+        known = known_minima.size // n3
+        assert known_minima.size == n3 * known and known_minima.dtype == dtype, "known_minima must hold 3 * n_particles * K elements"
+    both = DeviceArray((known + 2 * batch, n3), dtype)
+    if known:
+        _check(lib().dzo_memcpy_d2d(both.ptr, known_minima.ptr, known_minima.nbytes))
+    ends = both.view(known * n3, (2 * batch, n3))
+    for side, sign in enumerate((1.0, -1.0)):
+        end = ends.view(side * batch * n3, (batch * n3,))
+        _check(lib().dzo_memcpy_d2d(end.ptr, saddles.ptr, saddles.nbytes))
+        axpy_(sign * float(displacement), modes, end)
+    stuck = quench_to_rest(ends, n, history_length, initial_step_length, steps_per_launch, max_steps, radial)
+    fp, energies = structure_fingerprints(both, n, radial)
+    for k in np.flatnonzero(~stuck):                         # an end that is still moving names no minimum
+        fill_(fp.view((known + int(k)) * 2 * n, (1,)), float("nan"))
+    labels, reps = classify_structures(fp, tol)
+    position = {int(r): i for i, r in enumerate(reps)}
+    minima = DeviceArray((len(reps), n3), dtype)
+    for i, r in enumerate(reps):
+        _check(lib().dzo_memcpy_d2d(minima.ptr + i * n3 * es, both.ptr + int(r) * n3 * es, n3 * es))
+    minimum_energies = energies[reps]
+    saddle_energies = pairwise_batch_energy_gradient(saddles, n, radial=radial)
+    edges = np.array([[position.get(int(labels[known + side * batch + b]), -1) for side in range(2)] for b in range(batch)],
+                     dtype=np.int32).reshape(batch, 2)
+    barriers = np.full((batch, 2), np.nan, dtype=dtype)
+    ok = edges >= 0
+    if ok.any():
+        barriers[ok] = (saddle_energies[:, None] - minimum_energies[np.where(ok, edges, 0)])[ok]
+    degenerate = ok[:, 0] & (edges[:, 0] == edges[:, 1])
+    return Pathways(minima=minima, minimum_energies=minimum_energies, saddle_energies=saddle_energies, edges=edges, barriers=barriers,
+                    degenerate=degenerate, ends=ends, end_stuck=stuck, labels=labels, n_known=known, _both=both)
 
 
 # ------------------------------------------------------------------------------ profiling

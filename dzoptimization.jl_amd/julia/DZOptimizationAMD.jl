@@ -35,6 +35,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        lowest_modes, LOWMODE_CONVERGED, LOWMODE_UNFINISHED, LOWMODE_FAILED,
        ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array,
        HybridModeFollowing, hybridef_apply!, find_saddles_hybrid, HYBRIDEF_ACTIVE, HYBRIDEF_CONVERGED, HYBRIDEF_FAILED,
+       structure_fingerprints, classify_structures, connect_saddles,
        BasinHopping, hop!, set_record!, set_array!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
@@ -919,6 +920,96 @@ function quench(f::typeof(lj_energy), points::HipVector{T}, n_particles::Integer
         taken += k
     end
     return opt
+end
+
+################################################################################ structure fingerprints, classification, pathways
+# (not exercised in the build container either; the Python functions of the same names bind the same entry points and ARE tested)
+
+"""`structure_fingerprints(points, n_particles)`: the fingerprint of every instance in one launch (include/dzo.h, "Structure
+fingerprints"): per-particle energies sorted ascending, then squared distances from the centroid sorted ascending.  Unchanged
+by rotation, translation, reflection and relabelling beyond rounding; blind to mirror images.  Returns
+`(fingerprints::HipVector{T} (2N, batch), energies::Vector{T})`.  Blocks."""
+function structure_fingerprints(points::HipVector{T}, n_particles::Integer) where {T}
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch && batch >= 1
+    fingerprints = HipVector{T}(undef, 2 * n_particles * batch)
+    energies = HipVector{T}(undef, batch)
+    check(ccall((:dzo_structure_batch_fingerprint, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, fingerprints.ptr, energies.ptr))
+    return fingerprints, Array(energies)
+end
+
+"""`classify_structures(fingerprints, length, tol)`: greedy leader labels of the `length`-element vectors in `fingerprints` on
+the device: a and b match iff `|a_i - b_i| <= tol * max(1, |a_i|, |b_i|)` for every i (fp64); instance k takes the label of the
+first representative before it that it matches, or becomes one; a non-finite vector gets -1.  Returns `(labels::Vector{Int32}
+(0-based, as the library numbers them), representatives::Vector{Int} (0-based))`.  Blocks."""
+function classify_structures(fingerprints::HipVector{T}, length_::Integer, tol::Real) where {T}
+    batch = div(length(fingerprints), length_)
+    @assert length(fingerprints) == length_ * batch && batch >= 1
+    labels_dev = HipVector{Float32}(undef, batch)            # four bytes per label: read back as Int32
+    count = Ref{Cint}(0)
+    check(ccall((:dzo_structure_batch_classify, libdzo), Cint, (Int64, Int64, Cint, Ptr{Cvoid}, Cdouble, Ptr{Cvoid}, Ref{Cint}),
+                length_, batch, dtype_code(T), fingerprints.ptr, Float64(tol), labels_dev.ptr, count))
+    labels = collect(reinterpret(Int32, Array(labels_dev)))
+    representatives = [k - 1 for k in 1:batch if labels[k] == k - 1]
+    @assert length(representatives) == count[]
+    return labels, representatives
+end
+
+"""`connect_saddles(lj_energy, saddles, modes, n_particles; displacement, tol, known_minima=nothing, ...)`: which two minima every
+transition state joins.  The 2 batch points `saddle +- displacement * mode` are formed on the device, quenched together by
+`BatchedLBFGSOptimizer`s (restarted until no point moves), and `[known_minima | ends]` is fingerprinted and classified with `tol`.  `displacement` and `tol` have no
+default (README.md, the structure block, has measured guidance).  Returns a named tuple `(minima, minimum_energies,
+saddle_energies, edges, barriers, degenerate)`; `edges` is `batch x 2`, 1-based indices into the columns of `minima`, 0 where an
+end was not stuck and at rest after `max_steps` or has a non-finite fingerprint."""
+function connect_saddles(f::typeof(lj_energy), saddles::HipVector{T}, modes::HipVector{T}, n_particles::Integer; displacement::Real, tol::Real,
+                         known_minima::Union{Nothing,HipVector{T}}=nothing, history_length::Integer=10, initial_step_length::Real=0.01,
+                         steps_per_launch::Integer=50, max_steps::Integer=2000) where {T}
+    n3 = 3 * n_particles
+    batch = div(length(saddles), n3)
+    @assert length(saddles) == n3 * batch && length(modes) == length(saddles)
+    known = known_minima === nothing ? 0 : div(length(known_minima), n3)
+    both = HipVector{T}(undef, (known + 2 * batch) * n3)
+    part(offset, count) = HipVector{T}(both.ptr + offset * n3 * sizeof(T), count * n3)
+    known > 0 && copy!(part(0, known), known_minima)
+    for (side, sign) in enumerate((1.0, -1.0))
+        end_ = part(known + (side - 1) * batch, batch)
+        copy!(end_, saddles)
+        axpy!(sign * displacement, modes, end_)
+    end
+    # "stuck" alone does not say "at rest": next to a saddle the first pair has s.y < 0, the L-BFGS direction points uphill and
+    # the search halves the step to nothing on a slope.  A fresh optimizer (empty history) takes over until one leaves every
+    # energy as it was, to the bit.
+    stuck = falses(2 * batch)
+    before = nothing
+    taken = 0
+    while taken < max_steps && !all(stuck)
+        budget = max_steps - taken
+        opt = quench(f, part(known, 2 * batch), n_particles; history_length=history_length, initial_step_length=initial_step_length,
+                     steps_per_launch=steps_per_launch, max_steps=budget)
+        taken += max(steps_per_launch, Int(maximum(iteration_counts(opt))))
+        now = objective_values(opt)
+        before === nothing || (stuck = stuck_flags(opt) .& (reinterpret.(UInt64, Float64.(now)) .== reinterpret.(UInt64, Float64.(before))))
+        before = now
+        finalize(opt)
+    end
+    fingerprints, energies = structure_fingerprints(both, n_particles)
+    for k in findall(.!stuck)                                # an end that is still moving names no minimum
+        fill!(HipVector{T}(fingerprints.ptr + (known + k - 1) * 2 * n_particles * sizeof(T), 1), NaN)
+    end
+    labels, representatives = classify_structures(fingerprints, 2 * n_particles, tol)
+    position = Dict(r => i for (i, r) in enumerate(representatives))
+    minima = HipVector{T}(undef, n3 * length(representatives))
+    for (i, r) in enumerate(representatives)
+        copy!(HipVector{T}(minima.ptr + (i - 1) * n3 * sizeof(T), n3), part(r, 1))
+    end
+    minimum_energies = energies[representatives .+ 1]
+    saddle_energies = Array(pairwise_batch_energy_gradient!(HipVector{T}(undef, batch), HipVector{T}(undef, n3 * batch), saddles, n_particles))
+    edges = [get(position, Int(labels[known + (side - 1) * batch + b]), 0) for b in 1:batch, side in 1:2]
+    barriers = [edges[b, side] > 0 ? saddle_energies[b] - minimum_energies[edges[b, side]] : T(NaN) for b in 1:batch, side in 1:2]
+    degenerate = [edges[b, 1] > 0 && edges[b, 1] == edges[b, 2] for b in 1:batch]
+    return (minima=minima, minimum_energies=minimum_energies, saddle_energies=saddle_energies, edges=edges, barriers=barriers,
+            degenerate=degenerate, both=both)
 end
 
 ################################################################################ batched AdGD over Lennard-Jones clusters

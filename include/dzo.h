@@ -959,6 +959,56 @@ int32_t dzo_hybridef_batch_get_ptr(dzo_hybridef_batch_t h, int32_t what, void **
 int32_t dzo_hybridef_batch_read(dzo_hybridef_batch_t h, int32_t what, void *out_host);
 
 /* ---------------------------------------------------------------------------------------
+ * Structure fingerprints and their classification: which of many Lennard-Jones clusters are the same structure up to
+ * rotation, translation, reflection and a relabelling of the particles.  Every unit above ends in a (3N, batch) array of
+ * stationary points most of which are copies of each other; these two entries say how many distinct ones there are and which.
+ *
+ * dzo_structure_batch_fingerprint, one launch for the whole batch, up to DZO_STRUCTURE_MAX_PARTICLES = 1024 particles (one
+ * wave per instance up to 64 particles, one 256-thread block above; the point and then the sort buffers in 24 KiB of LDS at
+ * most, so there is no device-memory fallback).  T is the element type.  Per instance:
+ *   1. e_i = sum_{j != i} e(r2_ij), summed in T from +0 with j ascending, the pair term that of the pairwise objective with the
+ *      self term dropped by a select: the bits of the row sums behind dzo_pairwise_batch_energy_gradient.
+ *   2. E = (T)(0.5 * sum_i e_i), the rows added in fp64 in THE ORDER OF THE SUMS of the block above (a thread's particles in
+ *      order, the wave tree, the four waves in wave order): E has the bits of dzo_pairwise_batch_energy_gradient.  Written to
+ *      energies_dev unless that is NULL.
+ *   3. c = (sum_i r_i) / N per coordinate: the sum in fp64 in the same order, one division in fp64, one rounding to T.
+ *      d_i = (x_i - c_x)^2 + (y_i - c_y)^2 + (z_i - c_z)^2 in T, the squares added left to right.
+ *   4. fingerprint = [e sorted ascending (N) | d sorted ascending (N)], instance b at 2N b.  The sort is an exact in-kernel
+ *      bitonic sort of the values, padded with +inf to a power of two.  Values that are not numbers sort last, behind +inf, and
+ *      are written as the canonical quiet NaN; -0 sorts before +0.
+ * No floating-point atomics; every output element is written once; an instance computes the same bits alone or anywhere in
+ * any batch.  The call enqueues and then blocks.
+ * What the fingerprint does NOT do: it does not tell a structure from its mirror image, and two different structures could
+ * in principle share it.  It is the identification GMIN-style programs use (energy plus sorted invariants), made stricter by
+ * the per-particle energies.  A coincident pair of particles gives a fingerprint with elements that are not finite.
+ * Errors: unknown radial or dtype, n_particles < 1, batch outside 1 .. 2^30, null points or fingerprints DZO_ERR_INVALID;
+ * n_particles > 1024 DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required DZO_ERR_ASSERT.
+ *
+ * dzo_structure_batch_classify labels `batch` vectors of `length` elements (instance b at length b; fingerprints, or
+ * fingerprints with descriptors of the caller's appended: length is free).  The match rule, evaluated in fp64: a and b match
+ * iff for every i  |a_i - b_i| <= tol * max(1, |a_i|, |b_i|).  An instance with any non-finite element matches nothing and
+ * gets label -1.  Labels are greedy leader labels in index order: instance k takes the label of the first REPRESENTATIVE
+ * j < k it matches; if there is none, k becomes a representative with label k.  *n_classes is the number of representatives.
+ * This is deliberately not "the smallest matching index": matching is not transitive (a ~ b, b ~ c, a !~ c gives 0, 0, 2),
+ * and a label always names a representative.  Known structures placed first in the batch make the call "match against a
+ * database": as long as they are distinct from each other they keep their own labels.
+ * One launch fills the lower triangle of a batch x batch bit matrix (a pair's comparison leaves at the first failing element),
+ * one single-wave launch walks k = 0 .. batch-1 over its rows masked by the representatives so far.  The result does not
+ * depend on grid size or scheduling.  The matrix, batch^2 / 8 bytes (32 MiB at DZO_STRUCTURE_MAX_BATCH = 16384), is allocated
+ * and freed by the call.  The call blocks: it returns *n_classes (host memory).
+ * Errors: tol < 0 or not a number, length < 1, batch < 1, unknown dtype, null pointers DZO_ERR_INVALID; batch > 16384
+ * DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required DZO_ERR_ASSERT; no memory for the matrix DZO_ERR_NOMEM.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_STRUCTURE_MAX_PARTICLES 1024
+#define DZO_STRUCTURE_MAX_BATCH 16384
+int32_t dzo_structure_batch_fingerprint(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype,
+                                        const void *points_dev,    /* T, (3N, batch), the quench layout [x|y|z] */
+                                        void *fingerprints_dev,    /* T, (2N, batch) */
+                                        void *energies_dev);       /* T, batch; may be NULL */
+int32_t dzo_structure_batch_classify(int64_t length, int64_t batch, int32_t dtype, const void *fingerprints_dev, /* T, (length, batch) */
+                                     double tol, int32_t *labels_dev /* int32, batch */, int32_t *n_classes /* host */);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
