@@ -494,29 +494,81 @@ def pairwise_radial_energy_delta(x, y, z, i, x_new, y_new, z_new, radial=RADIAL_
     return r.value
 
 
-# ------------------------------------------------------------------------------ parallel tempering (scripts/MonteCarlo.jl)
-TEMPERING_MAX_PARTICLES = 1024
-(TEMPERING_REPLICAS, TEMPERING_RADII, TEMPERING_INV_TEMPS, TEMPERING_NUM_ACCEPT, TEMPERING_NUM_REJECT, TEMPERING_RNG_STATES,
- TEMPERING_REC_INDEX, TEMPERING_REC_NORMALS, TEMPERING_REC_UNIFORM, TEMPERING_REC_CODE, TEMPERING_REC_SWAP,
- TEMPERING_REC_SWAP_LOGP) = range(12)
+# ------------------------------------------------------------------------------ handles of the C ABI
+class _Handle:
+    """An object of the C ABI and its lifetime.  A subclass names the prefix of its unit's entry points (``_prefix``, spelled
+    out: ``"dzo_<unit>_"``) and sets ``h`` to what its ``create`` entry returned."""
+    _prefix = None
+    h = None
+
+    def _fn(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    def _call(self, name, *args):
+        _check(self._fn(name)(*args))
+
+    def close(self):
+        """Destroys the handle.  Safe to call again, on an object whose constructor raised, and once the library is gone."""
+        h, self.h = self.h, None
+        if h and _lib is not None:
+            self._fn("destroy")(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
-class _HandleArrays:
-    """``read`` / ``ptr`` of a handle whose device arrays are numbered by a ``what`` constant.  A subclass names the library's
-    two entry points and has ``_shape(what)`` -> (shape, dtype)."""
-    _read_fn = _ptr_fn = None
+class _HandleArrays(_Handle):
+    """``read`` / ``ptr`` / ``_set`` of a handle whose device arrays are numbered by a ``what`` constant.  A subclass has
+    ``_shape(what)`` -> (shape, dtype)."""
 
     def read(self, what):
         """A blocking host copy of one of the handle's arrays; row k = replica / instance k."""
         shape, dtype = self._shape(what)
         out = np.empty(shape, dtype=dtype)
-        _check(getattr(lib(), self._read_fn)(self.h, int(what), out.ctypes.data))
+        self._call("read", self.h, int(what), out.ctypes.data)
         return out
 
     def ptr(self, what):
         p = C.c_void_p()
-        _check(getattr(lib(), self._ptr_fn)(self.h, int(what), C.byref(p)))
+        self._call("get_ptr", self.h, int(what), C.byref(p))
         return p.value
+
+    def _set(self, what, values):
+        shape, dtype = self._shape(what)
+        a = np.ascontiguousarray(values, dtype=dtype)
+        assert a.shape == shape
+        self._call("set", self.h, int(what), a.ctypes.data)
+
+
+def _u64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _per_walker(inverse_temperatures, perturbation_radii):
+    """The two host sequences of a tempering or basin-hopping handle, one entry per replica / walker, as fp64 arrays."""
+    beta = np.ascontiguousarray(inverse_temperatures, dtype=np.float64)
+    rad = np.ascontiguousarray(perturbation_radii, dtype=np.float64)
+    assert beta.ndim == 1 and beta.shape == rad.shape
+    return beta, rad
+
+
+def _batch_of(points, n_particles, name="points", least=0, batch=None):
+    """``(n, batch)`` of an array of ``3 * n_particles * batch`` elements, instance b ``[x | y | z]`` at ``3 * n_particles * b``,
+    with at least ``least`` instances; ``batch``: the number the array must hold, where something else tells it."""
+    n = int(n_particles)
+    batch = int(batch) if batch is not None else points.size // (3 * n) if n > 0 else 0
+    assert points.size == 3 * n * batch and batch >= least, name + " must hold 3 * n_particles * batch elements"
+    return n, batch
+
+
+# ------------------------------------------------------------------------------ parallel tempering (scripts/MonteCarlo.jl)
+TEMPERING_MAX_PARTICLES = 1024
+(TEMPERING_REPLICAS, TEMPERING_RADII, TEMPERING_INV_TEMPS, TEMPERING_NUM_ACCEPT, TEMPERING_NUM_REJECT, TEMPERING_RNG_STATES,
+ TEMPERING_REC_INDEX, TEMPERING_REC_NORMALS, TEMPERING_REC_UNIFORM, TEMPERING_REC_CODE, TEMPERING_REC_SWAP,
+ TEMPERING_REC_SWAP_LOGP) = range(12)
 
 
 class ParallelTempering(_HandleArrays):
@@ -526,7 +578,7 @@ class ParallelTempering(_HandleArrays):
     ``inverse_temperatures`` and ``perturbation_radii`` are host sequences.  The random-number rule is in include/dzo.h.
 
     ``temper``, ``swap`` and ``run`` do not block; every property that reads device state does."""
-    _read_fn, _ptr_fn = "dzo_tempering_read", "dzo_tempering_get_ptr"
+    _prefix = "dzo_tempering_"
 
     def __init__(self, replicas, n_particles, inverse_temperatures, perturbation_radii, constraining_radius, base_seed=0,
                  radial=RADIAL_LENNARD_JONES):
@@ -534,9 +586,7 @@ class ParallelTempering(_HandleArrays):
         self.replicas = replicas
         self.dtype = replicas.dtype
         self.n_particles = int(n_particles)
-        beta = np.ascontiguousarray(inverse_temperatures, dtype=np.float64)
-        rad = np.ascontiguousarray(perturbation_radii, dtype=np.float64)
-        assert beta.ndim == 1 and beta.shape == rad.shape
+        beta, rad = _per_walker(inverse_temperatures, perturbation_radii)
         self.n_replicas = int(beta.size)
         assert replicas.size == 3 * self.n_particles * self.n_replicas, "replicas must hold 3 * n_particles * n_replicas elements"
         self.constraining_radius = float(constraining_radius)
@@ -544,16 +594,8 @@ class ParallelTempering(_HandleArrays):
         h = C.c_void_p()
         _check(lib().dzo_tempering_create(radial, self.n_particles, self.n_replicas, _dt(self.dtype), replicas.ptr,
                                           beta.ctypes.data_as(_P(_dbl)), rad.ctypes.data_as(_P(_dbl)), self.constraining_radius,
-                                          int(base_seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+                                          _u64(base_seed), C.byref(h)))
         self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None) and _lib is not None:
-                lib().dzo_tempering_destroy(self.h)
-            self.h = None
-        except Exception:
-            pass
 
     @staticmethod
     def _trace(energies, ld, rows):
@@ -598,12 +640,6 @@ class ParallelTempering(_HandleArrays):
                 TEMPERING_REC_CODE: ((r, cap), np.int8), TEMPERING_REC_SWAP: ((r,), np.int8),
                 TEMPERING_REC_SWAP_LOGP: ((r,), self.dtype)}[what]
 
-    def _set(self, what, values):
-        shape, dtype = self._shape(what)
-        a = np.ascontiguousarray(values, dtype=dtype)
-        assert a.shape == shape
-        _check(lib().dzo_tempering_set(self.h, int(what), a.ctypes.data))
-
     coordinates = property(lambda self: self.read(TEMPERING_REPLICAS))
     inverse_temperatures = property(lambda self: self.read(TEMPERING_INV_TEMPS))
     perturbation_radii = property(lambda self: self.read(TEMPERING_RADII), lambda self, v: self._set(TEMPERING_RADII, v))
@@ -624,11 +660,7 @@ class ParallelTempering(_HandleArrays):
             opt = BatchedAdGD(minima, self.n_particles, initial_step_length)
         else:
             opt = BatchedLBFGS(minima, self.n_particles, initial_step_length, history_length)
-        done, taken = opt.count_active() == 0, 0
-        while not done and taken < max_steps:
-            k = min(int(steps_per_launch), int(max_steps) - taken)
-            done = opt.step(k)
-            taken += k
+        opt._run(max_steps, steps_per_launch)
         return opt.current_objective_values, minima, opt
 
 
@@ -644,64 +676,62 @@ def pairwise_batch_energy_gradient(points, n_particles, gradients=None, radial=R
     """Energy (host array, one per instance) of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b
     ``[x | y | z]`` at ``3 * n_particles * b``) and, into ``gradients`` when given, its gradient: the device routine and the
     summation order of ``BatchedLBFGS``."""
-    n = int(n_particles)
-    batch = points.size // (3 * n)
-    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    n, batch = _batch_of(points, n_particles, least=1)
     e = DeviceArray(batch, points.dtype)
     _check(lib().dzo_pairwise_batch_energy_gradient(radial, n, batch, _dt(points.dtype), points.ptr, e.ptr,
                                                     gradients.ptr if gradients is not None else None))
     return e.to_host()
 
 
-class _BatchedOptimizer(_HandleArrays):
-    """What ``BatchedLBFGS`` and ``BatchedAdGD`` share.  A subclass names the prefix of its entry points (``_prefix``) and the
-    ``what`` constants of the arrays both have (``_what``: property name -> constant), calls ``_create`` with the arguments
-    that follow ``points`` in its ``create`` entry, and has ``_shape(what)``."""
-    _prefix = None
-    _what = {}
+class _ClusterHandle(_HandleArrays):
+    """A handle over ``points``: a DeviceArray of ``3 * n_particles * batch`` elements (the tempering replica layout), aliased.
+    A subclass calls ``_create`` with the arguments that follow ``points`` in its ``create`` entry."""
 
-    def _fn(self, name):
-        return getattr(lib(), self._prefix + name)
-
-    def _create(self, points, n_particles, radial, *args):
+    def _create(self, points, n_particles, radial, *args, batch=None):
+        """Adopts ``points`` and creates the handle; ``batch``: where it is not the points' to tell (one per walker)."""
         _need_init()
         self.points = points
         self.dtype = points.dtype
-        self.n_particles = int(n_particles)
-        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
-        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        self.n_particles, self.batch = _batch_of(points, n_particles, batch=batch)
         h = C.c_void_p()
-        _check(self._fn("create")(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, *args, C.byref(h)))
+        self._call("create", radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, *args, C.byref(h))
         self.h = h
 
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            self._fn("destroy")(self.h)
-        self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_max_halvings(self, v):
-        _check(self._fn("set_max_halvings")(self.h, int(v)))
+class _SteppedCluster(_ClusterHandle):
+    """A cluster handle whose unit has the entries ``step`` and ``count_active``: an instance is active until it is stuck,
+    converged or failed, and ``step`` moves the active ones."""
 
     def step(self, steps=1, wait=True):
-        """``steps`` calls of ``step!()`` of every instance that is not stuck.  ``wait=True``: blocks and returns whether all
-        instances are stuck; ``wait=False``: enqueues only and returns None."""
-        if not wait:
-            _check(self._fn("step")(self.h, int(steps), None))
-            return None
-        flag = C.c_int32(0)
-        _check(self._fn("step")(self.h, int(steps), C.byref(flag)))
-        return bool(flag.value)
+        """``steps`` steps (calls of ``step!()``) of every active instance.  ``wait=True``: blocks and returns whether no
+        instance is active any more; ``wait=False``: enqueues only and returns None."""
+        flag = C.c_int32(0) if wait else None
+        self._call("step", self.h, int(steps), C.byref(flag) if wait else None)
+        return bool(flag.value) if wait else None
 
     def count_active(self):
         n = C.c_int64(0)
-        _check(self._fn("count_active")(self.h, C.byref(n)))
+        self._call("count_active", self.h, C.byref(n))
         return int(n.value)
+
+    def _run(self, max_steps, steps_per_call):
+        """Steps in chunks of ``steps_per_call`` until no instance is active, at most ``max_steps`` per instance.  Returns the
+        steps enqueued."""
+        done, taken = self.count_active() == 0, 0
+        while not done and taken < max_steps:
+            k = min(int(steps_per_call), int(max_steps) - taken)
+            done = self.step(k)
+            taken += k
+        return taken
+
+
+class _BatchedOptimizer(_SteppedCluster):
+    """What ``BatchedLBFGS`` and ``BatchedAdGD`` share.  A subclass names the ``what`` constants of the arrays both have
+    (``_what``: property name -> constant) and has ``_shape(what)``."""
+    _what = {}
+
+    def set_max_halvings(self, v):
+        self._call("set_max_halvings", self.h, int(v))
 
     current_points = property(lambda self: self.read(self._what["current_points"]))
     current_gradients = property(lambda self: self.read(self._what["current_gradients"]))
@@ -720,7 +750,6 @@ class BatchedLBFGS(_BatchedOptimizer):
     ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
     ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
     _prefix = "dzo_lbfgs_batch_"
-    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
     _what = dict(current_points=LBFGS_BATCH_POINTS, current_gradients=LBFGS_BATCH_GRADIENTS, current_objective_values=LBFGS_BATCH_OBJECTIVES,
                  delta_points=LBFGS_BATCH_DELTA_POINTS, delta_gradients=LBFGS_BATCH_DELTA_GRADIENTS,
                  delta_objective_values=LBFGS_BATCH_DELTA_OBJECTIVES, is_stuck=LBFGS_BATCH_IS_STUCK,
@@ -752,7 +781,7 @@ BASIN_HOPPING_MAX_PARTICLES = 1024
  BASIN_HOPPING_REC_TRIAL_ENERGY, BASIN_HOPPING_REC_QUENCH_ITERATIONS, BASIN_HOPPING_REC_CODE) = range(17)
 
 
-class BasinHopping(_HandleArrays):
+class BasinHopping(_ClusterHandle):
     """Basin hopping (Monte Carlo over the quenched landscape) of many walkers over Lennard-Jones clusters: ``hop(k)`` runs k
     hops -- perturb every particle, quench with the batched L-BFGS, Metropolis test on the quenched energies -- of every walker
     at the walker's own pace, ``hops_per_launch`` hops per launch.  ``points`` is a DeviceArray of ``3 * n_particles * batch``
@@ -760,42 +789,19 @@ class BasinHopping(_HandleArrays):
     ``perturbation_radii`` are host sequences, one per walker.  The rule is in include/dzo.h.
 
     The constructor and ``hop(wait=False)`` do not block; every property that reads device state does."""
-    _read_fn, _ptr_fn = "dzo_basin_hopping_read", "dzo_basin_hopping_get_ptr"
+    _prefix = "dzo_basin_hopping_"
 
     def __init__(self, points, n_particles, inverse_temperatures, perturbation_radii, constraining_radius, initial_step_length=0.01,
                  history_length=10, quench_steps=400, base_seed=0, radial=RADIAL_LENNARD_JONES):
-        _need_init()
-        self.points = points
-        self.dtype = points.dtype
-        self.n_particles = int(n_particles)
-        beta = np.ascontiguousarray(inverse_temperatures, dtype=np.float64)
-        rad = np.ascontiguousarray(perturbation_radii, dtype=np.float64)
-        assert beta.ndim == 1 and beta.shape == rad.shape
-        self.batch = int(beta.size)
-        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
+        beta, rad = _per_walker(inverse_temperatures, perturbation_radii)
         self.constraining_radius = float(constraining_radius)
         self.history_length, self.quench_steps = int(history_length), int(quench_steps)
         self.record_capacity = 0
-        h = C.c_void_p()
-        _check(lib().dzo_basin_hopping_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr,
-                                              beta.ctypes.data_as(_P(_dbl)), rad.ctypes.data_as(_P(_dbl)), self.constraining_radius,
-                                              float(initial_step_length), self.history_length, self.quench_steps,
-                                              int(base_seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_basin_hopping_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(points, n_particles, radial, beta.ctypes.data_as(_P(_dbl)), rad.ctypes.data_as(_P(_dbl)), self.constraining_radius,
+                     float(initial_step_length), self.history_length, self.quench_steps, _u64(base_seed), batch=beta.size)
 
     def set_max_halvings(self, v):
-        _check(lib().dzo_basin_hopping_set_max_halvings(self.h, int(v)))
+        self._call("set_max_halvings", self.h, int(v))
 
     def hop(self, num_hops, adapt=True, hops_per_launch=8, wait=True):
         """``num_hops`` hops of every walker in ``ceil(num_hops / hops_per_launch)`` launches (a launch lasts as long as its
@@ -825,12 +831,6 @@ class BasinHopping(_HandleArrays):
                 BASIN_HOPPING_REC_UNIFORM: ((b, cap), self.dtype), BASIN_HOPPING_REC_TRIAL_ENERGY: ((b, cap), self.dtype),
                 BASIN_HOPPING_REC_QUENCH_ITERATIONS: ((b, cap), np.int32), BASIN_HOPPING_REC_CODE: ((b, cap), np.int8)}[what]
 
-    def _set(self, what, values):
-        shape, dtype = self._shape(what)
-        a = np.ascontiguousarray(values, dtype=dtype)
-        assert a.shape == shape
-        _check(lib().dzo_basin_hopping_set(self.h, int(what), a.ctypes.data))
-
     current_points = property(lambda self: self.read(BASIN_HOPPING_POINTS))
     energies = property(lambda self: self.read(BASIN_HOPPING_ENERGIES))
     best_points = property(lambda self: self.read(BASIN_HOPPING_BEST_POINTS))
@@ -858,7 +858,6 @@ class BatchedAdGD(_BatchedOptimizer):
     ``3 * n_particles * batch`` elements (the tempering replica layout); it is aliased, as the live constructor aliases
     ``initial_point``.  Arrays come back instance-major (row b = instance b)."""
     _prefix = "dzo_adgd_batch_"
-    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
     _what = dict(current_points=ADGD_BATCH_POINTS, current_gradients=ADGD_BATCH_GRADIENTS, current_objective_values=ADGD_BATCH_OBJECTIVES,
                  delta_points=ADGD_BATCH_DELTA_POINTS, delta_gradients=ADGD_BATCH_DELTA_GRADIENTS,
                  delta_objective_values=ADGD_BATCH_DELTA_OBJECTIVES, is_stuck=ADGD_BATCH_IS_STUCK,
@@ -890,9 +889,7 @@ def pairwise_batch_hvp(points, directions, n_particles, products=None, curvature
     has the same layout, or with ``shared_point=True`` holds ONE point to which every direction is applied.  The products go
     into ``products`` (allocated when None).  Returns the products' DeviceArray, or with ``curvatures=True`` the pair
     ``(products, c)`` where ``c`` is a host array ``(batch, 2)`` of ``u.Hu`` and ``u.u`` in fp64."""
-    n = int(n_particles)
-    batch = directions.size // (3 * n) if n > 0 else 0
-    assert directions.size == 3 * n * batch and batch >= 1, "directions must hold 3 * n_particles * batch elements"
+    n, batch = _batch_of(directions, n_particles, "directions", least=1)
     assert points.size == (3 * n if shared_point else 3 * n * batch), "points must hold one point per instance, or one point when shared"
     assert points.dtype == directions.dtype, "points and directions must have one element type"
     if products is None:
@@ -908,9 +905,7 @@ def pairwise_batch_hessian(points, n_particles, out=None, radial=RADIAL_LENNARD_
     """The dense ``3N x 3N`` Hessian of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b
     ``[x | y | z]``) from one launch.  Returns a host array ``[b, c, r]``: column c, row r of instance b (the device layout,
     column-major per instance).  ``out``: a DeviceArray of ``9 * n_particles**2 * batch`` elements to hold the device copy."""
-    n = int(n_particles)
-    batch = points.size // (3 * n) if n > 0 else 0
-    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    n, batch = _batch_of(points, n_particles, least=1)
     if out is None:
         out = DeviceArray((batch, 3 * n, 3 * n), points.dtype)
     assert out.size == 9 * n * n * batch and out.dtype == points.dtype
@@ -981,9 +976,7 @@ def hessian_spectrum(points, n_particles, vectors=False, radial=RADIAL_LENNARD_J
     ``(batch, 3N)`` fp64 host array, or with ``vectors=True`` the pair ``(eigenvalues, eigenvectors)`` with the eigenvectors
     ``(batch, 3N, 3N)`` in the points' element type (``[b, k, :]`` is the normal mode of eigenvalue k).  Raises when an
     instance did not converge (non-finite Hessian: coincident particles)."""
-    n = int(n_particles)
-    batch = points.size // (3 * n) if n > 0 else 0
-    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    n, batch = _batch_of(points, n_particles, least=1)
     h = DeviceArray((batch, 3 * n, 3 * n), points.dtype)
     _check(lib().dzo_pairwise_batch_hessian(radial, n, batch, _dt(points.dtype), points.ptr, h.ptr))
     w, v, s = _symeig_device(h, 3 * n, batch, vectors, 0)
@@ -1022,9 +1015,7 @@ def lowest_modes(points, n_particles, project_rigid=True, krylov=32, max_cycles=
     CONVERGED when the residual of its Ritz pair is at most ``res_tol`` times the largest eigenvalue estimate seen
     (None: ``LOWMODE_DEFAULT_RES_TOL`` of the element type).  ``start``: a DeviceArray of start vectors laid out like
     ``points``, or None to draw them in the kernel from ``seed``.  Returns a ``LowestModes``."""
-    n = int(n_particles)
-    batch = points.size // (3 * n) if n > 0 else 0
-    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    n, batch = _batch_of(points, n_particles, least=1)
     assert start is None or (start.size == points.size and start.dtype == points.dtype), "start must be laid out like points"
     if res_tol is None:
         res_tol = LOWMODE_DEFAULT_RES_TOL[np.dtype(points.dtype)]
@@ -1033,7 +1024,7 @@ def lowest_modes(points, n_particles, project_rigid=True, krylov=32, max_cycles=
     r = DeviceArray((batch,), np.float64)
     info = DeviceArray((batch, 3), np.int32)
     _check(lib().dzo_pairwise_batch_lowest_mode(radial, n, batch, _dt(points.dtype), points.ptr, 1 if project_rigid else 0, int(krylov),
-                                                int(max_cycles), float(res_tol), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                int(max_cycles), float(res_tol), _u64(seed),
                                                 start.ptr if start is not None else None, w.ptr, v.ptr, r.ptr, info.ptr))
     return LowestModes(w.to_host(), v, r.to_host(), info.to_host().reshape(batch, 3))
 
@@ -1054,10 +1045,8 @@ def modefollow_apply(points, eigenvalues, eigenvectors, n_particles, target_inde
     DeviceArrays or host arrays, which are uploaded.  ``target_index=1`` needs ``follow`` (DeviceArray ``(batch, 3N)``, updated)
     and ``follow_set`` (DeviceArray of int32 ``(batch,)``, updated).  Returns a dict of host arrays: ``energies``, ``gradients``,
     ``projections`` (F), ``grms``, ``status``, ``index``, ``zeros``, ``followed_mode``, ``step_lengths``."""
-    n = int(n_particles)
+    n, batch = _batch_of(points, n_particles, least=1)
     n3 = 3 * n
-    batch = points.size // n3 if n > 0 else 0
-    assert points.size == n3 * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
     lam, vec = _as_dev(eigenvalues, points.dtype), _as_dev(eigenvectors, points.dtype)
     assert lam.dtype == points.dtype and vec.dtype == points.dtype, "points and modes must have one element type"
     assert lam.size == n3 * batch and vec.size == n3 * n3 * batch, "modes must hold 3N and 3N * 3N elements per instance"
@@ -1075,7 +1064,7 @@ def modefollow_apply(points, eigenvalues, eigenvectors, n_particles, target_inde
                 index=ix.to_host(), zeros=zr.to_host(), followed_mode=fm.to_host(), step_lengths=sl.to_host())
 
 
-class ModeFollowing(_HandleArrays):
+class ModeFollowing(_SteppedCluster):
     """Eigenvector following (Cerjan-Miller / Wales; include/dzo.h states the step) of many small Lennard-Jones clusters at once:
     ``step(k)`` enqueues, k times, the dense Hessians, their eigenvalues and eigenvectors and the step kernel, with no host wait
     in between.  ``target_index=0`` polishes minima, ``target_index=1`` searches transition states.  ``points`` is a DeviceArray
@@ -1083,64 +1072,23 @@ class ModeFollowing(_HandleArrays):
     (``grms <= grad_tol``) or FAILED (non-finite values, no convergence of the eigensolver, no mode to follow) and is then left
     alone; ``index`` and ``zeros`` tell what kind of stationary point it ended on."""
     _prefix = "dzo_modefollow_batch_"
-    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
 
     def __init__(self, points, n_particles, target_index=0, max_step=0.2, zero_tol=1e-4, grad_tol=1e-10, radial=RADIAL_LENNARD_JONES):
-        _need_init()
-        self.points = points
-        self.dtype = points.dtype
-        self.n_particles = int(n_particles)
-        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
-        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
-        h = C.c_void_p()
-        _check(lib().dzo_modefollow_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, int(target_index),
-                                                 float(max_step), float(zero_tol), float(grad_tol), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_modefollow_batch_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(points, n_particles, radial, int(target_index), float(max_step), float(zero_tol), float(grad_tol))
 
     def set_start_mode(self, mode):
-        _check(lib().dzo_modefollow_batch_set_start_mode(self.h, int(mode)))
+        self._call("set_start_mode", self.h, int(mode))
 
     def set_directions(self, directions):
         """An initial followed vector per instance: a DeviceArray or host array ``(batch, 3N)``."""
         d = _as_dev(directions, self.dtype)
         assert d.size == 3 * self.n_particles * self.batch and d.dtype == self.dtype
-        _check(lib().dzo_modefollow_batch_set_directions(self.h, d.ptr))
+        self._call("set_directions", self.h, d.ptr)
         synchronize()                                       # `d` may be a temporary
-
-    def step(self, steps=1, wait=True):
-        """``steps`` steps of every ACTIVE instance.  ``wait=True``: blocks and returns whether no instance is ACTIVE any more;
-        ``wait=False``: enqueues only and returns None."""
-        if not wait:
-            _check(lib().dzo_modefollow_batch_step(self.h, int(steps), None))
-            return None
-        flag = C.c_int32(0)
-        _check(lib().dzo_modefollow_batch_step(self.h, int(steps), C.byref(flag)))
-        return bool(flag.value)
 
     def run(self, max_steps, steps_per_call=10):
         """Steps until no instance is ACTIVE, at most ``max_steps`` per instance.  Returns the steps enqueued."""
-        done, taken = self.count_active() == 0, 0
-        while not done and taken < max_steps:
-            k = min(int(steps_per_call), int(max_steps) - taken)
-            done = self.step(k)
-            taken += k
-        return taken
-
-    def count_active(self):
-        n = C.c_int64(0)
-        _check(lib().dzo_modefollow_batch_count_active(self.h, C.byref(n)))
-        return int(n.value)
+        return self._run(max_steps, steps_per_call)
 
     def _shape(self, what):
         b, n3 = self.batch, 3 * self.n_particles
@@ -1214,10 +1162,8 @@ def hybridef_apply(points, eigenvalues, modes, n_particles, max_step=0.1, tangen
     ``(batch,)`` and ``modes`` ``(batch, 3N)`` (unit vectors) are DeviceArrays or host arrays, which are uploaded.  Returns a
     dict of host arrays: ``energies``, ``gradients``, ``projections`` (F), ``uphill_steps`` (h), ``grms``, ``status``,
     ``tangent_steps``."""
-    n = int(n_particles)
+    n, batch = _batch_of(points, n_particles, least=1)
     n3 = 3 * n
-    batch = points.size // n3 if n > 0 else 0
-    assert points.size == n3 * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
     lam, vec = _as_dev(eigenvalues, points.dtype), _as_dev(modes, points.dtype)
     assert lam.dtype == points.dtype and vec.dtype == points.dtype, "points and modes must have one element type"
     assert lam.size == batch and vec.size == n3 * batch, "a mode holds one eigenvalue and 3N elements per instance"
@@ -1231,7 +1177,7 @@ def hybridef_apply(points, eigenvalues, modes, n_particles, max_step=0.1, tangen
                 status=st.to_host(), tangent_steps=ts.to_host())
 
 
-class HybridModeFollowing(_HandleArrays):
+class HybridModeFollowing(_SteppedCluster):
     """Hybrid eigenvector following (Munro & Wales 1999; include/dzo.h states the step) of many Lennard-Jones clusters at once,
     up to 1024 particles: a transition-state search from Hessian-vector products and gradients alone.  ``step(k)`` enqueues, k
     times, the refinement of the lowest mode from the previous step's vector (``krylov`` Lanczos vectors, ``mode_cycles``
@@ -1243,67 +1189,26 @@ class HybridModeFollowing(_HandleArrays):
     the point is stationary; ``eigenvalues < -zero_tol`` says that it is a saddle, and only the spectrum (``hessian_spectrum``,
     ``hessian_eigenvalues``) tells its index: the method can end on a saddle of higher index."""
     _prefix = "dzo_hybridef_batch_"
-    _read_fn, _ptr_fn = _prefix + "read", _prefix + "get_ptr"
 
     def __init__(self, points, n_particles, directions=None, max_step=0.1, tangent_steps=10, tangent_steps_convex=2, tangent_cap=0.05,
                  tangent_first=0.01, krylov=8, mode_cycles=1, mode_tol=1e-3, zero_tol=1e-4, grad_tol=1e-10, seed=0,
                  radial=RADIAL_LENNARD_JONES):
-        _need_init()
-        self.points = points
-        self.dtype = points.dtype
-        self.n_particles = int(n_particles)
-        self.batch = points.size // (3 * self.n_particles) if self.n_particles > 0 else 0
-        assert points.size == 3 * self.n_particles * self.batch, "points must hold 3 * n_particles * batch elements"
-        d = None if directions is None else _as_dev(directions, self.dtype)
-        assert d is None or (d.size == points.size and d.dtype == self.dtype), "directions must be laid out like points"
-        h = C.c_void_p()
-        _check(lib().dzo_hybridef_batch_create(radial, self.n_particles, self.batch, _dt(self.dtype), points.ptr, d.ptr if d is not None else None,
-                                               float(max_step), int(tangent_steps), int(tangent_steps_convex), float(tangent_cap),
-                                               float(tangent_first), int(krylov), int(mode_cycles), float(mode_tol), float(zero_tol),
-                                               float(grad_tol), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_hybridef_batch_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        d = None if directions is None else _as_dev(directions, points.dtype)
+        assert d is None or (d.size == points.size and d.dtype == points.dtype), "directions must be laid out like points"
+        self._create(points, n_particles, radial, d.ptr if d is not None else None, float(max_step), int(tangent_steps),
+                     int(tangent_steps_convex), float(tangent_cap), float(tangent_first), int(krylov), int(mode_cycles), float(mode_tol),
+                     float(zero_tol), float(grad_tol), _u64(seed))
 
     def set_directions(self, directions):
         """The mode the next refinement of every instance starts from: a DeviceArray or host array ``(batch, 3N)``."""
         d = _as_dev(directions, self.dtype)
         assert d.size == 3 * self.n_particles * self.batch and d.dtype == self.dtype
-        _check(lib().dzo_hybridef_batch_set_directions(self.h, d.ptr))
+        self._call("set_directions", self.h, d.ptr)
         synchronize()                                       # `d` may be a temporary
-
-    def step(self, steps=1, wait=True):
-        """``steps`` steps of every ACTIVE instance.  ``wait=True``: blocks and returns whether no instance is ACTIVE any more;
-        ``wait=False``: enqueues only and returns None."""
-        if not wait:
-            _check(lib().dzo_hybridef_batch_step(self.h, int(steps), None))
-            return None
-        flag = C.c_int32(0)
-        _check(lib().dzo_hybridef_batch_step(self.h, int(steps), C.byref(flag)))
-        return bool(flag.value)
 
     def run(self, max_steps, steps_per_call=20):
         """Steps until no instance is ACTIVE, at most ``max_steps`` per instance.  Returns the steps enqueued."""
-        done, taken = self.count_active() == 0, 0
-        while not done and taken < max_steps:
-            k = min(int(steps_per_call), int(max_steps) - taken)
-            done = self.step(k)
-            taken += k
-        return taken
-
-    def count_active(self):
-        n = C.c_int64(0)
-        _check(lib().dzo_hybridef_batch_count_active(self.h, C.byref(n)))
-        return int(n.value)
+        return self._run(max_steps, steps_per_call)
 
     def _shape(self, what):
         b, n3 = self.batch, 3 * self.n_particles
@@ -1355,9 +1260,7 @@ def structure_fingerprints(points, n_particles, radial=RADIAL_LENNARD_JONES):
     of the particles beyond rounding; it does not tell a structure from its mirror image.  Returns ``(fingerprints, energies)``:
     a DeviceArray ``(batch, 2 * n_particles)`` and the total energies (host array, the bits of
     ``pairwise_batch_energy_gradient``)."""
-    n = int(n_particles)
-    batch = points.size // (3 * n) if n > 0 else 0
-    assert points.size == 3 * n * batch and batch >= 1, "points must hold 3 * n_particles * batch elements"
+    n, batch = _batch_of(points, n_particles, least=1)
     fp = DeviceArray((batch, 2 * n), points.dtype)
     e = DeviceArray((batch,), points.dtype)
     _check(lib().dzo_structure_batch_fingerprint(radial, n, batch, _dt(points.dtype), points.ptr, fp.ptr, e.ptr))
@@ -1418,20 +1321,17 @@ def quench_to_rest(points, n_particles, history_length=10, initial_step_length=0
     is stuck a FRESH handle (empty history: its first step is the plain gradient step) takes over, and an instance is at rest
     when it is stuck and a fresh handle has not lowered its energy by a single bit.  At most ``max_steps`` steps are taken
     by any instance over all handles (a handle counts as one step at least).  Returns the host bool array "at rest"."""
-    n = int(n_particles)
-    batch = points.size // (3 * n)
+    n, batch = _batch_of(points, n_particles)
     taken, before = 0, None
     at_rest = np.zeros(batch, dtype=bool)
     while taken < max_steps and not at_rest.all():
         opt = BatchedLBFGS(points, n, initial_step_length, history_length, radial)
-        done, launched = opt.count_active() == 0, 0
-        while not done and launched < max_steps - taken:
-            k = min(int(steps_per_launch), int(max_steps) - taken - launched)
-            done = opt.step(k)
-            launched += k
-        energies, stuck = opt.current_objective_values, opt.is_stuck
-        taken += max(1, int(opt.iteration_counts.max()))
-        opt.close()
+        try:
+            opt._run(max_steps - taken, steps_per_launch)
+            energies, stuck = opt.current_objective_values, opt.is_stuck
+            taken += max(1, int(opt.iteration_counts.max()))
+        finally:
+            opt.close()
         if before is not None:
             at_rest = stuck & (energies.view(np.int64 if energies.itemsize == 8 else np.int32)
                                == before.view(np.int64 if before.itemsize == 8 else np.int32))
@@ -1455,10 +1355,8 @@ def connect_saddles(saddles, modes, n_particles, displacement, tol, known_minima
     different energy at least 2.0e-2, so anything from 1e-5 to 1e-3 serves; in fp32 the two figures are NOT a factor 100 apart
     (instances that energy and spectrum call one minimum are up to 1.2e-1 apart, minima of different energy as close as 8.1e-3),
     so no ``tol`` identifies fp32 minima of that size reliably: bring them to rest in fp64 first.  Of the displacements 1e-3 .. 1e-1, 3e-2 and 1e-1 gave every saddle two different ends in fp64."""
-    n = int(n_particles)
+    n, batch = _batch_of(saddles, n_particles, "saddles", least=1)
     n3 = 3 * n
-    batch = saddles.size // n3 if n > 0 else 0
-    assert saddles.size == n3 * batch and batch >= 1, "saddles must hold 3 * n_particles * batch elements"
     assert modes.size == saddles.size and modes.dtype == saddles.dtype, "modes must be laid out like saddles"
     dtype, es = saddles.dtype, saddles.dtype.itemsize
     known = 0
@@ -1527,9 +1425,10 @@ def profile_table():
 
 
 # ------------------------------------------------------------------------------ problems
-class Problem:
+class Problem(_Handle):
     """Built-in device objective; callable like the reference's callbacks:
     ``p(x)`` = objective_function(x), ``p.gradient_(g, x)`` = gradient_function!(g, x)."""
+    _prefix = "dzo_problem_"
 
     def __init__(self, kind, n, dtype=np.float64, A=None, c=None, lam=0.0, l2=0.0, box_gradient=None,
                  box_constraint=None):
@@ -1568,14 +1467,6 @@ class Problem:
         general, callback-driven path with no Python frame in the loop -- what a Julia host's closures over
         ``dzo_problem_eval`` / ``dzo_problem_grad`` amount to."""
         return NativeCallbacks(self, with_constraint)
-
-    def __del__(self):
-        try:
-            if self.h and _lib is not None:
-                lib().dzo_problem_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
 
 class NativeCallbacks:
@@ -1666,30 +1557,29 @@ class _FieldView(DeviceArray):
     def to_host(self):
         out = np.empty(self.shape, dtype=self.dtype)
         o = self._opt
-        fn = getattr(lib(), f"dzo_{o._prefix}_read")
+        fn = getattr(lib(), o._prefix + "read")
         _check(fn(o.h, self._what, self._idx, out.ctypes.data) if o._ptr_idx else fn(o.h, self._what, out.ctypes.data))
         return out
 
 
-class _OptBase:
-    _prefix = ""
+class _OptBase(_Handle):
     _ptr_idx = True
 
     def _i(self, what):
         v = C.c_int64()
-        _check(getattr(lib(), f"dzo_{self._prefix}_get_i")(self.h, what, C.byref(v)))
+        _check(getattr(lib(), self._prefix + "get_i")(self.h, what, C.byref(v)))
         return v.value
 
     def _s(self, what):
         v = C.c_double()
-        _check(getattr(lib(), f"dzo_{self._prefix}_get_s")(self.h, what, C.byref(v)))
+        _check(getattr(lib(), self._prefix + "get_s")(self.h, what, C.byref(v)))
         return v.value
 
-    _has_read = False                # the C ABI has dzo_<prefix>_read (a copy to the host without a pointer hand-out)
+    _has_read = False                # the C ABI has <prefix>read (a copy to the host without a pointer hand-out)
 
     def _get_ptr(self, what, idx=0):
         p = C.c_void_p()
-        fn = getattr(lib(), f"dzo_{self._prefix}_get_ptr")
+        fn = getattr(lib(), self._prefix + "get_ptr")
         _check(fn(self.h, what, idx, C.byref(p)) if self._ptr_idx else fn(self.h, what, C.byref(p)))
         return p.value
 
@@ -1697,17 +1587,6 @@ class _OptBase:
         if self._has_read and shape is None:
             return _FieldView(self, what, idx)
         return DeviceArray(self.n if shape is None else shape, self.dtype, ptr=self._get_ptr(what, idx), owner=False)
-
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            getattr(lib(), f"dzo_{self._prefix}_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     iteration_count = property(lambda s: s._i(1))
     current_objective_value = property(lambda s: s._s(0))
@@ -1724,7 +1603,7 @@ class LBFGSOptimizer(_OptBase):
     (:347-356).  ``objective_function`` may be a :class:`Problem` (then ``gradient_function!``
     is ignored and may be ``None``).  The optimizer ALIASES ``initial_point`` (:393)."""
 
-    _prefix = "lbfgs"
+    _prefix = "dzo_lbfgs_"
     _has_read = True
 
     def __init__(self, constraint_function_, objective_function, gradient_function_, initial_point, *rest):
@@ -1870,7 +1749,7 @@ class AdGDOptimizer(_OptBase):
     """``AdGDOptimizer(constraint!, objective, gradient!, x0, initial_step_length)``
     (src/DZOptimization.jl:245-251)."""
 
-    _prefix = "adgd"
+    _prefix = "dzo_adgd_"
     _ptr_idx = False
     _has_read = True
 
@@ -1919,7 +1798,7 @@ class BFGSOptimizer(_OptBase):
     initial_point, initial_step_length)`` (README.md:33-36; legacy/DZOptimization.jl:753-766).
     COPIES ``initial_point`` (:769)."""
 
-    _prefix = "bfgs"
+    _prefix = "dzo_bfgs_"
     _ptr_idx = False
 
     def __init__(self, objective_function, gradient_function_, *rest):
@@ -2079,8 +1958,9 @@ def symv_(out, H, v):
     return out
 
 
-class BatchedBFGS:
+class BatchedBFGS(_Handle):
     """B independent ``BFGSOptimizer`` instances on one device (config 5)."""
+    _prefix = "dzo_bfgs_batch_"
 
     def __init__(self, problem_kind, x0, initial_step_length, device=None, matrices=None):
         """``device``: the GPU this shard lives on (default: the device selected with ``init``); a host that
@@ -2177,17 +2057,6 @@ class BatchedBFGS:
             self.delta_gradient.upload(np.asarray(dg, dt).reshape(B, n))
         return self
 
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_bfgs_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _preload_rccl():
     """Same reasoning as _preload_hip_runtime: libdzo_hip.so dlopen()s librccl.so.1 at first use; when
@@ -2204,7 +2073,7 @@ def _preload_rccl():
         C.CDLL(cand, mode=C.RTLD_GLOBAL)
 
 
-class Comm:
+class Comm(_Handle):
     """The one collective of the design (include/dzo.h): all-reduce(MIN) of the convergence flag of
     sharded independent optimizers over RCCL / xGMI, behind the C ABI.
 
@@ -2212,6 +2081,7 @@ class Comm:
     ``Comm.init_rank(uid, nranks, rank)``: one process per GPU; ``Comm.unique_id()`` on rank 0, carried to
     the other ranks by the launcher (``Comm.from_torch_distributed()`` does that over an initialised
     ``torch.distributed`` group)."""
+    _prefix = "dzo_comm_"
 
     def __init__(self, h):
         self.h = h
@@ -2302,17 +2172,6 @@ class Comm:
         _check(lib().dzo_bfgs_batch_all_done(self.h, hs, len(batches), C.byref(out)))
         return bool(out.value)
 
-    def close(self):
-        if getattr(self, "h", None) and _lib is not None:
-            lib().dzo_comm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def batches_all_done(batches, comm=None) -> bool:
     """``dzo_bfgs_batch_all_done`` with or without a communicator."""
@@ -2327,10 +2186,18 @@ def step_(opt):
     return opt.step()
 
 
+# every public class and function of the module, in the order of their definitions (tests/test_abi.py holds it to that)
 __all__ = [
-    "LBFGSOptimizer", "BFGSOptimizer", "AdGDOptimizer", "GradientDescentOptimizer", "BatchedBFGS", "Comm", "batches_all_done", "LineSearchEvaluator", "Problem", "NativeCallbacks", "DeviceArray", "step_",
-    "axpy_", "axpby_", "rmul_", "copy_", "fill_", "dot", "norm", "isequal", "trial_point_", "box_clamp_",
-    "norm2", "inv_norm", "negate_", "scale_",
-    "update_inverse_hessian_", "update_inverse_hessian_mfma_", "symv_", "init", "build", "lib", "device_info", "device_count", "synchronize",
-    "profile_enable", "profile_reset", "profile_table", "DzoError", "AssertionFailed",
+    "DzoError", "AssertionFailed", "build", "lib", "init", "device_info", "device_count", "synchronize",
+    "calibrate_read_bandwidth", "selftest_fast_div", "calibrate_read_bandwidth_of", "DeviceArray", "axpy_", "axpby_", "rmul_",
+    "copy_", "fill_", "dot", "norm", "isequal", "norm2", "inv_norm", "negate_", "scale_", "box_clamp_", "trial_point_",
+    "calibrate_fma_rate", "pairwise_radial_energy", "pairwise_radial_gradient_", "pairwise_radial_hvp_",
+    "pairwise_radial_energy_delta", "ParallelTempering", "pairwise_batch_energy_gradient", "BatchedLBFGS", "BasinHopping",
+    "BatchedAdGD", "pairwise_batch_hvp", "pairwise_batch_hessian", "hessian_eigenvalues", "morse_index", "symeig_plan",
+    "symmetric_batch_eigen", "hessian_spectrum", "LowestModes", "lowest_modes", "modefollow_apply", "ModeFollowing",
+    "polish_minima", "find_saddles", "hybridef_apply", "HybridModeFollowing", "find_saddles_hybrid", "structure_fingerprints",
+    "classify_structures", "unique_structures", "Pathways", "quench_to_rest", "connect_saddles", "profile_enable",
+    "profile_reset", "unsealed_first_reads", "profile_table", "Problem", "NativeCallbacks", "LineSearchEvaluator",
+    "LBFGSOptimizer", "AdGDOptimizer", "BFGSOptimizer", "GradientDescentOptimizer", "update_inverse_hessian_",
+    "update_inverse_hessian_mfma_", "symv_", "BatchedBFGS", "Comm", "batches_all_done", "step_",
 ]

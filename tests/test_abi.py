@@ -34,6 +34,42 @@ def test_python_abi_table_covers_the_header():
     assert declared == bound, (declared - bound, bound - declared)
 
 
+PROBLEM_KINDS = ("ROSENBROCK2D", "ROSENBROCK_CHAIN", "QUADRATIC", "LSE", "QUADRATIC_CHAIN", "PAIRWISE_LJ")
+# the defines of include/dzo.h that the Python module does not restate: the include guard, the version, the return codes (the module
+# keeps their texts in _ERR) and two sizes that only the library and the C examples use
+HEADER_ONLY = {"H", "VERSION", "OK", "ERR_INVALID", "ERR_HIP", "ERR_ASSERT", "ERR_NOMEM", "ERR_UNSUPPORTED", "ERR_STATE", "COMM_UNIQUE_ID_BYTES",
+               "SYMEIG_DEFAULT_SWEEPS"}
+
+
+def _header_defines():
+    """name without ``DZO_`` -> value of every ``#define DZO_<name> <integer>`` of include/dzo.h (None: no value)."""
+    text = open(os.path.join(ROOT, "include", "dzo.h")).read()
+    found = re.findall(r"^#define[ \t]+DZO_(\w+)(?:[ \t]+(-?\d+)\b)?", text, flags=re.M)
+    assert len(found) == len({name for name, _ in found}), "a name is defined twice"
+    return {name: int(value) if value else None for name, value in found}
+
+
+def test_python_constants_match_the_header():
+    """Every integer constant the module restates has the header's value, and every what / status / limit constant of the header
+    is restated: a constant added on one side only, or with another value, fails here whether or not its unit has a build test."""
+    defines = _header_defines()
+    constants = {k: v for k, v in vars(dzo).items() if k.isupper() and type(v) is int}
+    shared = sorted(set(constants) & set(defines))
+    assert len(shared) >= 116
+    assert {k: constants[k] for k in shared} == {k: defines[k] for k in shared}
+    assert {k: constants[k] for k in PROBLEM_KINDS} == {k: defines["PROBLEM_" + k] for k in PROBLEM_KINDS}
+    header_only = set(defines) - set(constants) - {"PROBLEM_" + k for k in PROBLEM_KINDS}
+    assert header_only == HEADER_ONLY, (header_only - HEADER_ONLY, HEADER_ONLY - header_only)
+
+
+def test_all_lists_the_public_classes_and_functions():
+    import inspect
+    public = [k for k, v in vars(dzo).items() if not k.startswith("_") and (inspect.isclass(v) or inspect.isfunction(v))
+              and v.__module__ == dzo.__name__]
+    assert len(dzo.__all__) == len(set(dzo.__all__))
+    assert set(dzo.__all__) == set(public), (set(public) - set(dzo.__all__), set(dzo.__all__) - set(public))
+
+
 def test_version_and_error_string_without_gpu():
     lib = dzo.lib()
     assert lib.dzo_version() == 100
