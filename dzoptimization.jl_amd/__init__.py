@@ -218,6 +218,12 @@ ABI = {
     "dzo_hybridef_batch_destroy": [_vp], "dzo_hybridef_batch_set_directions": [_vp, _vp],
     "dzo_hybridef_batch_step": [_vp, _i32, _P(_i32)], "dzo_hybridef_batch_count_active": [_vp, _P(_i64)],
     "dzo_hybridef_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_hybridef_batch_read": [_vp, _i32, _vp],
+    "dzo_neb_plan": [_i64, _i32, _i32, _P(_i32), _P(_i32), _P(_i64)],
+    "dzo_neb_batch_interpolate": [_i64, _i32, _i64, _i32, _vp, _vp, _vp],
+    "dzo_neb_batch_apply": [_i32, _i64, _i32, _i64, _i32, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dzo_neb_batch_create": [_i32, _i64, _i32, _i64, _i32, _vp, _dbl, _dbl, _dbl, _dbl, _i32, _i64, _P(_vp)],
+    "dzo_neb_batch_destroy": [_vp], "dzo_neb_batch_step": [_vp, _i32, _P(_i32)], "dzo_neb_batch_count_active": [_vp, _P(_i64)],
+    "dzo_neb_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_neb_batch_read": [_vp, _i32, _vp],
     "dzo_structure_batch_fingerprint": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
     "dzo_structure_batch_classify": [_i64, _i64, _i32, _vp, _dbl, _vp, _P(_i32)],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
@@ -1393,6 +1399,169 @@ def connect_saddles(saddles, modes, n_particles, displacement, tol, known_minima
                     degenerate=degenerate, ends=ends, end_stuck=stuck, labels=labels, n_known=known, _both=both)
 
 
+# ------------------------------------------------------------------------------ batched nudged elastic band
+NEB_MAX_PARTICLES = 1024
+NEB_MAX_IMAGES = 32
+NEB_ACTIVE, NEB_CONVERGED, NEB_FAILED = 0, 1, 2
+NEB_SHAPE_WAVE, NEB_SHAPE_BLOCK = 0, 1
+NEB_STORAGE_LDS, NEB_STORAGE_MEMORY = 0, 1
+(NEB_BAND, NEB_VELOCITIES, NEB_FORCES, NEB_TANGENTS, NEB_ENERGIES, NEB_FORCE_RMS, NEB_RESIDUALS, NEB_CLIMBING_IMAGES, NEB_HIGHEST_IMAGES,
+ NEB_STATUS, NEB_ITERATION_COUNTS) = range(11)
+
+
+def neb_plan(n_particles, n_images, dtype):
+    """``(shape, storage, lds_bytes)`` of ``dzo_neb_plan``: the launch shape that serves a band of ``n_images`` images of
+    ``n_particles`` particles, where its points, velocities and forces live during a launch, and the dynamic LDS of the launch.
+    A pure function; needs no device."""
+    shape, storage, lds = C.c_int32(), C.c_int32(), C.c_int64()
+    _check(lib().dzo_neb_plan(int(n_particles), int(n_images), _dt(dtype), C.byref(shape), C.byref(storage), C.byref(lds)))
+    return shape.value, storage.value, lds.value
+
+
+def _bands_of(band, n_particles, n_images):
+    """``(n, M, batch)`` of a band array of ``3 * n_particles * n_images * batch`` elements."""
+    n, m = int(n_particles), int(n_images)
+    batch = band.size // (3 * n * m) if n > 0 and m > 0 else 0
+    assert band.size == 3 * n * m * batch and batch >= 1, "band must hold 3 * n_particles * n_images * batch elements"
+    return n, m, batch
+
+
+def interpolate_band(a, b, n_particles, n_images, band=None):
+    """``dzo_neb_batch_interpolate``: the straight bands of ``n_images`` images between the points ``a`` and ``b`` (DeviceArrays
+    of ``3 * n_particles * batch`` elements in a common frame).  Returns the band, a DeviceArray ``(batch, n_images, 3N)``
+    (``band`` when given): images 0 and ``n_images - 1`` are copies of ``a`` and ``b``."""
+    n, batch = _batch_of(a, n_particles, "a", least=1)
+    assert b.size == a.size and b.dtype == a.dtype, "a and b must be laid out alike"
+    if band is None:
+        band = DeviceArray((batch, int(n_images), 3 * n), a.dtype)
+    assert band.size == a.size * int(n_images) and band.dtype == a.dtype
+    _check(lib().dzo_neb_batch_interpolate(n, int(n_images), batch, _dt(a.dtype), a.ptr, b.ptr, band.ptr))
+    return band
+
+
+def neb_apply(band, velocities, n_particles, n_images, spring=1.0, dt=0.02, max_move=0.1, force_tol=0.0, climb=True,
+              radial=RADIAL_LENNARD_JONES):
+    """``dzo_neb_batch_apply``: ONE iteration of the nudged elastic band (include/dzo.h) of every band, from the band and the
+    velocities given (DeviceArrays of ``3 * n_particles * n_images * batch`` elements, both moved in place); ``climb``: the
+    highest interior image climbs.  Returns a dict of host arrays: ``energies`` and ``force_rms`` ``(batch, M)``;
+    ``gradients``, ``forces`` and ``tangents`` ``(batch, M, 3N)``; ``residuals``, ``climbing_images``, ``highest_images`` and
+    ``status`` ``(batch,)``."""
+    n, m, batch = _bands_of(band, n_particles, n_images)
+    assert velocities.size == band.size and velocities.dtype == band.dtype, "velocities must be laid out like the band"
+    t = band.dtype
+    e, frms = DeviceArray((batch, m), t), DeviceArray((batch, m), np.float64)
+    g, f, tau = (DeviceArray((batch, m, 3 * n), t) for _ in range(3))
+    res = DeviceArray(batch, np.float64)
+    ci, hi, st = (DeviceArray(batch, np.int32) for _ in range(3))
+    _check(lib().dzo_neb_batch_apply(radial, n, m, batch, _dt(t), band.ptr, velocities.ptr, float(spring), float(dt), float(max_move),
+                                     float(force_tol), int(bool(climb)), e.ptr, g.ptr, f.ptr, tau.ptr, frms.ptr, res.ptr, ci.ptr, hi.ptr, st.ptr))
+    return dict(energies=e.to_host(), gradients=g.to_host(), forces=f.to_host(), tangents=tau.to_host(), force_rms=frms.to_host(),
+                residuals=res.to_host(), climbing_images=ci.to_host(), highest_images=hi.to_host(), status=st.to_host())
+
+
+class ElasticBand(_SteppedCluster):
+    """The nudged elastic band with a climbing image (Henkelman & Jonsson 2000; include/dzo.h states the iteration) of many
+    pairs of Lennard-Jones minima at once, up to 1024 particles and 32 images.  ``band`` is a DeviceArray of
+    ``3 * n_particles * n_images * batch`` elements (image m of band b ``[x | y | z]`` at ``3 * n_particles * (n_images * b + m)``,
+    for instance from ``interpolate_band``), aliased and moved; images 0 and ``n_images - 1`` are the fixed ends.  ``step(k)``
+    enqueues ONE launch that iterates every ACTIVE band k times: improved tangents, the spring force along the band, projected
+    velocity Verlet with time step ``dt`` and moves capped at ``max_move``, and from iteration ``climb_after`` on (``climb``) a
+    climbing image.  A band ends CONVERGED (the largest force rms of its images ``<= force_tol``) or FAILED and is then left
+    alone.  ``force_tol`` has no default: what a band can reach depends on the element type and the system (on 7-atom bands of
+    five images 1e-6 in float64 and 1e-5 in float32, tests/test_gpu_neb.py; the ``neb-readme`` block of README.md has how many
+    38-atom bands reach 1e-6 and 1e-4)."""
+    _prefix = "dzo_neb_batch_"
+
+    def __init__(self, band, n_particles, n_images, spring=1.0, dt=0.02, max_move=0.1, *, force_tol, climb=True, climb_after=50,
+                 radial=RADIAL_LENNARD_JONES):
+        _need_init()
+        self.points = self.band = band
+        self.dtype = band.dtype
+        self.n_particles, self.n_images, self.batch = _bands_of(band, n_particles, n_images)
+        h = C.c_void_p()
+        self._call("create", radial, self.n_particles, self.n_images, self.batch, _dt(self.dtype), band.ptr, float(spring), float(dt),
+                   float(max_move), float(force_tol), int(bool(climb)), int(climb_after), C.byref(h))
+        self.h = h
+
+    def run(self, max_iterations, steps_per_call=100):
+        """Iterates until no band is ACTIVE, at most ``max_iterations`` per band.  Returns the iterations enqueued."""
+        return self._run(max_iterations, steps_per_call)
+
+    def _shape(self, what):
+        b, m, n3 = self.batch, self.n_images, 3 * self.n_particles
+        vec, per, i32 = ((b, m, n3), self.dtype), ((b, m), self.dtype), ((b,), np.int32)
+        return {NEB_BAND: vec, NEB_VELOCITIES: vec, NEB_FORCES: vec, NEB_TANGENTS: vec, NEB_ENERGIES: per, NEB_FORCE_RMS: ((b, m), np.float64),
+                NEB_RESIDUALS: ((b,), np.float64), NEB_CLIMBING_IMAGES: i32, NEB_HIGHEST_IMAGES: i32, NEB_STATUS: i32,
+                NEB_ITERATION_COUNTS: ((b,), np.int64)}[what]
+
+    images = property(lambda self: self.read(NEB_BAND))
+    velocities = property(lambda self: self.read(NEB_VELOCITIES))
+    forces = property(lambda self: self.read(NEB_FORCES))
+    tangents = property(lambda self: self.read(NEB_TANGENTS))
+    energies = property(lambda self: self.read(NEB_ENERGIES))
+    force_rms = property(lambda self: self.read(NEB_FORCE_RMS))
+    residuals = property(lambda self: self.read(NEB_RESIDUALS))
+    climbing_images = property(lambda self: self.read(NEB_CLIMBING_IMAGES))
+    highest_images = property(lambda self: self.read(NEB_HIGHEST_IMAGES))
+    status = property(lambda self: self.read(NEB_STATUS))
+    iteration_counts = property(lambda self: self.read(NEB_ITERATION_COUNTS))
+
+
+class BandConnections:
+    """What ``connect_minima`` returns.  ``band``: DeviceArray ``(batch, M, 3N)`` of the relaxed bands; ``energies`` (host,
+    ``(batch, M)``: the profile of every band); ``status``, ``climbing_images``, ``iteration_counts`` and ``residuals`` (host,
+    ``(batch,)``); ``converged`` (host indices of the CONVERGED bands); ``saddles`` (DeviceArray ``(len(converged), 3N)``: their
+    climbing images after the refinement), ``saddle_energies``, ``saddle_status`` (``HYBRIDEF_*``), ``saddle_eigenvalues`` and
+    ``saddle_grms`` (host, per converged band); ``barriers`` (host ``(batch, 2)``: refined saddle energy minus the energy of
+    image 0 and of image M - 1, NaN for a band that did not converge)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def connect_minima(a, b, n_particles, n_images, force_tol, grad_tol=1e-10, max_iterations=10000, steps_per_call=100, refine_steps=100,
+                   radial=RADIAL_LENNARD_JONES, **band_options):
+    """The double-ended search: what joins minimum ``a[k]`` to minimum ``b[k]``, and how high is the barrier.  ``a`` and ``b``
+    are DeviceArrays of ``3 * n_particles * batch`` elements in a common frame (no alignment is done: the two ``ends`` of one
+    saddle in ``connect_saddles`` are in one); neither is changed.  Interpolates (``interpolate_band``), relaxes the bands
+    (``ElasticBand`` with ``band_options``: spring, dt, max_move, climb_after) to ``force_tol`` in at most ``max_iterations``
+    iterations, then takes the climbing image and its tangent of every CONVERGED band and refines them with
+    ``HybridModeFollowing(directions=tangent)`` to ``grad_tol`` in at most ``refine_steps`` steps.  Returns a
+    ``BandConnections``.  ``force_tol`` has no default, like ``tol`` in ``connect_saddles``: it depends on the element type."""
+    n, batch = _batch_of(a, n_particles, "a", least=1)
+    m, n3, es = int(n_images), 3 * n, a.dtype.itemsize
+    band = interpolate_band(a, b, n, m)
+    neb = ElasticBand(band, n, m, force_tol=force_tol, radial=radial, **band_options)
+    try:
+        neb.run(max_iterations, steps_per_call)
+        energies, status, climbing = neb.energies, neb.status, neb.climbing_images
+        counts, residuals = neb.iteration_counts, neb.residuals
+        converged = np.flatnonzero((status == NEB_CONVERGED) & (climbing >= 0))
+        k = len(converged)
+        saddles, tangents = DeviceArray((k, n3), a.dtype), DeviceArray((k, n3), a.dtype)
+        # two small copies per converged band from the host: fine for the hundreds of bands of one call
+        for i, bi in enumerate(converged):
+            offset = ((int(bi) * m + int(climbing[bi])) * n3) * es
+            _check(lib().dzo_memcpy_d2d(saddles.ptr + i * n3 * es, band.ptr + offset, n3 * es))
+            _check(lib().dzo_memcpy_d2d(tangents.ptr + i * n3 * es, neb.ptr(NEB_TANGENTS) + offset, n3 * es))
+    finally:
+        neb.close()
+    barriers = np.full((batch, 2), np.nan, dtype=a.dtype)
+    fields = dict(saddle_energies=np.empty(0, a.dtype), saddle_status=np.empty(0, np.int32), saddle_eigenvalues=np.empty(0, a.dtype),
+                  saddle_grms=np.empty(0, np.float64))
+    if k:
+        search = HybridModeFollowing(saddles, n, tangents, grad_tol=grad_tol, radial=radial)
+        try:
+            search.run(refine_steps)
+            fields = dict(saddle_energies=search.energies, saddle_status=search.status, saddle_eigenvalues=search.eigenvalues,
+                          saddle_grms=search.grms)
+        finally:
+            search.close()
+        barriers[converged] = fields["saddle_energies"][:, None] - energies[converged][:, [0, m - 1]]
+    return BandConnections(band=band, energies=energies, status=status, climbing_images=climbing, iteration_counts=counts, residuals=residuals,
+                           converged=converged, saddles=saddles, barriers=barriers, **fields)
+
+
 # ------------------------------------------------------------------------------ profiling
 def profile_enable(level=2):
     """0/False off, 1 = the roofline kernels only (cheap), 2/True = every kernel."""
@@ -2196,7 +2365,8 @@ __all__ = [
     "BatchedAdGD", "pairwise_batch_hvp", "pairwise_batch_hessian", "hessian_eigenvalues", "morse_index", "symeig_plan",
     "symmetric_batch_eigen", "hessian_spectrum", "LowestModes", "lowest_modes", "modefollow_apply", "ModeFollowing",
     "polish_minima", "find_saddles", "hybridef_apply", "HybridModeFollowing", "find_saddles_hybrid", "structure_fingerprints",
-    "classify_structures", "unique_structures", "Pathways", "quench_to_rest", "connect_saddles", "profile_enable",
+    "classify_structures", "unique_structures", "Pathways", "quench_to_rest", "connect_saddles", "neb_plan", "interpolate_band",
+    "neb_apply", "ElasticBand", "BandConnections", "connect_minima", "profile_enable",
     "profile_reset", "unsealed_first_reads", "profile_table", "Problem", "NativeCallbacks", "LineSearchEvaluator",
     "LBFGSOptimizer", "AdGDOptimizer", "BFGSOptimizer", "GradientDescentOptimizer", "update_inverse_hessian_",
     "update_inverse_hessian_mfma_", "symv_", "BatchedBFGS", "Comm", "batches_all_done", "step_",

@@ -36,6 +36,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        ModeFollowing, modefollow_apply!, set_start_mode!, set_directions!, polish_minima, find_saddles, read_array,
        HybridModeFollowing, hybridef_apply!, find_saddles_hybrid, HYBRIDEF_ACTIVE, HYBRIDEF_CONVERGED, HYBRIDEF_FAILED,
        structure_fingerprints, classify_structures, connect_saddles,
+       ElasticBand, interpolate_band!, neb_apply!, neb_plan, connect_minima, NEB_ACTIVE, NEB_CONVERGED, NEB_FAILED,
        BasinHopping, hop!, set_record!, set_array!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
@@ -1010,6 +1011,181 @@ function connect_saddles(f::typeof(lj_energy), saddles::HipVector{T}, modes::Hip
     degenerate = [edges[b, 1] > 0 && edges[b, 1] == edges[b, 2] for b in 1:batch]
     return (minima=minima, minimum_energies=minimum_energies, saddle_energies=saddle_energies, edges=edges, barriers=barriers,
             degenerate=degenerate, both=both)
+end
+
+################################################################################ batched nudged elastic band
+# (not exercised in the build container either; the Python class ElasticBand binds the same entry points and IS tested)
+#
+# The nudged elastic band with a climbing image (Henkelman & Jonsson 2000; include/dzo.h states the iteration) of `batch` pairs of
+# minima at once: `band` holds n_images images of n_particles particles per band, image m of band b at 3 n_particles (n_images b + m),
+# aliased and moved; images 0 and n_images - 1 are the fixed ends.
+
+const NEB_MAX_PARTICLES, NEB_MAX_IMAGES = 1024, 32
+const NEB_ACTIVE, NEB_CONVERGED, NEB_FAILED = 0, 1, 2
+const NEB_SHAPE_WAVE, NEB_SHAPE_BLOCK = 0, 1
+const NEB_STORAGE_LDS, NEB_STORAGE_MEMORY = 0, 1
+# `what` of read_array (DZO_NEB_* of include/dzo.h)
+const NEB_BAND, NEB_VELOCITIES, NEB_FORCES, NEB_TANGENTS, NEB_ENERGIES, NEB_FORCE_RMS, NEB_RESIDUALS, NEB_CLIMBING_IMAGES,
+      NEB_HIGHEST_IMAGES, NEB_STATUS, NEB_ITERATION_COUNTS = 0:10
+
+mutable struct ElasticBand{T}
+    handle::Ptr{Cvoid}
+    band::HipVector{T}
+    n_particles::Int
+    n_images::Int
+    batch::Int
+end
+
+"""`neb_plan(T, n_particles, n_images)`: `(shape, storage, lds_bytes)` of `dzo_neb_plan`; a pure function, needs no device."""
+function neb_plan(::Type{T}, n_particles::Integer, n_images::Integer) where {T}
+    shape, storage, lds = Ref{Cint}(0), Ref{Cint}(0), Ref{Int64}(0)
+    check(ccall((:dzo_neb_plan, libdzo), Cint, (Int64, Cint, Cint, Ref{Cint}, Ref{Cint}, Ref{Int64}),
+                n_particles, n_images, dtype_code(T), shape, storage, lds))
+    return Int(shape[]), Int(storage[]), Int(lds[])
+end
+
+"""`interpolate_band!(band, a, b, n_particles, n_images)`: the straight bands between the points `a` and `b` (3N elements per
+band, in a common frame): images 0 and n_images - 1 are copies of `a` and `b`.  Returns `band`."""
+function interpolate_band!(band::HipVector{T}, a::HipVector{T}, b::HipVector{T}, n_particles::Integer, n_images::Integer) where {T}
+    ensure_init()
+    batch = div(length(a), 3 * n_particles)
+    @assert length(a) == 3 * n_particles * batch && length(b) == length(a) && length(band) == length(a) * n_images
+    check(ccall((:dzo_neb_batch_interpolate, libdzo), Cint, (Int64, Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                n_particles, n_images, batch, dtype_code(T), a.ptr, b.ptr, band.ptr))
+    return band
+end
+
+"""`ElasticBand(lj_energy, band, n_particles, n_images; force_tol, spring=1.0, dt=0.02, max_move=0.1, climb=true, climb_after=50)`.
+`force_tol` has no default: what a band can reach depends on the element type."""
+function ElasticBand(::typeof(lj_energy), band::HipVector{T}, n_particles::Integer, n_images::Integer; force_tol::Real, spring::Real=1.0,
+                     dt::Real=0.02, max_move::Real=0.1, climb::Bool=true, climb_after::Integer=50) where {T}
+    ensure_init()
+    batch = div(length(band), 3 * n_particles * n_images)
+    @assert length(band) == 3 * n_particles * n_images * batch
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_neb_batch_create, libdzo), Cint,
+                (Cint, Int64, Cint, Int64, Cint, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Int64, Ref{Ptr{Cvoid}}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, n_images, batch, dtype_code(T), band.ptr, Float64(spring), Float64(dt), Float64(max_move),
+                Float64(force_tol), climb ? 1 : 0, climb_after, h))
+    eb = ElasticBand{T}(h[], band, n_particles, n_images, batch)
+    finalizer(eb) do w
+        w.handle != C_NULL && ccall((:dzo_neb_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return eb
+end
+
+"""`step!(eb, steps; wait=true)`: ONE launch that iterates every ACTIVE band `steps` times.  Returns whether no band is ACTIVE any
+more (`wait=true`, blocking) or `nothing` (enqueued only)."""
+function step!(eb::ElasticBand, steps::Integer=1; wait::Bool=true)
+    if !wait
+        check(ccall((:dzo_neb_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), eb.handle, steps, C_NULL))
+        return nothing
+    end
+    flag = Ref{Cint}(0)
+    check(ccall((:dzo_neb_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), eb.handle, steps, flag))
+    return flag[] != 0
+end
+
+function count_active(eb::ElasticBand)
+    n = Ref{Int64}(0)
+    check(ccall((:dzo_neb_batch_count_active, libdzo), Cint, (Ptr{Cvoid}, Ref{Int64}), eb.handle, n))
+    return Int(n[])
+end
+
+"""`read_array(eb, what)`: a blocking host copy of one of the NEB_* arrays, in its own element type; the band is the last
+dimension, the image the one before it."""
+function read_array(eb::ElasticBand{T}, what::Integer) where {T}
+    n, m, b = 3 * eb.n_particles, eb.n_images, eb.batch
+    r = what in (NEB_BAND, NEB_VELOCITIES, NEB_FORCES, NEB_TANGENTS) ? Array{T}(undef, n, m, b) :
+        what == NEB_ENERGIES ? Array{T}(undef, m, b) : what == NEB_FORCE_RMS ? Array{Float64}(undef, m, b) :
+        what == NEB_RESIDUALS ? Vector{Float64}(undef, b) : what == NEB_ITERATION_COUNTS ? Vector{Int64}(undef, b) : Vector{Int32}(undef, b)
+    check(ccall((:dzo_neb_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), eb.handle, what, r))
+    return r
+end
+
+"""Device address of one of the NEB_* arrays (no wait)."""
+function array_pointer(eb::ElasticBand, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_neb_batch_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), eb.handle, what, p))
+    return p[]
+end
+
+"""`neb_apply!(band, velocities, n_particles, n_images; ...)`: ONE iteration of every band from the band and the velocities
+given (`dzo_neb_batch_apply`), both moved.  Returns the status of every band as a `Vector{Int32}`; the other records of the
+entry point (energies, gradients, forces, tangents, ...) are not asked for here: an `ElasticBand` stepped once has them.  Blocks."""
+function neb_apply!(band::HipVector{T}, velocities::HipVector{T}, n_particles::Integer, n_images::Integer; spring::Real=1.0, dt::Real=0.02,
+                    max_move::Real=0.1, force_tol::Real=0.0, climb::Bool=true) where {T}
+    batch = div(length(band), 3 * n_particles * n_images)
+    @assert length(band) == 3 * n_particles * n_images * batch && length(velocities) == length(band)
+    # HipVector holds the two floating-point types only: four bytes per band, written as int32 by the kernel and read back as such
+    status = HipVector{Float32}(undef, batch)
+    check(ccall((:dzo_neb_batch_apply, libdzo), Cint,
+                (Cint, Int64, Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cdouble, Cint,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                DZO_RADIAL_LENNARD_JONES, n_particles, n_images, batch, dtype_code(T), band.ptr, velocities.ptr, Float64(spring), Float64(dt),
+                Float64(max_move), Float64(force_tol), climb ? 1 : 0,
+                C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, status.ptr))
+    return collect(reinterpret(Int32, Array(status)))
+end
+
+"""Destroys the handle now (the finalizer would otherwise, at some later collection); the band stays the caller's."""
+function destroy!(eb::ElasticBand)
+    eb.handle != C_NULL && ccall((:dzo_neb_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), eb.handle)
+    eb.handle = C_NULL
+    return nothing
+end
+
+function run_steps!(eb::ElasticBand, max_iterations::Integer, steps_per_call::Integer=100)
+    taken = 0
+    done = count_active(eb) == 0
+    while !done && taken < max_iterations
+        k = min(steps_per_call, max_iterations - taken)
+        done = step!(eb, k)
+        taken += k
+    end
+    return eb
+end
+
+"""`connect_minima(lj_energy, a, b, n_particles, n_images; force_tol, grad_tol=1e-10, max_iterations=10000, refine_steps=100, ...)`:
+interpolates between the minima `a` and `b` (3N elements per pair, in a common frame; neither is changed), relaxes the bands to
+`force_tol`, and refines the climbing image of every CONVERGED band along its tangent with a `HybridModeFollowing`.  Returns a
+named tuple: `band`, `energies` (n_images x batch), `status`, `climbing_images`, `converged` (the indices of the CONVERGED bands),
+`saddles` (3N per converged band), `saddle_energies`, `saddle_status`, `barriers` (batch x 2: from image 1 and from image n_images,
+NaN for a band that did not converge)."""
+function connect_minima(f::typeof(lj_energy), a::HipVector{T}, b::HipVector{T}, n_particles::Integer, n_images::Integer; force_tol::Real,
+                        grad_tol::Real=1e-10, max_iterations::Integer=10000, steps_per_call::Integer=100, refine_steps::Integer=100,
+                        options...) where {T}
+    n3 = 3 * n_particles
+    batch = div(length(a), n3)
+    band = interpolate_band!(HipVector{T}(undef, n3 * n_images * batch), a, b, n_particles, n_images)
+    eb = run_steps!(ElasticBand(f, band, n_particles, n_images; force_tol=force_tol, options...), max_iterations, steps_per_call)
+    energies, status, climbing = read_array(eb, NEB_ENERGIES), read_array(eb, NEB_STATUS), read_array(eb, NEB_CLIMBING_IMAGES)
+    converged = [k for k in 1:batch if status[k] == NEB_CONVERGED && climbing[k] >= 0]
+    saddles, tangents = HipVector{T}(undef, n3 * max(length(converged), 1)), HipVector{T}(undef, n3 * max(length(converged), 1))
+    GC.@preserve eb begin                                   # the tangents are the handle's: it must outlive the copies
+        tangent_ptr = array_pointer(eb, NEB_TANGENTS)
+        for (i, k) in enumerate(converged)
+            offset = ((k - 1) * n_images + Int(climbing[k])) * n3 * sizeof(T)
+            copy!(HipVector{T}(saddles.ptr + (i - 1) * n3 * sizeof(T), n3), HipVector{T}(band.ptr + offset, n3))
+            copy!(HipVector{T}(tangents.ptr + (i - 1) * n3 * sizeof(T), n3), HipVector{T}(tangent_ptr + offset, n3))
+        end
+        synchronize()
+    end
+    destroy!(eb)
+    barriers = fill(T(NaN), batch, 2)
+    saddle_energies, saddle_status = T[], Int32[]
+    if !isempty(converged)
+        search = run_steps!(HybridModeFollowing(f, saddles, n_particles; directions=tangents, grad_tol=grad_tol), refine_steps)
+        saddle_energies, saddle_status = read_array(search, HYBRIDEF_ENERGIES), read_array(search, HYBRIDEF_STATUS)
+        finalize(search)                                    # destroys the handle now; `saddles` stays
+        for (i, k) in enumerate(converged)
+            barriers[k, 1] = saddle_energies[i] - energies[1, k]
+            barriers[k, 2] = saddle_energies[i] - energies[n_images, k]
+        end
+    end
+    return (band=band, energies=energies, status=status, climbing_images=climbing, converged=converged, saddles=saddles,
+            saddle_energies=saddle_energies, saddle_status=saddle_status, barriers=barriers)
 end
 
 ################################################################################ batched AdGD over Lennard-Jones clusters

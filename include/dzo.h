@@ -1009,6 +1009,124 @@ int32_t dzo_structure_batch_classify(int64_t length, int64_t batch, int32_t dtyp
                                      double tol, int32_t *labels_dev /* int32, batch */, int32_t *n_classes /* host */);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched nudged elastic band with a climbing image (Henkelman & Jonsson 2000; Henkelman, Uberuaga & Jonsson 2000) over many
+ * pairs of Lennard-Jones minima: the double-ended search.  The mode-following units above start from one point and end where
+ * they end; a band is strung between two GIVEN minima and relaxed until its highest image sits on the saddle that joins them.
+ * Its output is what those units consume: a transition-state candidate (the climbing image) with a direction (its tangent).
+ * Nothing in the reference relaxes a band: this block is the specification.
+ *
+ * Layout.  A band is n_images = M images of an N-particle cluster; image m of band b sits at element 3N (M b + m), [x | y | z]:
+ * the whole array is a (3N, M batch) points array that dzo_pairwise_batch_energy_gradient evaluates as it is.  Images 0 and
+ * M-1 are the fixed ends.  velocities, forces and tangents have the band's layout (zero at the ends); energies and force_rms
+ * are M per band; residuals, climbing and highest image, status and iteration count are one per band.
+ * 3 <= n_images <= DZO_NEB_MAX_IMAGES = 32, n_particles <= DZO_NEB_MAX_PARTICLES = 1024.  The ends must be given in a common
+ * frame (no rigid or permutational alignment is done here; the two quenched sides of one saddle are in one).
+ *
+ * Launch shapes of the step kernel (dzo_neb_plan tells).  One 256-thread block per band, `steps` iterations per launch, the
+ * phases of an iteration separated by workgroup barriers only: no grid-wide synchronisation, no atomics, no host wait inside or
+ * between launches.  DZO_NEB_SHAPE_WAVE, n_particles <= 64: the interior images are dealt round-robin to the four waves
+ * (image m to wave (m - 1) mod 4), lane i holds particle i.  DZO_NEB_SHAPE_BLOCK, 65 .. 1024: the block takes the images one
+ * after another, thread t owns particles t + 256 q, the image under evaluation staged in LDS.  DZO_NEB_STORAGE_LDS: band,
+ * velocities and forces live in LDS for the whole launch, whenever 768 bytes, the stage (3N elements, BLOCK shape only) and
+ * 3 * 3N M elements fit the 159 KiB of dynamic LDS the cluster units allow; that always holds for the WAVE shape.  Otherwise
+ * DZO_NEB_STORAGE_MEMORY: the same kernel body on the caller's band and the handle's velocities and forces in device memory.
+ * Both storages compute the same bits.
+ *
+ * One iteration, per band (T = the element type, n = 3N; every operation in T with one rounding, no contraction, IEEE division
+ * and square root, unless fp64 is named; "fp64" names operations in double precision on values converted exactly from T).
+ * Every sum over the particles is in fp64 in THE ORDER OF THE SUMS of the cluster units (a thread's particles in order, the wave
+ * tree, in the BLOCK shape the four waves in wave order), a dot a.b with its three terms per particle.  Inputs: the band x, the
+ * velocities v; spring > 0, dt > 0, max_move > 0, force_tol >= 0 (all fp64; dt also rounded once to T), climb, climb_after.
+ * A band whose status is not ACTIVE is left alone.
+ *  1. Evaluate.  E_m and g_m of every interior image, with the bits of dzo_pairwise_batch_energy_gradient.  The ends are
+ *     evaluated once, at create (by apply: in the call), and feel no force.
+ *  2. Improved tangent of every interior m.  d+ = x_{m+1} - x_m and d- = x_m - x_{m-1}, element by element in T.
+ *     If E_{m+1} > E_m > E_{m-1}: t = d+.  If E_{m+1} < E_m < E_{m-1}: t = d-.  Otherwise, with (in T)
+ *     a = max(|E_{m+1} - E_m|, |E_{m-1} - E_m|) and b = min of the same two: t_e = fma(a, d+_e, b d-_e) if E_{m+1} > E_{m-1},
+ *     else t_e = fma(b, d+_e, a d-_e).  tau_e = T(t_e / sqrt(t.t)), the root and the quotient in fp64: unit length.
+ *  3. Force.  c = g_m.tau (fp64), w = spring (sqrt(d+.d+) - sqrt(d-.d-)) (fp64).
+ *     F_e = T(-(g_e - c tau_e) + w tau_e), every operation in fp64: the gradient with its component along the band taken
+ *     out, and the spring force along the band only.  The climbing image feels F_e = T(-g_e + (c + c) tau_e) instead: the
+ *     gradient with its component along the band turned uphill, no spring.  The climbing image exists when climb != 0 and the
+ *     band's iteration count is >= climb_after (apply: when climb != 0); it is the interior image of highest E, the first one
+ *     in index order (compared with > in T).
+ *  4. Residual and status.  frms_m = sqrt((F_m.F_m) / n) in fp64, residual = max_m frms_m.  Any E_m (the ends included) or
+ *     F_m.F_m non-finite (which any non-finite g or F makes so): status FAILED.  Otherwise residual <= force_tol: status
+ *     CONVERGED.  In both cases nothing moves, and the band is frozen for all later iterations with these records.
+ *  5. Move, per interior image, by projected velocity Verlet.  p = v.F (fp64).  If p > 0, v_e = T((p / F.F) F_e), quotient
+ *     and product in fp64; else v_e = 0.  v_e = fma(T(dt), F_e, v_e).  s_e = T(dt) v_e.  If sqrt(s.s) > max_move (fp64),
+ *     s_e = T((max_move / sqrt(s.s)) s_e) in fp64.  x_e = x_e + s_e.  Iteration count += 1.
+ *  6. Every force of an iteration is computed from the band as it stood at the start of that iteration, not from images
+ *     already moved.
+ * The records are those of the band BEFORE the move of the last iteration made: energies, forces, tangents, force_rms (zero
+ * at the ends), residual, the climbing image (-1 while none climbs) and the highest image.
+ * No floating-point atomics; one writer per element; every loop is bounded by an argument.  A band computes the same bits alone
+ * or anywhere in any batch, and a handle in one call of k steps or k calls of one.
+ * CONVERGED says that the forces of the band vanish to force_tol.  With a climbing image that makes the climbing image a
+ * stationary point of the energy to force_tol; whether it is a first-order saddle is for the spectrum to say.
+ * Out of scope: alignment of arbitrary end pairs, the doubly-nudged spring term, L-BFGS on the band, other radials.
+ *
+ * dzo_neb_batch_interpolate writes the straight band between a_dev and b_dev (3N, batch): images 0 and M-1 are copies of a
+ * and b, and x_m = fma(T(m / (M-1)), b - a, a) in between (the quotient in fp64, rounded once).  One launch; blocking.
+ * dzo_neb_batch_apply is ONE iteration from the caller's band and velocities (both moved); it sets every status to ACTIVE
+ * first and evaluates the ends itself.  Record outputs other than status_dev may be NULL; gradients_dev receives g of every
+ * image, the ends included.  Blocking.
+ * A handle ALIASES band_dev and owns the velocities (zero at create) and the records; create evaluates the ends.  step
+ * enqueues ONE launch for `steps` iterations; all_done may be NULL (then no host wait).
+ *
+ * Errors follow the neighbours: unknown radial or dtype, sizes < 1, n_images outside 3 .. 32, spring, dt or max_move <= 0, a
+ * negative tolerance or count, null pointers, unknown `what` DZO_ERR_INVALID; n_particles > 1024 DZO_ERR_UNSUPPORTED; a host
+ * pointer where a device pointer is required DZO_ERR_ASSERT; no memory for the state DZO_ERR_NOMEM.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_NEB_MAX_PARTICLES 1024
+#define DZO_NEB_MAX_IMAGES 32
+/* status */
+#define DZO_NEB_ACTIVE 0
+#define DZO_NEB_CONVERGED 1
+#define DZO_NEB_FAILED 2
+/* what dzo_neb_plan tells */
+#define DZO_NEB_SHAPE_WAVE 0
+#define DZO_NEB_SHAPE_BLOCK 1
+#define DZO_NEB_STORAGE_LDS 0
+#define DZO_NEB_STORAGE_MEMORY 1
+/* `what` of get_ptr / read (T = the handle's element type, M = n_images) */
+#define DZO_NEB_BAND 0                /* T, 3N M batch: the caller's array */
+#define DZO_NEB_VELOCITIES 1          /* T, 3N M batch */
+#define DZO_NEB_FORCES 2              /* T, 3N M batch: F of the last iteration, before its move */
+#define DZO_NEB_TANGENTS 3            /* T, 3N M batch: tau likewise */
+#define DZO_NEB_ENERGIES 4            /* T, M batch */
+#define DZO_NEB_FORCE_RMS 5           /* fp64, M batch */
+#define DZO_NEB_RESIDUALS 6           /* fp64, batch */
+#define DZO_NEB_CLIMBING_IMAGES 7     /* int32, batch: -1 before climbing starts */
+#define DZO_NEB_HIGHEST_IMAGES 8      /* int32, batch */
+#define DZO_NEB_STATUS 9              /* int32, batch */
+#define DZO_NEB_ITERATION_COUNTS 10   /* int64, batch: moves made */
+typedef struct dzo_neb_batch_s *dzo_neb_batch_t;
+/* launch shape, storage and dynamic LDS of a band; a pure function, needs no device.  Outputs may be NULL. */
+int32_t dzo_neb_plan(int64_t n_particles, int32_t n_images, int32_t dtype, int32_t *shape, int32_t *storage, int64_t *lds_bytes);
+/* a_dev, b_dev: (3N, batch).  band_dev: (3N, M batch), written. */
+int32_t dzo_neb_batch_interpolate(int64_t n_particles, int32_t n_images, int64_t batch, int32_t dtype, const void *a_dev,
+                                  const void *b_dev, void *band_dev);
+/* the iteration above, once, on every band, from the caller's band and velocities */
+int32_t dzo_neb_batch_apply(int32_t radial, int64_t n_particles, int32_t n_images, int64_t batch, int32_t dtype, void *band_dev,
+                            void *velocities_dev, double spring, double dt, double max_move, double force_tol, int32_t climb,
+                            void *energies_dev, void *gradients_dev, void *forces_dev, void *tangents_dev,
+                            double *force_rms_dev, double *residuals_dev, int32_t *climbing_dev, int32_t *highest_dev,
+                            int32_t *status_dev);
+/* band_dev: (3N, M batch), ALIASED.  Blocking. */
+int32_t dzo_neb_batch_create(int32_t radial, int64_t n_particles, int32_t n_images, int64_t batch, int32_t dtype, void *band_dev,
+                             double spring, double dt, double max_move, double force_tol, int32_t climb, int64_t climb_after,
+                             dzo_neb_batch_t *out);
+int32_t dzo_neb_batch_destroy(dzo_neb_batch_t h);
+/* `steps` iterations of every ACTIVE band in one launch; all_done may be NULL (then no host wait) */
+int32_t dzo_neb_batch_step(dzo_neb_batch_t h, int32_t steps, int32_t *all_done);
+/* bands with status ACTIVE.  Blocking. */
+int32_t dzo_neb_batch_count_active(dzo_neb_batch_t h, int64_t *active);
+/* device address of an array above (no wait) / a blocking copy of it to host memory, in the array's own element type */
+int32_t dzo_neb_batch_get_ptr(dzo_neb_batch_t h, int32_t what, void **ptr_dev);
+int32_t dzo_neb_batch_read(dzo_neb_batch_t h, int32_t what, void *out_host);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
