@@ -224,6 +224,8 @@ ABI = {
     "dzo_neb_batch_create": [_i32, _i64, _i32, _i64, _i32, _vp, _dbl, _dbl, _dbl, _dbl, _i32, _i64, _P(_vp)],
     "dzo_neb_batch_destroy": [_vp], "dzo_neb_batch_step": [_vp, _i32, _P(_i32)], "dzo_neb_batch_count_active": [_vp, _P(_i64)],
     "dzo_neb_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_neb_batch_read": [_vp, _i32, _vp],
+    "dzo_align_batch_assign": [_i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "dzo_align_batch_pairs": [_i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dzo_structure_batch_fingerprint": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
     "dzo_structure_batch_classify": [_i64, _i64, _i32, _vp, _dbl, _vp, _P(_i32)],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
@@ -1513,23 +1515,30 @@ class BandConnections:
     ``(batch,)``); ``converged`` (host indices of the CONVERGED bands); ``saddles`` (DeviceArray ``(len(converged), 3N)``: their
     climbing images after the refinement), ``saddle_energies``, ``saddle_status`` (``HYBRIDEF_*``), ``saddle_eigenvalues`` and
     ``saddle_grms`` (host, per converged band); ``barriers`` (host ``(batch, 2)``: refined saddle energy minus the energy of
-    image 0 and of image M - 1, NaN for a band that did not converge)."""
+    image 0 and of image M - 1, NaN for a band that did not converge); ``alignment`` (the ``Alignment`` of the end pairs, only
+    when ``connect_minima`` was asked to align them)."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
 
 
 def connect_minima(a, b, n_particles, n_images, force_tol, grad_tol=1e-10, max_iterations=10000, steps_per_call=100, refine_steps=100,
-                   radial=RADIAL_LENNARD_JONES, **band_options):
+                   radial=RADIAL_LENNARD_JONES, align=False, **band_options):
     """The double-ended search: what joins minimum ``a[k]`` to minimum ``b[k]``, and how high is the barrier.  ``a`` and ``b``
     are DeviceArrays of ``3 * n_particles * batch`` elements in a common frame (no alignment is done: the two ``ends`` of one
-    saddle in ``connect_saddles`` are in one); neither is changed.  Interpolates (``interpolate_band``), relaxes the bands
-    (``ElasticBand`` with ``band_options``: spring, dt, max_move, climb_after) to ``force_tol`` in at most ``max_iterations``
+    saddle in ``connect_saddles`` are in one); neither is changed.  ``align=True``, or a dict of ``align_pairs`` options, brings
+    arbitrary pairs into one first: ``b`` is replaced by ``align_pairs(a, b, n_particles, **options).aligned`` and the result
+    carries the ``Alignment`` as ``alignment``; with the default nothing of that happens.  Interpolates (``interpolate_band``),
+    relaxes the bands (``ElasticBand`` with ``band_options``: spring, dt, max_move, climb_after) to ``force_tol`` in at most ``max_iterations``
     iterations, then takes the climbing image and its tangent of every CONVERGED band and refines them with
     ``HybridModeFollowing(directions=tangent)`` to ``grad_tol`` in at most ``refine_steps`` steps.  Returns a
     ``BandConnections``.  ``force_tol`` has no default, like ``tol`` in ``connect_saddles``: it depends on the element type."""
     n, batch = _batch_of(a, n_particles, "a", least=1)
     m, n3, es = int(n_images), 3 * n, a.dtype.itemsize
+    extra = {}
+    if align is not False and align is not None:
+        extra["alignment"] = align_pairs(a, b, n, **(align if isinstance(align, dict) else {}))
+        b = extra["alignment"].aligned
     band = interpolate_band(a, b, n, m)
     neb = ElasticBand(band, n, m, force_tol=force_tol, radial=radial, **band_options)
     try:
@@ -1559,7 +1568,69 @@ def connect_minima(a, b, n_particles, n_images, force_tol, grad_tol=1e-10, max_i
             search.close()
         barriers[converged] = fields["saddle_energies"][:, None] - energies[converged][:, [0, m - 1]]
     return BandConnections(band=band, energies=energies, status=status, climbing_images=climbing, iteration_counts=counts, residuals=residuals,
-                           converged=converged, saddles=saddles, barriers=barriers, **fields)
+                           converged=converged, saddles=saddles, barriers=barriers, **fields, **extra)
+
+
+# ------------------------------------------------------------------------------ rigid and permutational alignment of pairs
+ALIGN_MAX_PARTICLES = 1024
+ALIGN_MAX_RANDOM_TRIALS = 64
+ALIGN_MAX_CYCLES = 64
+ALIGN_TRIAL_IDENTITY, ALIGN_TRIAL_PRINCIPAL = 1, 2
+ALIGN_CONVERGED, ALIGN_CYCLE_LIMIT, ALIGN_FAILED = 0, 1, 2
+
+
+def _pair_of(a, b, n_particles):
+    """``(n, batch)`` of two arrays of ``3 * n_particles * batch`` elements of one element type."""
+    n, batch = _batch_of(a, n_particles, "a", least=1)
+    _batch_of(b, n_particles, "b", batch=batch)
+    assert b.dtype == a.dtype, "a and b must have one element type"
+    return n, batch
+
+
+def assign_particles(a, b, n_particles):
+    """``dzo_align_batch_assign``: for every pair of points ``a[k]``, ``b[k]`` (DeviceArrays of ``3 * n_particles * batch``
+    elements, ``[x | y | z]``; neither is changed) the permutation p that minimises ``sum_i |a_i - b_p(i)|^2`` in the frames
+    given, by the shortest augmenting path in fp64 on the device.  Returns ``(perm, cost)``: host int32 ``(batch, N)`` and
+    host float64 ``(batch,)``.  A pair with a non-finite coordinate gets the identity and NaN."""
+    n, batch = _pair_of(a, b, n_particles)
+    perm, cost = DeviceArray((batch, n), np.int32), DeviceArray((batch,), np.float64)
+    _check(lib().dzo_align_batch_assign(n, batch, _dt(a.dtype), a.ptr, b.ptr, perm.ptr, cost.ptr))
+    return perm.to_host(), cost.to_host()
+
+
+class Alignment:
+    """What ``align_pairs`` returns.  ``aligned``: DeviceArray ``(batch, 3N)``, ``b`` in ``a``'s frame with ``a``'s labels;
+    ``permutations`` (host int32 ``(batch, N)``: particle i of ``a`` is particle ``p[i]`` of ``b``); ``rotations`` (host float64
+    ``(batch, 3, 3)``, the inversion folded in: det = +-1); ``distances`` (host float64 ``(batch,)``); ``best_trials``,
+    ``cycles`` and ``status`` (host int32 ``(batch,)``, ``ALIGN_CONVERGED`` / ``ALIGN_CYCLE_LIMIT`` / ``ALIGN_FAILED``, of the
+    winning start); ``trial_distances`` (host float64 ``(batch, n_starts)`` when asked for, else None)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def align_pairs(a, b, n_particles, trials=ALIGN_TRIAL_IDENTITY | ALIGN_TRIAL_PRINCIPAL, random_trials=8, max_cycles=20,
+                allow_inversion=False, seed=0, want_trials=False):
+    """``dzo_align_batch_pairs`` (include/dzo.h states the rule): brings every ``b[k]`` onto ``a[k]`` by a translation, a
+    rotation, a relabelling of its identical particles and, with ``allow_inversion``, an inversion, so that
+    ``sum_i |a_i - x'_i|^2`` is small.  From every start (the identity, the four principal-axis rotations, ``random_trials``
+    random ones from the stream ``seed``; all of them once more inverted) it alternates the optimal assignment with the best
+    rotation until the permutation repeats, ``max_cycles`` cycles at most, and keeps the best start.  ``a`` and ``b`` are
+    DeviceArrays of ``3 * n_particles * batch`` elements; neither is changed.  A multi-start local method: the distance is an
+    upper bound of the true one (the ``align-readme`` block of README.md has what it finds).  Returns an ``Alignment``."""
+    n, batch = _pair_of(a, b, n_particles)
+    n_orient = (int(trials) & 1) + 4 * ((int(trials) >> 1) & 1) + int(random_trials)
+    n_starts = (2 if allow_inversion else 1) * n_orient
+    aligned = DeviceArray((batch, 3 * n), a.dtype)
+    perm, rot, dist = DeviceArray((batch, n), np.int32), DeviceArray((batch, 3, 3), np.float64), DeviceArray((batch,), np.float64)
+    best, cycles, status = (DeviceArray((batch,), np.int32) for _ in range(3))
+    per_trial = DeviceArray((batch, max(n_starts, 1)), np.float64) if want_trials else None
+    _check(lib().dzo_align_batch_pairs(n, batch, _dt(a.dtype), a.ptr, b.ptr, int(trials), int(random_trials), int(max_cycles),
+                                       int(bool(allow_inversion)), _u64(seed), aligned.ptr, perm.ptr, rot.ptr, dist.ptr, best.ptr,
+                                       cycles.ptr, status.ptr, per_trial.ptr if want_trials else None))
+    return Alignment(aligned=aligned, permutations=perm.to_host(), rotations=rot.to_host(), distances=dist.to_host(),
+                     best_trials=best.to_host(), cycles=cycles.to_host(), status=status.to_host(),
+                     trial_distances=per_trial.to_host() if want_trials else None)
 
 
 # ------------------------------------------------------------------------------ profiling
@@ -2366,7 +2437,7 @@ __all__ = [
     "symmetric_batch_eigen", "hessian_spectrum", "LowestModes", "lowest_modes", "modefollow_apply", "ModeFollowing",
     "polish_minima", "find_saddles", "hybridef_apply", "HybridModeFollowing", "find_saddles_hybrid", "structure_fingerprints",
     "classify_structures", "unique_structures", "Pathways", "quench_to_rest", "connect_saddles", "neb_plan", "interpolate_band",
-    "neb_apply", "ElasticBand", "BandConnections", "connect_minima", "profile_enable",
+    "neb_apply", "ElasticBand", "BandConnections", "connect_minima", "assign_particles", "Alignment", "align_pairs", "profile_enable",
     "profile_reset", "unsealed_first_reads", "profile_table", "Problem", "NativeCallbacks", "LineSearchEvaluator",
     "LBFGSOptimizer", "AdGDOptimizer", "BFGSOptimizer", "GradientDescentOptimizer", "update_inverse_hessian_",
     "update_inverse_hessian_mfma_", "symv_", "BatchedBFGS", "Comm", "batches_all_done", "step_",

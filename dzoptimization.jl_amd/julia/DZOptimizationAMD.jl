@@ -37,6 +37,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        HybridModeFollowing, hybridef_apply!, find_saddles_hybrid, HYBRIDEF_ACTIVE, HYBRIDEF_CONVERGED, HYBRIDEF_FAILED,
        structure_fingerprints, classify_structures, connect_saddles,
        ElasticBand, interpolate_band!, neb_apply!, neb_plan, connect_minima, NEB_ACTIVE, NEB_CONVERGED, NEB_FAILED,
+       assign_particles, align_pairs, ALIGN_TRIAL_IDENTITY, ALIGN_TRIAL_PRINCIPAL, ALIGN_CONVERGED, ALIGN_CYCLE_LIMIT, ALIGN_FAILED,
        BasinHopping, hop!, set_record!, set_array!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
@@ -1147,17 +1148,73 @@ function run_steps!(eb::ElasticBand, max_iterations::Integer, steps_per_call::In
     return eb
 end
 
+################################################################################ rigid and permutational alignment of pairs
+# (not exercised in the build container either; the Python functions of the same names bind the same entry points and ARE tested)
+const ALIGN_MAX_PARTICLES, ALIGN_MAX_RANDOM_TRIALS, ALIGN_MAX_CYCLES = 1024, 64, 64
+const ALIGN_TRIAL_IDENTITY, ALIGN_TRIAL_PRINCIPAL = 1, 2
+const ALIGN_CONVERGED, ALIGN_CYCLE_LIMIT, ALIGN_FAILED = 0, 1, 2
+
+# int32 results come back through four-byte device vectors (the method of classify_structures)
+int32_array(v::HipVector{Float32}) = collect(reinterpret(Int32, Array(v)))
+
+"""`assign_particles(a, b, n_particles)`: for every pair of points (3N elements each, `[x | y | z]`; neither is changed) the
+permutation p that minimises `sum_i |a_i - b_p(i)|^2` in the frames given, by the shortest augmenting path in fp64 on the device
+(`dzo_align_batch_assign`).  Returns `(perm::Matrix{Int32} (N x batch, 0-based as the library numbers them), cost::Vector{Float64})`.
+Blocks."""
+function assign_particles(a::HipVector{T}, b::HipVector{T}, n_particles::Integer) where {T}
+    batch = div(length(a), 3 * n_particles)
+    @assert length(a) == 3 * n_particles * batch && length(b) == length(a) && batch >= 1
+    perm = HipVector{Float32}(undef, n_particles * batch)
+    cost = HipVector{Float64}(undef, batch)
+    check(ccall((:dzo_align_batch_assign, libdzo), Cint, (Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                n_particles, batch, dtype_code(T), a.ptr, b.ptr, perm.ptr, cost.ptr))
+    return reshape(int32_array(perm), Int(n_particles), batch), Array(cost)
+end
+
+"""`align_pairs(a, b, n_particles; trials=ALIGN_TRIAL_IDENTITY | ALIGN_TRIAL_PRINCIPAL, random_trials=8, max_cycles=20,
+allow_inversion=false, seed=0, want_trials=false)`: brings every `b[k]` onto `a[k]` by a translation, a rotation, a relabelling of
+its identical particles and, with `allow_inversion`, an inversion (`dzo_align_batch_pairs`; include/dzo.h states the rule).
+Returns a named tuple: `aligned` (a HipVector, 3N per pair: b in a's frame with a's labels), `permutations` (N x batch, 0-based),
+`rotations` (9 x batch, row-major, the inversion folded in), `distances`, `best_trials`, `cycles`, `status`, and
+`trial_distances` (n_starts x batch, or `nothing`).  Blocks."""
+function align_pairs(a::HipVector{T}, b::HipVector{T}, n_particles::Integer; trials::Integer=ALIGN_TRIAL_IDENTITY | ALIGN_TRIAL_PRINCIPAL,
+                     random_trials::Integer=8, max_cycles::Integer=20, allow_inversion::Bool=false, seed::Integer=0,
+                     want_trials::Bool=false) where {T}
+    batch = div(length(a), 3 * n_particles)
+    @assert length(a) == 3 * n_particles * batch && length(b) == length(a) && batch >= 1
+    n_orient = (trials & 1) + 4 * ((trials >> 1) & 1) + random_trials
+    n_starts = (allow_inversion ? 2 : 1) * n_orient
+    aligned = HipVector{T}(undef, 3 * n_particles * batch)
+    perm = HipVector{Float32}(undef, n_particles * batch)
+    rotation, distance = HipVector{Float64}(undef, 9 * batch), HipVector{Float64}(undef, batch)
+    best, cycles, status = HipVector{Float32}(undef, batch), HipVector{Float32}(undef, batch), HipVector{Float32}(undef, batch)
+    per_trial = want_trials ? HipVector{Float64}(undef, max(n_starts, 1) * batch) : nothing
+    check(ccall((:dzo_align_batch_pairs, libdzo), Cint,
+                (Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                n_particles, batch, dtype_code(T), a.ptr, b.ptr, trials, random_trials, max_cycles, allow_inversion ? 1 : 0,
+                seed % UInt64, aligned.ptr, perm.ptr, rotation.ptr, distance.ptr, best.ptr, cycles.ptr, status.ptr,
+                want_trials ? per_trial.ptr : C_NULL))
+    return (aligned=aligned, permutations=reshape(int32_array(perm), Int(n_particles), batch), rotations=reshape(Array(rotation), 9, batch),
+            distances=Array(distance), best_trials=int32_array(best), cycles=int32_array(cycles), status=int32_array(status),
+            trial_distances=want_trials ? reshape(Array(per_trial), max(n_starts, 1), batch) : nothing)
+end
+
 """`connect_minima(lj_energy, a, b, n_particles, n_images; force_tol, grad_tol=1e-10, max_iterations=10000, refine_steps=100, ...)`:
 interpolates between the minima `a` and `b` (3N elements per pair, in a common frame; neither is changed), relaxes the bands to
-`force_tol`, and refines the climbing image of every CONVERGED band along its tangent with a `HybridModeFollowing`.  Returns a
+`force_tol`, and refines the climbing image of every CONVERGED band along its tangent with a `HybridModeFollowing`.
+`align=true`, or a named tuple of `align_pairs` options, brings arbitrary pairs into a common frame first (`b` is replaced by the
+aligned copy, and the result carries `alignment`; it is `nothing` otherwise).  Returns a
 named tuple: `band`, `energies` (n_images x batch), `status`, `climbing_images`, `converged` (the indices of the CONVERGED bands),
 `saddles` (3N per converged band), `saddle_energies`, `saddle_status`, `barriers` (batch x 2: from image 1 and from image n_images,
 NaN for a band that did not converge)."""
 function connect_minima(f::typeof(lj_energy), a::HipVector{T}, b::HipVector{T}, n_particles::Integer, n_images::Integer; force_tol::Real,
                         grad_tol::Real=1e-10, max_iterations::Integer=10000, steps_per_call::Integer=100, refine_steps::Integer=100,
-                        options...) where {T}
+                        align=false, options...) where {T}
     n3 = 3 * n_particles
     batch = div(length(a), n3)
+    alignment = align === false ? nothing : align_pairs(a, b, n_particles; (align === true ? NamedTuple() : align)...)
+    alignment === nothing || (b = alignment.aligned)
     band = interpolate_band!(HipVector{T}(undef, n3 * n_images * batch), a, b, n_particles, n_images)
     eb = run_steps!(ElasticBand(f, band, n_particles, n_images; force_tol=force_tol, options...), max_iterations, steps_per_call)
     energies, status, climbing = read_array(eb, NEB_ENERGIES), read_array(eb, NEB_STATUS), read_array(eb, NEB_CLIMBING_IMAGES)
@@ -1185,7 +1242,7 @@ function connect_minima(f::typeof(lj_energy), a::HipVector{T}, b::HipVector{T}, 
         end
     end
     return (band=band, energies=energies, status=status, climbing_images=climbing, converged=converged, saddles=saddles,
-            saddle_energies=saddle_energies, saddle_status=saddle_status, barriers=barriers)
+            saddle_energies=saddle_energies, saddle_status=saddle_status, barriers=barriers, alignment=alignment)
 end
 
 ################################################################################ batched AdGD over Lennard-Jones clusters

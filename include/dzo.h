@@ -1127,6 +1127,111 @@ int32_t dzo_neb_batch_get_ptr(dzo_neb_batch_t h, int32_t what, void **ptr_dev);
 int32_t dzo_neb_batch_read(dzo_neb_batch_t h, int32_t what, void *out_host);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched rigid and permutational alignment of pairs of clusters of identical particles (the minpermdist of Wales' OPTIM, as
+ * used in GMIN / PATHSAMPLE): for every pair (A, B) a rotation R, a sign s and a permutation p that make
+ * sum_i |a_i - R s b_p(i)|^2 small, centroids removed.  dzo_neb_batch_* and the double-ended search built on it need their two
+ * ends in a common frame and leave "alignment of arbitrary end pairs" out of scope: this block supplies it.  Nothing in the
+ * reference aligns structures: this block is the specification.  No potential is involved, so there is no `radial`.
+ *
+ * a_dev and b_dev are (3N, batch), pair k [x | y | z] at element 3N k, the layout of every dzo_*_batch_* unit; neither is
+ * changed.  1 <= n_particles <= DZO_ALIGN_MAX_PARTICLES = 1024.  All arithmetic below is fp64 on values widened exactly from T,
+ * every operation rounded once, no contraction except the fma named, IEEE division and square root; so the permutations do
+ * not depend on the element type beyond the input values.
+ *
+ * THE ORDER OF EVERY SUM over particles: column j (a particle of B) belongs to lane j mod 64 of the pair's wave; a lane adds
+ * the terms of its columns j = l, l + 64, ... in that order onto 0, lanes without a column hold 0, and the 64 lane sums are
+ * added by the wave tree of the dzo_*_batch_* units (offsets 32, 16, 8, 4, 2, 1).  A sum over rows i is taken over the columns
+ * j = p(i) in this order.
+ *
+ * Assignment (dzo_align_batch_assign, and step 1 of a cycle): the permutation p, row i of A -> column p(i) of B, that
+ * minimises sum_i c(i, p(i)), c(i, j) = fma(dz, dz, fma(dy, dy, dx dx)) with dx = a_i.x - b_j.x and dy, dz alike.  No N x N
+ * matrix is stored.  The method is the shortest augmenting path with row potentials u and column potentials v, all zero at
+ * the start.  Rows are taken in index order.  For row i: every slack is +inf, no column is visited; the path starts at a
+ * virtual column whose row is i.  Repeat, at most N + 1 times: let i0 be the row of the path's last column; for every
+ * unvisited column j ascending, cur = (c(i0, j) - u[i0]) - v[j], and if cur < slack[j] then slack[j] = cur and the
+ * predecessor of j is the path's last column; delta = the smallest slack of the unvisited columns, j1 the lowest column that
+ * has it; u += delta on the rows of the visited columns and on row i, v -= delta on the visited columns, slack -= delta on
+ * the unvisited ones; j1 is visited and becomes the path's last column; stop when j1 has no row.  Then the rows move one
+ * column along the predecessors, from j1 back to the virtual column.  cost_dev = sum_i c(i, p(i)) in the order above.
+ *
+ * Pairs (dzo_align_batch_pairs).  c_A and c_B are the centroids (the sum of each coordinate, divided by N); a_i and b_j below
+ * are a_i - c_A and s (b_j - c_B).  Starts: n_orient first rotations R_0, in this order: the identity, if trials has
+ * DZO_ALIGN_TRIAL_IDENTITY; the four principal ones, if it has DZO_ALIGN_TRIAL_PRINCIPAL; random_trials random ones
+ * (<= DZO_ALIGN_MAX_RANDOM_TRIALS = 64).  With allow_inversion the same n_orient rotations follow once more with s = -1:
+ * n_starts = (allow_inversion ? 2 : 1) n_orient, start t has orientation t mod n_orient.
+ *   Principal: the second moments (xx, xy, xz, yy, yz, zz; sums of plain products) of A and of B make two symmetric 3 x 3
+ *   matrices; cyclic Jacobi (below) gives their eigenvectors; the columns are ordered by eigenvalue ascending, equal ones by
+ *   index, and the third is negated if the determinant is negative: frames F_A, F_B.  R_0 = F_A D F_B^T, element (r, c) =
+ *   (d0 F_A[r][0] F_B[c][0] + d1 F_A[r][1] F_B[c][1]) + d2 F_A[r][2] F_B[c][2], D = (+,+,+), (+,-,-), (-,+,-), (-,-,+).
+ *   Random: the PCG32 XSH-RR stream of dzo_tempering_* seeded with `seed` (state = A (C + seed) + C), jumped ahead by
+ *   4 r draws for random trial r.  Every pair of a call is given the same random rotations: the stream is selected by the seed
+ *   and the trial index alone, so a pair draws the same numbers alone or anywhere in a batch, and with any other trial
+ *   count.  The draws d1 .. d4 give u_m = (d_m + 1/2) 2^-32, r1 = sqrt(-2 log u1), r2 = sqrt(-2 log u3), the
+ *   quaternion (w, x, y, z) = (r1 cospi(2 u2), r1 sinpi(2 u2), r2 cospi(2 u4), r2 sinpi(2 u4)), four standard normals, and
+ *   R_0 is its rotation (below).  The inverted copy of a random start uses the same rotation.
+ * One cycle of a start, at most max_cycles (<= DZO_ALIGN_MAX_CYCLES = 64): (1) b'_j = R b_j, each coordinate
+ * (R0 x + R1 y) + R2 z, and the assignment above between A and b'; (2) Horn's rotation for that assignment: the nine sums
+ * S_uv = sum b_p(i).u a_i.v, the symmetric 4 x 4 matrix H00 = (Sxx + Syy) + Szz, H11 = (Sxx - Syy) - Szz,
+ * H22 = (Syy - Sxx) - Szz, H33 = (Szz - Sxx) - Syy, H01 = Syz - Szy, H02 = Szx - Sxz, H03 = Sxy - Syx, H12 = Sxy + Syx,
+ * H13 = Szx + Sxz, H23 = Syz + Szy, its eigenvectors by cyclic Jacobi, the one of the largest eigenvalue (the first among
+ * equals) as the quaternion (w, x, y, z); R is its rotation.  The start ends DZO_ALIGN_CONVERGED when a cycle's permutation
+ * is the previous cycle's (so after two cycles at least), DZO_ALIGN_CYCLE_LIMIT after max_cycles cycles.  Its distance is
+ * sqrt(sum_i |a_i - R b_p(i)|^2) with the last permutation and the last rotation, the squares as in c(i, j).
+ *   Rotation of a quaternion: n = sqrt((ww + xx) + (yy + zz)), every component divided by n, then R00 = (ww + xx) - (yy + zz),
+ *   R01 = 2 (xy - wz), R02 = 2 (xz + wy), R10 = 2 (xy + wz), R11 = (ww - xx) + (yy - zz), R12 = 2 (yz - wx),
+ *   R20 = 2 (xz - wy), R21 = 2 (yz + wx), R22 = (ww - xx) - (yy - zz).
+ *   Cyclic Jacobi of a D x D matrix M: V = 1; at most 12 sweeps over the pairs (p, q), p < q, in row order; a pair with
+ *   M_pq == 0 is skipped, a sweep that skips every pair ends it.  theta = (M_qq - M_pp) / (M_pq + M_pq),
+ *   g = sqrt(theta theta + 1), t = 1 / (theta + g) if theta >= 0 else -1 / (g - theta), c = 1 / sqrt(t t + 1), s = t c; for
+ *   every k columns p and q of M and of V become (c m_kp - s m_kq, s m_kp + c m_kq), then rows p and q of M likewise, then
+ *   M_pq = M_qp = 0.  Eigenvalues are the diagonal, eigenvectors the columns of V.  N = 1 and N = 2 give rank-deficient
+ *   matrices and finite answers: a zero matrix keeps V = 1.
+ * The pair's result is the start with the smallest distance, the first in index order among equals; status_dev, cycles_dev
+ * and best_trial_dev are that start's.  aligned_dev: x'_i = ((R0 x + R1 y) + R2 z) + c_A.x ... of (b_p(i) - c_B) with the
+ * signed rotation s R, rounded once to T: B in A's frame with A's labels, so dzo_neb_batch_interpolate(a, aligned) is the
+ * straight band.  perm_dev: p, int32 (N, batch).  rotation_dev: s R, row-major, fp64 (9, batch), det = +-1.  distance_dev:
+ * from the unrounded values.  trial_distances_dev: every start's distance, (n_starts, batch); may be NULL.
+ * A pair with any non-finite coordinate is detected before any loop runs: status DZO_ALIGN_FAILED, the identity permutation,
+ * aligned = b, the identity rotation, distance (every trial distance; the cost of assign) NaN, cycles and best trial 0.
+ *
+ * Launches: one wave per (pair, start), batch n_starts independent waves; lane l holds the rotated coordinates, potentials,
+ * slacks and visited flags of columns l + 64 q in registers (instantiated for 1, 4 and 16 columns per lane: N <= 64, 256,
+ * 1024); A, the row potentials and three 16-bit index arrays in LDS, 38 N + 8 bytes: 38 920 at N = 1024, four waves per
+ * compute unit of 160 KiB, one per SIMD.  The argmin is a wave reduction through DPP and permlane moves: a column scan waits
+ * for no other wave.  A second kernel, one wave per pair, picks the best start and writes the outputs.  No floating-point
+ * atomics, no atomics at all; every output element is written once; every loop is bounded by a count known at entry (a path
+ * by N + 1 columns, the cycles by max_cycles, a Jacobi by its 12 sweeps) and no NaN can keep one alive: the next column is an
+ * index out of the unvisited ones whatever the values are.  A pair computes the same bits alone or anywhere in any batch.
+ * Both calls block; the workspace (192 + 4 N bytes per start) is allocated and freed inside the call.
+ * Out of scope: several atom species (every particle may take every place), point-group symmetry detection, and a guarantee
+ * of the global minimum: the method is a multi-start local one, and its distance is an upper bound of the true one.
+ *
+ * Errors follow the neighbours: sizes < 1, unknown dtype, unknown bits in trials, negative counts, max_cycles < 1, null required
+ * pointers, trials == 0 && random_trials == 0 DZO_ERR_INVALID; n_particles, random_trials or max_cycles above its limit
+ * DZO_ERR_UNSUPPORTED; a host pointer where a device pointer is required DZO_ERR_ASSERT; no memory for the workspace
+ * DZO_ERR_NOMEM.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_ALIGN_MAX_PARTICLES 1024
+#define DZO_ALIGN_MAX_RANDOM_TRIALS 64
+#define DZO_ALIGN_MAX_CYCLES 64
+/* bits of `trials` */
+#define DZO_ALIGN_TRIAL_IDENTITY 1
+#define DZO_ALIGN_TRIAL_PRINCIPAL 2
+/* status */
+#define DZO_ALIGN_CONVERGED 0
+#define DZO_ALIGN_CYCLE_LIMIT 1
+#define DZO_ALIGN_FAILED 2
+int32_t dzo_align_batch_assign(int64_t n_particles, int64_t batch, int32_t dtype, const void *a_dev, const void *b_dev, /* T, (3N, batch) */
+                               int32_t *perm_dev /* int32, (N, batch) */, double *cost_dev /* fp64, batch */);
+int32_t dzo_align_batch_pairs(int64_t n_particles, int64_t batch, int32_t dtype, const void *a_dev, const void *b_dev, /* T, (3N, batch) */
+                              int32_t trials /* DZO_ALIGN_TRIAL_* bits */, int32_t random_trials, int32_t max_cycles,
+                              int32_t allow_inversion, uint64_t seed, void *aligned_dev /* T, (3N, batch) */,
+                              int32_t *perm_dev /* int32, (N, batch) */, double *rotation_dev /* fp64, (9, batch) */,
+                              double *distance_dev /* fp64, batch */, int32_t *best_trial_dev, int32_t *cycles_dev,
+                              int32_t *status_dev /* int32, batch each */,
+                              double *trial_distances_dev /* fp64, (n_starts, batch); may be NULL */);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
