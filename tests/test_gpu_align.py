@@ -22,11 +22,21 @@ point against the returned rotation applied to the returned permutation of b, wi
 (seen / allowed 0.0085 in float64, 0.59 in float32, where the one rounding to T is nearly all of it), the rotation orthogonal
 with determinant 1 to 16 eps.
 
+No tolerance at all in the second half of the file.  The exact assignment cases have integer coordinates, so the optimum cost is
+a known integer and the device returns it with ``==``.  The replays (deterministic starts, the cycle limit, the ten fixed starts
+among all 138) compare every float as a bit pattern with the twin run with ``order="device"``: the header states every sum order,
+fma and tie rule, the library is built without contraction, and only the random starts call functions (log, cospi, sinpi) that no
+header pins, so those are compared device against device.  MEASURED: every one of them holds as written; with the lower-column
+rule of the wave argmin flipped the exact cases fail from N = 2 on (``all_tie``, then ``lattice``) while every test of the first
+half still passes, and with Horn's nine sums taken in another association the replays fail from N = 3 on while, again, every
+test of the first half passes.
+
 Where a planted motion has two exact answers (``align_twin.two_answers``: a pair of points is swapped by a half turn; up to three
 points are inverted by one) the permutation or the sign of the determinant is not asked for; everything else is.
 """
 import functools
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -371,6 +381,277 @@ def test_refusals():
     assert call(a_ptr=host.ctypes.data) == 3                                                           # DZO_ERR_ASSERT
     with pytest.raises(AssertionError, match="must hold 3 \\* n_particles \\* batch elements"):
         dzo.align_pairs(da, dzo.DeviceArray(3 * n, np.float64), n)
+
+
+# ------------------------------------------------------------------------------ exact assignment cases: known integer costs, no tolerance
+EXACT_SIZES = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024)
+TWIN_LIMIT = 257                                             # above it the twin runs only the kinds whose answer has no closed form
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_inputs(n):
+    """(a, b, [(kind, permutation, cost)]) of the four exact kinds at one size, fp64; exact in fp32 too.  The cost is the known
+    integer: the closed form of ``line``, sum |a_i - b_0|^2 of ``all_tie``, the twin's for the other two (scipy's, asserted in
+    tests/test_align_twin.py up to 257 and for ``lattice`` at 1024, and again here where scipy imports).  The permutation is the
+    twin's.  ``line`` and ``all_tie`` take n (n + 1) / 2 scans, half a million at 1024 and many seconds each in the twin, so above TWIN_LIMIT their
+    permutation is the closed form that tests/test_align_twin.py shows the twin to return (the reversal: the optimum is
+    unique; the identity: the lowest-column rule on equal slacks)."""
+    cases, a, b = [], [], []
+    for kind in at.EXACT_KINDS:
+        pa, pb = at.exact_case(kind, n)
+        c = at.cost_matrix(pa, pb)
+        closed = {"line": np.arange(n)[::-1], "all_tie": np.arange(n)}.get(kind)
+        perm = closed if closed is not None and n > TWIN_LIMIT else at.assign_costs(c)[0]
+        if closed is not None:
+            assert np.array_equal(perm, closed), (kind, n)
+        cost = at.matched_cost(c, perm, "device")
+        assert cost == float(c[np.arange(n), perm].astype(np.int64).sum()) and (kind != "line" or cost == at.line_cost(n))
+        try:
+            from scipy import optimize
+            rows, cols = optimize.linear_sum_assignment(c)
+            assert cost == c[rows, cols].sum(), (kind, n)
+        except ImportError:
+            pass
+        cases.append((kind, perm, cost))
+        a.append(at.join(pa)); b.append(at.join(pb))
+    return np.stack(a), np.stack(b), cases
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n", EXACT_SIZES)
+def test_exact_assignment_cases(n, dtype):
+    """Integer coordinates: every cost, potential and slack is an exact integer, so the optimum cost is one too and the device
+    returns it with ``==`` in both element types; the permutation is the twin's, tie rules included.  One batch of
+    (line, lattice, all_tie, lane_tie) per size.  ``line`` and ``all_tie`` put the loops ``step <= N`` and ``k <= N`` at their
+    bound (row i scans i + 1 times: 524 800 scans at 1024 by one wave of the Q = 16 form), ``all_tie`` ties all unvisited columns
+    at every scan, ``lane_tie`` ties the columns l + 64 q of a lane and seven classes of lanes, ``lattice`` ties at four scans
+    in five on paths nearly N long.
+    MEASURED on an MI355X (wall clock round the call, printed with ``-s``; the ``align_assign`` timer of ``dzo.profile_table``
+    agrees to the millisecond): the batch of four takes 1.35 s at N = 1024 and at 1023 in either element type, 0.07 s at 257,
+    0.04 s at 256, 0.003 s at 65.  Alone at N = 1024: ``line`` 1.37 s in float64 and 1.34 s in float32 (2.6 us a scan),
+    ``all_tie`` 1.31 s, ``lane_tie`` 0.66 s (231 204 scans), ``lattice`` 0.06 s (19 964 scans).  So ``line`` stays at every size
+    in both element types.  The first case of a size also pays the twin once for both types: 2.5 s at 1023 and at 1024."""
+    a, b, cases = _exact_inputs(n)
+    assert np.array_equal(a.astype(dtype), a) and np.array_equal(b.astype(dtype), b)
+    da, db = _dev(a, dtype), _dev(b, dtype)
+    start = time.perf_counter()
+    perm, cost = dzo.assign_particles(da, db, n)
+    seconds = time.perf_counter() - start
+    print(n, np.dtype(dtype).name, "assign_particles of the four exact kinds: %.3f s" % seconds)
+    for k, (kind, want_perm, want_cost) in enumerate(cases):
+        print(" ", kind, "cost", cost[k], "exact", want_cost)
+        assert np.array_equal(perm[k], want_perm), (kind, n)
+        assert cost[k] == want_cost, (kind, n, cost[k], want_cost)
+
+
+# ------------------------------------------------------------------------------ bit-for-bit replay of the deterministic starts
+REPLAY_SIZES = (1, 2, 3, 13, 63, 64, 65, 255, 256, 257)
+REPLAY_INVERTED = (13, 65, 257)
+DETERMINISTIC = at.TRIAL_IDENTITY | at.TRIAL_PRINCIPAL
+
+
+def _same_as_twin(r, k, t, dtype, trial_slots=None):
+    """pair k of the Alignment r against the device-order twin t: floats as bit patterns, the rest as integers"""
+    what = {}
+    if r.trial_distances is not None:
+        seen = r.trial_distances[k] if trial_slots is None else r.trial_distances[k][trial_slots]
+        what["trial_distances"] = (seen, t.trial_distances)
+    what["distances"] = (r.distances[k:k + 1], np.array([t.distance]))
+    what["rotations"] = (r.rotations[k], np.asarray(t.rotation, dtype=np.float64))
+    what["aligned"] = (r.aligned.to_host()[k], t.aligned.astype(dtype))      # the twin's fp64 value rounded once to T
+    for name, (seen, want) in what.items():
+        assert seen.dtype == want.dtype and np.array_equal(_bits(seen), _bits(want)), (name, k, seen, want)
+    assert np.array_equal(r.permutations[k], t.perm), k
+    if trial_slots is None:
+        assert (r.best_trials[k], r.cycles[k], r.status[k]) == (t.best_trial, t.cycles, t.status), k
+
+
+@functools.lru_cache(maxsize=None)
+def _replay_inputs(n, dtype, batch=3, **options):
+    rng = np.random.default_rng(5000 + n)
+    a = np.stack([at.join(at.ball_points(rng, n)) for _ in range(batch)]).astype(dtype)
+    b = np.stack([at.join(at.ball_points(rng, n)) for _ in range(batch)]).astype(dtype)
+    twin = [at.align(a[k], b[k], n, order="device", **options) for k in range(batch)]
+    return a, b, twin
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n", REPLAY_SIZES)
+def test_deterministic_starts_replay_bit_for_bit(n, dtype):
+    """The identity and the four principal starts use +, -, *, /, sqrt and the stated fma only, in a stated order: every
+    output has the twin's bits (sums in the device's order).  No tolerance, and no exemption for close seconds: the best start
+    of a bit-exact list is decided."""
+    options = dict(trials=DETERMINISTIC, random_trials=0, max_cycles=20, allow_inversion=n in REPLAY_INVERTED)
+    a, b, twin = _replay_inputs(n, dtype, **options)
+    r = dzo.align_pairs(_dev(a, dtype), _dev(b, dtype), n, want_trials=True, **options)
+    assert r.trial_distances.shape == (3, 10 if options["allow_inversion"] else 5)
+    print(n, np.dtype(dtype).name, "cycles", r.cycles, "best", r.best_trials, "status", r.status)
+    for k in range(3):
+        _same_as_twin(r, k, twin[k], dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _largest_inputs(dtype):
+    """one pair of N = 1024 that needs six cycles from the identity start (in the twin), so three end in CYCLE_LIMIT"""
+    n = 1024
+    rng = np.random.default_rng(1025)
+    a = at.join(at.ball_points(rng, n)).astype(dtype)[None]
+    b = at.join(at.ball_points(rng, n)).astype(dtype)[None]
+    return a, b, [at.align(a[0], b[0], n, trials=at.TRIAL_IDENTITY, random_trials=0, max_cycles=3, order="device")]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_the_widest_form_replays_bit_for_bit_at_the_cycle_limit(dtype):
+    """N = 1024, one unrelated pair, the identity start, three cycles: all sixteen columns of every lane and the 38 920-byte
+    LDS layout run the full cycle (three dense assignments, three rotations), and the start ends in CYCLE_LIMIT with the
+    rotation computed after the last assignment.
+    MEASURED on an MI355X: 0.18 s in either element type (the ``align_starts`` timer: 180 ms; ``align_finish`` 0.01 ms); the
+    twin takes 0.8 s.  Every field has the twin's bits."""
+    n = 1024
+    options = dict(trials=at.TRIAL_IDENTITY, random_trials=0, max_cycles=3)
+    a, b, twin = _largest_inputs(dtype)
+    da, db = _dev(a, dtype), _dev(b, dtype)
+    start = time.perf_counter()
+    r = dzo.align_pairs(da, db, n, want_trials=True, **options)
+    print(np.dtype(dtype).name, "align_pairs at N = 1024, three cycles: %.3f s" % (time.perf_counter() - start))
+    assert twin[0].status == at.CYCLE_LIMIT and r.status[0] == dzo.ALIGN_CYCLE_LIMIT and r.cycles[0] == 3
+    _same_as_twin(r, 0, twin[0], dtype)
+
+
+# ------------------------------------------------------------------------------ the cycle limit
+CYCLE_LIMITS = (1, 2, 3, 64)
+
+
+@functools.lru_cache(maxsize=None)
+def _cycle_inputs(n, dtype):
+    rng = np.random.default_rng(6100 + n)
+    a = np.stack([at.join(at.ball_points(rng, n)) for _ in range(4)]).astype(dtype)
+    b = np.stack([at.join(at.ball_points(rng, n)) for _ in range(4)]).astype(dtype)
+    twin = {m: [at.align(a[k], b[k], n, trials=at.TRIAL_IDENTITY, random_trials=0, max_cycles=m, order="device") for k in range(4)]
+            for m in CYCLE_LIMITS}
+    return a, b, twin
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n", [13, 65])
+def test_the_cycle_limit_reports_the_last_assignment_and_the_rotation_after_it(n, dtype):
+    """Four unrelated pairs, the identity start, max_cycles = 1, 2, 3 and 64.  In the twin the pairs of N = 13 converge in
+    2, 4, 5, 3 cycles and those of N = 65 in 3, 5, 8, 3 (both element types): one pair of N = 13 converges in two, two of N = 65
+    stay in CYCLE_LIMIT through three, and max_cycles = 3 produces both statuses in one batch at either size.  At the limit the permutation is the last cycle's and the rotation and
+    the distance are computed after it, as the header states: all bit-equal to the device-order twin."""
+    a, b, twin = _cycle_inputs(n, dtype)
+    da, db = _dev(a, dtype), _dev(b, dtype)
+    statuses = set()
+    for m in CYCLE_LIMITS:
+        r = dzo.align_pairs(da, db, n, trials=at.TRIAL_IDENTITY, random_trials=0, max_cycles=m, want_trials=True)
+        print(n, np.dtype(dtype).name, "max_cycles", m, "cycles", r.cycles, "status", r.status)
+        for k in range(4):
+            t = twin[m][k]
+            assert t.status == (at.CONVERGED if twin[64][k].cycles <= m else at.CYCLE_LIMIT) and t.cycles == min(m, twin[64][k].cycles)
+            _same_as_twin(r, k, t, dtype)
+            statuses.add((m, int(r.status[k])))
+    assert {s for m, s in statuses if m == 1} == {dzo.ALIGN_CYCLE_LIMIT}              # one cycle has no previous permutation
+    assert {s for m, s in statuses if m == 64} == {dzo.ALIGN_CONVERGED}
+    assert (3, dzo.ALIGN_CYCLE_LIMIT) in statuses and (3, dzo.ALIGN_CONVERGED) in statuses
+
+
+# ------------------------------------------------------------------------------ all 138 starts, and the stream rule
+def test_all_138_starts_and_the_stream_rule():
+    """The largest start count, 2 (1 + 4 + 64).  The ten deterministic starts (0 to 4, and 69 to 73 inverted) have the twin's
+    bits; the winner is the first smallest of the device's own list; random trial r draws the same numbers with another trial
+    count and for a pair alone (device against device: log, cospi and sinpi are pinned by no header); a call repeats itself."""
+    n, batch, dtype = 13, 3, np.float64
+    options = dict(trials=DETERMINISTIC, allow_inversion=True, max_cycles=20)
+    a, b, twin = _replay_inputs(n, dtype, random_trials=0, **options)
+    da, db = _dev(a, dtype), _dev(b, dtype)
+    r = dzo.align_pairs(da, db, n, random_trials=64, seed=138, want_trials=True, **options)
+    assert r.trial_distances.shape == (3, 138)
+    fixed = np.r_[0:5, 69:74]
+    x = r.aligned.to_host()
+    for k in range(batch):
+        assert np.array_equal(_bits(r.trial_distances[k][fixed]), _bits(twin[k].trial_distances)), k
+        best = int(np.argmin(r.trial_distances[k]))          # the first index of the minimum
+        assert r.best_trials[k] == best and _bits(r.distances[k:k + 1])[0] == _bits(r.trial_distances[k, best:best + 1])[0]
+        if best in fixed:
+            _same_as_twin(r, k, twin[k], dtype, trial_slots=fixed)
+    assert len({tuple(_bits(r.trial_distances[k, 5:69])) for k in range(batch)}) == batch      # the random starts did run
+    few = dzo.align_pairs(da, db, n, random_trials=3, seed=138, want_trials=True, **options)
+    assert few.trial_distances.shape == (3, 16)
+    for k in range(batch):
+        for rr in range(3):                                  # orientation 5 + r, and its inverted copy
+            assert _bits(few.trial_distances[k, 5 + rr:6 + rr])[0] == _bits(r.trial_distances[k, 5 + rr:6 + rr])[0], (k, rr)
+            assert _bits(few.trial_distances[k, 13 + rr:14 + rr])[0] == _bits(r.trial_distances[k, 74 + rr:75 + rr])[0], (k, rr)
+        assert np.array_equal(_bits(few.trial_distances[k][np.r_[0:5, 8:13]]), _bits(twin[k].trial_distances))
+    other = dzo.align_pairs(da, db, n, random_trials=3, seed=139, want_trials=True, **options)
+    assert not np.array_equal(_bits(other.trial_distances[:, 5:8]), _bits(few.trial_distances[:, 5:8]))   # the seed selects the stream
+    for k in range(batch):
+        one = dzo.align_pairs(_dev(a[k:k + 1], dtype), _dev(b[k:k + 1], dtype), n, random_trials=64, seed=138, want_trials=True, **options)
+        assert np.array_equal(_bits(one.trial_distances[0]), _bits(r.trial_distances[k])), k
+        assert np.array_equal(_bits(one.aligned.to_host()[0]), _bits(x[k])) and one.best_trials[0] == r.best_trials[k]
+    again = dzo.align_pairs(da, db, n, random_trials=64, seed=138, want_trials=True, **options)
+    for name in ("trial_distances", "distances", "rotations", "permutations", "best_trials", "cycles", "status"):
+        assert np.array_equal(_bits(getattr(again, name)), _bits(getattr(r, name))), name
+    assert np.array_equal(_bits(again.aligned.to_host()), _bits(x))
+
+
+# ------------------------------------------------------------------------------ guard bands, untouched inputs
+CANARY = 12345.0
+GUARD = 64
+
+
+def _guarded(shape, np_dtype):
+    size = int(np.prod(shape))
+    buf = dzo.DeviceArray.from_host(np.full(size + 2 * GUARD, CANARY, dtype=np_dtype))
+    return buf, buf.view(GUARD, shape)
+
+
+def _guards_hold(buffers):
+    for name, (buf, window) in buffers.items():
+        h = buf.to_host()
+        assert np.all(h[:GUARD] == h.dtype.type(CANARY)) and np.all(h[-GUARD:] == h.dtype.type(CANARY)), name + ": wrote outside its output"
+        assert not np.any(window.to_host() == h.dtype.type(CANARY)), name + ": an element of the output was not written"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("want_trials", [True, False])
+@pytest.mark.parametrize("n", [1, 64, 65, 257])
+def test_outputs_stay_inside_their_windows_and_inputs_are_untouched(n, want_trials, dtype):
+    """The C entry points with every output a window inside a larger array of canaries: no element outside a window changes,
+    every element inside one is written, and a and b come back bit-identical ("neither is changed")."""
+    batch, n_starts = 2, 2 * (1 + 4 + 2)
+    rng = np.random.default_rng(8000 + n)
+    a = np.stack([at.join(at.ball_points(rng, n)) for _ in range(batch)]).astype(dtype)
+    b = np.stack([at.join(at.ball_points(rng, n)) for _ in range(batch)]).astype(dtype)
+    da, db = _dev(a, dtype), _dev(b, dtype)
+    L = dzo.lib()
+    out = {"aligned": _guarded((batch, 3 * n), dtype), "perm": _guarded((batch, n), np.int32), "rotation": _guarded((batch, 3, 3), np.float64),
+           "distance": _guarded((batch,), np.float64), "best_trial": _guarded((batch,), np.int32), "cycles": _guarded((batch,), np.int32),
+           "status": _guarded((batch,), np.int32)}
+    trial = {"trial_distances": _guarded((batch, n_starts), np.float64)}
+    order = ("aligned", "perm", "rotation", "distance", "best_trial", "cycles", "status")
+    assert L.dzo_align_batch_pairs(n, batch, dzo.F64 if dtype is np.float64 else dzo.F32, da.ptr, db.ptr, DETERMINISTIC, 2, 20, 1, 7,
+                                   *[out[name][1].ptr for name in order], trial["trial_distances"][1].ptr if want_trials else None) == 0
+    _guards_hold(out)
+    if want_trials:
+        _guards_hold(trial)
+    else:
+        assert np.all(trial["trial_distances"][0].to_host() == CANARY)
+    assert np.array_equal(_bits(da.to_host()), _bits(a)) and np.array_equal(_bits(db.to_host()), _bits(b))
+    # the windows hold what the binding returns from plain arrays
+    plain = dzo.align_pairs(da, db, n, trials=DETERMINISTIC, random_trials=2, max_cycles=20, allow_inversion=True, seed=7, want_trials=True)
+    assert np.array_equal(_bits(out["aligned"][1].to_host()), _bits(plain.aligned.to_host()))
+    assert np.array_equal(out["perm"][1].to_host(), plain.permutations) and np.array_equal(out["status"][1].to_host(), plain.status)
+    assert np.array_equal(_bits(out["distance"][1].to_host()), _bits(plain.distances))
+    if want_trials:
+        assert np.array_equal(_bits(trial["trial_distances"][1].to_host()), _bits(plain.trial_distances))
+    if want_trials:                                          # the assignment alone, once per size and element type
+        assign = {"perm": _guarded((batch, n), np.int32), "cost": _guarded((batch,), np.float64)}
+        assert L.dzo_align_batch_assign(n, batch, dzo.F64 if dtype is np.float64 else dzo.F32, da.ptr, db.ptr, assign["perm"][1].ptr,
+                                        assign["cost"][1].ptr) == 0
+        _guards_hold(assign)
+        assert np.array_equal(_bits(da.to_host()), _bits(a)) and np.array_equal(_bits(db.to_host()), _bits(b))
+        p, c = dzo.assign_particles(da, db, n)
+        assert np.array_equal(assign["perm"][1].to_host(), p) and np.array_equal(_bits(assign["cost"][1].to_host()), _bits(c))
 
 
 # ------------------------------------------------------------------------------ the consumer
