@@ -34,6 +34,7 @@ F32, F64 = 0, 1
 ROSENBROCK2D, ROSENBROCK_CHAIN, QUADRATIC, LSE, QUADRATIC_CHAIN = 0, 1, 2, 3, 4
 PAIRWISE_LJ = 5                 # n = 3N, point = [x | y | z] (src/ExampleFunctions.jl)
 RADIAL_LENNARD_JONES = 0        # lj_energy / lj_first_derivative / lj_second_derivative (:16-72)
+RADIAL_MORSE_RHO6, RADIAL_MORSE_RHO14 = 2, 3   # E(r) = t^2 - 2 t, t = exp(rho (1 - r)): pair minimum at r = 1, depth 1 (include/dzo.h)
 TWOLOOP_CHAIN, TWOLOOP_GRAM = 0, 1
 LINE_SEARCH_BACKTRACKING, LINE_SEARCH_WOLFE = 0, 1
 STEP_NULL, STEP_GRADIENT_DESCENT, STEP_BFGS = 0, 1, 2
@@ -599,6 +600,7 @@ class ParallelTempering(_HandleArrays):
         assert replicas.size == 3 * self.n_particles * self.n_replicas, "replicas must hold 3 * n_particles * n_replicas elements"
         self.constraining_radius = float(constraining_radius)
         self.record_capacity = 0
+        self.radial = int(radial)
         h = C.c_void_p()
         _check(lib().dzo_tempering_create(radial, self.n_particles, self.n_replicas, _dt(self.dtype), replicas.ptr,
                                           beta.ctypes.data_as(_P(_dbl)), rad.ctypes.data_as(_P(_dbl)), self.constraining_radius,
@@ -661,13 +663,13 @@ class ParallelTempering(_HandleArrays):
         ``max_steps`` per instance).  ``optimizer="adgd"`` quenches the copy with a ``BatchedAdGD`` instead
         (``history_length`` is ignored).  Returns ``(energies, copy, optimizer)``: the minima's energies (host array), the
         DeviceArray that holds them, and the handle (its ``is_stuck`` tells which instances finished).  The Markov chain's
-        own array is not touched."""
+        own array is not touched.  The quench runs under the radial the tempering was created with."""
         assert optimizer in ("lbfgs", "adgd"), "optimizer must be 'lbfgs' or 'adgd'"
         minima = self.replicas.copy()
         if optimizer == "adgd":
-            opt = BatchedAdGD(minima, self.n_particles, initial_step_length)
+            opt = BatchedAdGD(minima, self.n_particles, initial_step_length, radial=self.radial)
         else:
-            opt = BatchedLBFGS(minima, self.n_particles, initial_step_length, history_length)
+            opt = BatchedLBFGS(minima, self.n_particles, initial_step_length, history_length, radial=self.radial)
         opt._run(max_steps, steps_per_launch)
         return opt.current_objective_values, minima, opt
 

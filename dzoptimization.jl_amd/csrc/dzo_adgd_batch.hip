@@ -66,7 +66,7 @@ template <typename T> __global__ __launch_bounds__(kBlock) void adgd_batch_init_
     }
 }
 
-template <typename T, typename F> __global__ __launch_bounds__(64) void adgd_batch_wave_step_kernel(AdgdBatchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void adgd_batch_wave_step_body(AdgdBatchArgs<T> a) {
     const int64_t b = blockIdx.x;
     if (a.stuck[b]) return;                                  // :276, the whole wave
     const int lane = threadIdx.x, N = a.N;
@@ -128,10 +128,13 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void adgd_bat
         a.halv[b] = halv;
     }
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void adgd_batch_wave_step_kernel(AdgdBatchArgs<T> a) { adgd_batch_wave_step_body<T, F>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_adgdb_wave_step(AdgdBatchArgs<T> a) { adgd_batch_wave_step_body<T, F>(a); }
 
 extern __shared__ __attribute__((aligned(16))) double adgd_batch_smem[];
 
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void adgd_batch_block_step_kernel(AdgdBatchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void adgd_batch_block_step_body(AdgdBatchArgs<T> a) {
     const int64_t b = blockIdx.x;
     if (a.stuck[b]) return;                                  // the whole block
     const int tid = threadIdx.x, N = a.N, n3 = 3 * N;
@@ -214,6 +217,9 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void adgd
         *ghalv_ = halv;
     }
 }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void adgd_batch_block_step_kernel(AdgdBatchArgs<T> a) { adgd_batch_block_step_body<T, F>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_adgdb_block_step(AdgdBatchArgs<T> a) { adgd_batch_block_step_body<T, F>(a); }
 
 }  // namespace dzo
 
@@ -240,12 +246,14 @@ template <typename T> static AdgdBatchArgs<T> ab_args(const dzo_adgd_batch_s *h,
     return a;
 }
 
-template <typename T> static void ab_launch_step(hipStream_t s, const dzo_adgd_batch_s *h, int steps) {
+template <typename T, typename F> static void ab_launch_step(hipStream_t s, const dzo_adgd_batch_s *h, int steps) {
     const AdgdBatchArgs<T> a = ab_args<T>(h, steps, 0.0);
     const dim3 grid((unsigned)h->core.B);
-    if (a.N <= 64) hipLaunchKernelGGL((adgd_batch_wave_step_kernel<T, LJRadial<T>>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((adgd_batch_block_step_kernel<T, LJRadial<T>>), grid, dim3(kBlock), h->core.lds_bytes, s, a);
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(adgd_batch_wave_step_kernel, rad_adgdb_wave_step, (T, F), grid, dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL(adgd_batch_block_step_kernel, rad_adgdb_block_step, (T, F), grid, dim3(kBlock), h->core.lds_bytes, s, a);
 }
+
+template <typename T, typename F> static const void *ab_block_kernel() { return DZO_RADIAL_KERNEL(adgd_batch_block_step_kernel, rad_adgdb_block_step, (T, F)); }
 
 // `what` -> device address, bytes
 static int32_t ab_array(dzo_adgd_batch_s *h, int32_t what, void **p, size_t *bytes) {
@@ -285,7 +293,7 @@ int32_t dzo_adgd_batch_create(int32_t radial, int64_t n_particles, int64_t batch
     dzo_adgd_batch_s *h = new (std::nothrow) dzo_adgd_batch_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     ClCore &c = h->core;
-    c.device = ctx().device; c.dtype = dtype; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
+    c.device = ctx().device; c.dtype = dtype; c.radial = radial; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
     const size_t es = dtype_size(dtype), B = (size_t)batch, n3 = 3 * (size_t)n_particles;
     if (n_particles > 64) c.lds_bytes = 16 * kWaves + 5 * n3 * es;
     int32_t rc = cl_alloc({{&c.g, es * n3 * B}, {&c.dx, es * n3 * B}, {&c.dg, es * n3 * B}, {&c.f, es * B}, {&c.df, es * B}, {&h->cur, es * B},
@@ -294,12 +302,14 @@ int32_t dzo_adgd_batch_create(int32_t radial, int64_t n_particles, int64_t batch
                           "the batched AdGD state");
     const void *k = dtype == DZO_F64 ? (const void *)adgd_batch_block_step_kernel<double, LJRadial<double>>
                                      : (const void *)adgd_batch_block_step_kernel<float, LJRadial<float>>;
+    if (rc == DZO_OK && radial != DZO_RADIAL_LENNARD_JONES)
+        rc = [&]() -> int32_t { DZO_DISPATCH_RADIAL(radial, dtype, k = (ab_block_kernel<T, F>())); return DZO_OK; }();
     if (rc == DZO_OK)
         rc = cl_finish_create(&c, k, "batched AdGD state", "batched AdGD constructor", [&](hipStream_t s) -> int32_t {
             DZO_TIMED("adgd_batch_init", s);
             // f0 and g0 by the evaluation kernels of dzo_pairwise_batch_energy_gradient, then the step sizes and is_stuck
-            DZO_DISPATCH(dtype, cl_launch_eval<T>(s, c.N, batch, (const T *)c.x, (T *)c.f, (T *)c.g);
-                         hipLaunchKernelGGL((adgd_batch_init_kernel<T>), dim3((unsigned)batch), dim3(kBlock), 0, s, ab_args<T>(h, 0, initial_step_length)));
+            DZO_DISPATCH(dtype, DZO_TRY(cl_launch_eval<T>(s, radial, c.N, batch, (const T *)c.x, (T *)c.f, (T *)c.g)));
+            DZO_DISPATCH(dtype, hipLaunchKernelGGL((adgd_batch_init_kernel<T>), dim3((unsigned)batch), dim3(kBlock), 0, s, ab_args<T>(h, 0, initial_step_length)));
             return DZO_OK;
         });
     if (rc != DZO_OK) { ab_free(h); return rc; }
@@ -321,7 +331,7 @@ int32_t dzo_adgd_batch_set_max_halvings(dzo_adgd_batch_t h, int64_t max_halvings
 int32_t dzo_adgd_batch_step(dzo_adgd_batch_t h, int32_t steps, int32_t *all_stuck) {
     return cl_step(h, steps, all_stuck, [&](hipStream_t s) -> int32_t {
         DZO_TIMED("adgd_batch_step", s);
-        DZO_DISPATCH(h->core.dtype, ab_launch_step<T>(s, h, steps));
+        DZO_DISPATCH_RADIAL(h->core.radial, h->core.dtype, (ab_launch_step<T, F>(s, h, steps)));
         DZO_HIP(hipGetLastError());
         return DZO_OK;
     });

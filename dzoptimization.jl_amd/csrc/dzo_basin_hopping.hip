@@ -144,7 +144,7 @@ __device__ __forceinline__ PcgMap bh_map(uint64_t k) {
 extern __shared__ __attribute__((aligned(16))) double basin_smem[];
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
-template <typename T, typename F> __global__ __launch_bounds__(64) void basin_hop_wave_kernel(BasinArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void basin_hop_wave_body(BasinArgs<T> a) {
     const int lane = threadIdx.x, N = a.N, m = a.m;
     const int64_t b = blockIdx.x, base = (int64_t)3 * N * b;
     const bool live = lane < N;
@@ -211,10 +211,13 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void basin_ho
         else out.called(E, bestE, radius, fac, adapt_ != 0, s, acc, rej, hops, iters, unfinished);
     }
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void basin_hop_wave_kernel(BasinArgs<T> a) { basin_hop_wave_body<T, F>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_bhop_wave(BasinArgs<T> a) { basin_hop_wave_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
 // HL: the history ring is in LDS (else in a.slab)
-template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void basin_hop_block_kernel(BasinArgs<T> a) {
+template <typename T, typename F, bool HL> __device__ __forceinline__ void basin_hop_block_body(BasinArgs<T> a) {
     const int tid = threadIdx.x, N = a.N, m = a.m, n3 = 3 * N;
     const int64_t b = blockIdx.x, base = (int64_t)n3 * b;
     const int create_ = bh_pinned(a.create), adapt_ = bh_pinned(a.adapt);
@@ -301,6 +304,9 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
         else out.called(E, bestE, radius, fac, adapt_ != 0, s, acc, rej, hops, iters, unfinished);
     }
 }
+template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void basin_hop_block_kernel(BasinArgs<T> a) { basin_hop_block_body<T, F, HL>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void rad_bhop_block(BasinArgs<T> a) { basin_hop_block_body<T, F, HL>(a); }
 
 }  // namespace dzo
 
@@ -308,7 +314,7 @@ using namespace dzo;
 
 struct dzo_basin_hopping_s {
     int device = -1;
-    int32_t dtype = DZO_F64;
+    int32_t dtype = DZO_F64, radial = DZO_RADIAL_LENNARD_JONES;
     int N = 0, m = 0, quench_steps = 0;
     int64_t B = 0, max_halvings = 4096;
     double step_length = 0, constraining_radius = 0, fac = 0;
@@ -341,12 +347,12 @@ static void bh_free(dzo_basin_hopping_s *h) {
     delete h;
 }
 
-template <typename T> static const void *bh_kernel(const dzo_basin_hopping_s *h) {
-    if (h->N <= 64) return (const void *)basin_hop_wave_kernel<T, LJRadial<T>>;
-    return h->hist_lds ? (const void *)basin_hop_block_kernel<T, LJRadial<T>, true> : (const void *)basin_hop_block_kernel<T, LJRadial<T>, false>;
+template <typename T, typename F> static const void *bh_kernel(const dzo_basin_hopping_s *h) {
+    if (h->N <= 64) return DZO_RADIAL_KERNEL(basin_hop_wave_kernel, rad_bhop_wave, (T, F));
+    return h->hist_lds ? DZO_RADIAL_KERNEL(basin_hop_block_kernel, rad_bhop_block, (T, F, true)) : DZO_RADIAL_KERNEL(basin_hop_block_kernel, rad_bhop_block, (T, F, false));
 }
 
-template <typename T> static void bh_launch(hipStream_t s, const dzo_basin_hopping_s *h, int64_t num_hops, int create, int adapt) {
+template <typename T, typename F> static void bh_launch(hipStream_t s, const dzo_basin_hopping_s *h, int64_t num_hops, int create, int adapt) {
     BasinArgs<T> a;
     a.N = h->N; a.m = h->m; a.quench_steps = h->quench_steps;
     a.create = create; a.adapt = adapt;
@@ -360,9 +366,9 @@ template <typename T> static void bh_launch(hipStream_t s, const dzo_basin_hoppi
     a.rec_normals = (T *)h->rec_normals; a.rec_uniform = (T *)h->rec_uniform; a.rec_trial = (T *)h->rec_trial;
     a.rec_iters = h->rec_iters; a.rec_code = h->rec_code;
     const dim3 grid((unsigned)h->B);
-    if (h->N <= 64) hipLaunchKernelGGL((basin_hop_wave_kernel<T, LJRadial<T>>), grid, dim3(64), h->lds_bytes, s, a);
-    else if (h->hist_lds) hipLaunchKernelGGL((basin_hop_block_kernel<T, LJRadial<T>, true>), grid, dim3(kBlock), h->lds_bytes, s, a);
-    else hipLaunchKernelGGL((basin_hop_block_kernel<T, LJRadial<T>, false>), grid, dim3(kBlock), h->lds_bytes, s, a);
+    if (h->N <= 64) DZO_LAUNCH_RADIAL(basin_hop_wave_kernel, rad_bhop_wave, (T, F), grid, dim3(64), h->lds_bytes, s, a);
+    else if (h->hist_lds) DZO_LAUNCH_RADIAL(basin_hop_block_kernel, rad_bhop_block, (T, F, true), grid, dim3(kBlock), h->lds_bytes, s, a);
+    else DZO_LAUNCH_RADIAL(basin_hop_block_kernel, rad_bhop_block, (T, F, false), grid, dim3(kBlock), h->lds_bytes, s, a);
 }
 
 // `what` -> device address, bytes
@@ -414,7 +420,7 @@ int32_t dzo_basin_hopping_create(int32_t radial, int64_t n_particles, int64_t ba
     DZO_TRY(require_same_backend("LBFGSOptimizer", "src/DZOptimization.jl:363-364", points_dev, "initial_point", nullptr, ""));
     dzo_basin_hopping_s *h = new (std::nothrow) dzo_basin_hopping_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
-    h->device = ctx().device; h->dtype = dtype; h->N = (int)n_particles; h->B = batch; h->points = points_dev;
+    h->device = ctx().device; h->dtype = dtype; h->radial = radial; h->N = (int)n_particles; h->B = batch; h->points = points_dev;
     h->m = history_length; h->quench_steps = quench_steps;
     h->step_length = initial_step_length; h->constraining_radius = constraining_radius;
     h->fac = dtype == DZO_F64 ? mc_fac<double>() : mc_fac<float>();
@@ -446,13 +452,16 @@ int32_t dzo_basin_hopping_create(int32_t radial, int64_t n_particles, int64_t ba
     if (e == hipSuccess) e = hipMemcpy(h->rng, states.data(), 8 * B, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();          // the memsets of cl_alloc ran on the null stream
     // dynamic LDS above the default needs the attribute; it belongs to the kernel and is raised to the limit (dzo_cluster.h)
-    if (e == hipSuccess && h->lds_bytes > 48 * 1024)
-        e = hipFuncSetAttribute(dtype == DZO_F64 ? bh_kernel<double>(h) : bh_kernel<float>(h), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax);
+    if (e == hipSuccess && h->lds_bytes > 48 * 1024) {
+        const void *k = nullptr;
+        DZO_DISPATCH_RADIAL(radial, dtype, k = (bh_kernel<T, F>(h)));   // (radial and dtype have been checked)
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax);
+    }
     if (e != hipSuccess) { bh_free(h); return hip_fail(e, "basin-hopping state upload", __FILE__, __LINE__); }
     {
         hipStream_t s = ctx().stream;
         DZO_TIMED("basin_hopping_init", s);
-        DZO_DISPATCH(dtype, bh_launch<T>(s, h, 0, 1, 0));     // the quench of the caller's points; not waited for
+        DZO_DISPATCH_RADIAL(radial, dtype, (bh_launch<T, F>(s, h, 0, 1, 0)));     // the quench of the caller's points; not waited for
         e = hipGetLastError();
     }
     if (e != hipSuccess) { bh_free(h); return hip_fail(e, "basin-hopping constructor", __FILE__, __LINE__); }
@@ -484,7 +493,7 @@ int32_t dzo_basin_hopping_hop(dzo_basin_hopping_t h, int64_t num_hops, int32_t a
     DeviceScope scope(h->device);
     hipStream_t s = ctx().stream;
     DZO_TIMED("basin_hopping_hop", s);
-    DZO_DISPATCH(h->dtype, bh_launch<T>(s, h, num_hops, 0, adapt ? 1 : 0));
+    DZO_DISPATCH_RADIAL(h->radial, h->dtype, (bh_launch<T, F>(s, h, num_hops, 0, adapt ? 1 : 0)));
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }

@@ -127,12 +127,12 @@ inline int32_t cl_check_args(int32_t radial, int64_t N, int64_t batch, int32_t d
 
 // energy (f, one per instance) and, where g is not null, gradient of `batch` points on s: the evaluation kernels of
 // dzo_lbfgs_batch.hip, which also defines the count below
-template <typename T> void cl_launch_eval(hipStream_t s, int N, int64_t batch, const T *x, T *f, T *g);
+template <typename T> int32_t cl_launch_eval(hipStream_t s, int32_t radial, int N, int64_t batch, const T *x, T *f, T *g);
 
 // What the handles of the batched optimizers share; each embeds one as `core`.
 struct ClCore {
     int device = -1;
-    int32_t dtype = DZO_F64;
+    int32_t dtype = DZO_F64, radial = DZO_RADIAL_LENNARD_JONES;   // the radial of every later launch is the constructor's
     int N = 0;
     int64_t B = 0, max_halvings = 4096;
     void *x = nullptr;               // the caller's

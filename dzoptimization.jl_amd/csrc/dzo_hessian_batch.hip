@@ -47,7 +47,7 @@ template <typename T> struct HessBatchArgs {
 };
 
 // ------------------------------------------------------------------------------ products, WAVE shape: grid batch, block 64
-template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hvp_kernel(HessBatchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void hess_batch_wave_hvp_body(HessBatchArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
     const int64_t b = blockIdx.x, base = (int64_t)3 * N * b, pbase = a.point_stride * b;
     const bool live = lane < N;
@@ -71,9 +71,12 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void hess_bat
     const double uu = wave_sum_all(cl_dot3(pi.u, pi.v, pi.w, pi.u, pi.v, pi.w));
     if (lane == 0) { a.curv[2 * b] = uhu; a.curv[2 * b + 1] = uu; }
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hvp_kernel(HessBatchArgs<T> a) { hess_batch_wave_hvp_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_hessb_wave_hvp(HessBatchArgs<T> a) { hess_batch_wave_hvp_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ products, BLOCK shape: grid batch, block 256
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess_batch_block_hvp_kernel(HessBatchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void hess_batch_block_hvp_body(HessBatchArgs<T> a) {
     __shared__ T XD[6 * kHessMaxN];
     __shared__ double red[2 * kWaves];
     const int tid = threadIdx.x, N = a.N;
@@ -106,6 +109,9 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess
     cl_block_sum2(uhu, uu, red);
     if (tid == 0) { a.curv[2 * b] = uhu; a.curv[2 * b + 1] = uu; }
 }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess_batch_block_hvp_kernel(HessBatchArgs<T> a) { hess_batch_block_hvp_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_hessb_block_hvp(HessBatchArgs<T> a) { hess_batch_block_hvp_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ dense Hessians
 // The pair (i, j) seen from particle i at (x, y, z): t[b][a] = the term of row component a for the direction +e_b of particle i
@@ -151,7 +157,7 @@ template <typename T> __device__ __forceinline__ void hb_store_diagonal(T *col0,
 }
 
 // WAVE shape: grid batch, block 64
-template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hessian_kernel(HessBatchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void hess_batch_wave_hessian_body(HessBatchArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
     const int64_t b = blockIdx.x, n3 = (int64_t)3 * N, pbase = n3 * b;
     const bool live = lane < N;
@@ -176,9 +182,12 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void hess_bat
     }
     if (live) hb_store_diagonal<T>(col0, n3, N, lane, acc);
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hessian_kernel(HessBatchArgs<T> a) { hess_batch_wave_hessian_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_hessb_wave_hessian(HessBatchArgs<T> a) { hess_batch_wave_hessian_body<T, F>(a); }
 
 // BLOCK shape: grid batch, block 256
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess_batch_block_hessian_kernel(HessBatchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void hess_batch_block_hessian_body(HessBatchArgs<T> a) {
     __shared__ T X[3 * kHessMaxN];
     const int tid = threadIdx.x, N = a.N;
     const int64_t b = blockIdx.x, n3 = (int64_t)3 * N, pbase = n3 * b;
@@ -211,21 +220,25 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess
         }
     }
 }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess_batch_block_hessian_kernel(HessBatchArgs<T> a) { hess_batch_block_hessian_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_hessb_block_hessian(HessBatchArgs<T> a) { hess_batch_block_hessian_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ host side
-template <typename T> static void hb_launch_hvp(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
-    if (a.N <= 64) hipLaunchKernelGGL((hess_batch_wave_hvp_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((hess_batch_block_hvp_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+template <typename T, typename F> static void hb_launch_hvp(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(hess_batch_wave_hvp_kernel, rad_hessb_wave_hvp, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL(hess_batch_block_hvp_kernel, rad_hessb_block_hvp, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
-template <typename T> static void hb_launch_hessian(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
-    if (a.N <= 64) hipLaunchKernelGGL((hess_batch_wave_hessian_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((hess_batch_block_hessian_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+template <typename T, typename F> static void hb_launch_hessian(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(hess_batch_wave_hessian_kernel, rad_hessb_wave_hessian, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL(hess_batch_block_hessian_kernel, rad_hessb_block_hessian, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 // dzo_chain.h: the launch of dzo_pairwise_batch_hessian on `s`, checked arguments, no wait
-int32_t hb_enqueue_hessian(hipStream_t s, int32_t dtype, int N, int64_t batch, const void *points, void *hessians) {
-    DZO_DISPATCH(dtype, hb_launch_hessian<T>(s, batch, HessBatchArgs<T>{N, (int64_t)3 * N, (const T *)points, nullptr, (T *)hessians, nullptr}));
+int32_t hb_enqueue_hessian(hipStream_t s, int32_t radial, int32_t dtype, int N, int64_t batch, const void *points, void *hessians) {
+    DZO_DISPATCH_RADIAL(radial, dtype,
+                        (hb_launch_hessian<T, F>(s, batch, HessBatchArgs<T>{N, (int64_t)3 * N, (const T *)points, nullptr, (T *)hessians, nullptr})));
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
@@ -251,9 +264,10 @@ int32_t dzo_pairwise_batch_hvp(int32_t radial, int64_t n_particles, int64_t batc
     Context &c = ctx();
     {
         DZO_TIMED("hess_batch_hvp", c.stream);
-        DZO_DISPATCH(dtype, hb_launch_hvp<T>(c.stream, batch,
-                                             HessBatchArgs<T>{(int)n_particles, point_stride, (const T *)points_dev, (const T *)directions_dev,
-                                                              (T *)products_dev, curvatures_dev}));
+        DZO_DISPATCH_RADIAL(radial, dtype,
+                            (hb_launch_hvp<T, F>(c.stream, batch,
+                                                 HessBatchArgs<T>{(int)n_particles, point_stride, (const T *)points_dev, (const T *)directions_dev,
+                                                                  (T *)products_dev, curvatures_dev})));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));
@@ -269,9 +283,7 @@ int32_t dzo_pairwise_batch_hessian(int32_t radial, int64_t n_particles, int64_t 
     Context &c = ctx();
     {
         DZO_TIMED("hess_batch_hessian", c.stream);
-        DZO_DISPATCH(dtype, hb_launch_hessian<T>(c.stream, batch,
-                                                 HessBatchArgs<T>{(int)n_particles, 3 * n_particles, (const T *)points_dev, nullptr,
-                                                                  (T *)hessians_dev, nullptr}));
+        DZO_TRY(hb_enqueue_hessian(c.stream, radial, dtype, (int)n_particles, batch, points_dev, hessians_dev));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));

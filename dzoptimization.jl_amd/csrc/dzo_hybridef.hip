@@ -46,7 +46,7 @@ template <typename T> struct HybridefArgs {
 };
 
 // X: 3N elements of LDS (BLOCK; unused by WAVE); red: 2 * kWaves doubles of LDS (BLOCK)
-template <typename T, bool BLOCK> __device__ __forceinline__ void he_run(const HybridefArgs<T> &a, T *X, double *red) {
+template <typename T, typename RF, bool BLOCK> __device__ __forceinline__ void he_run(const HybridefArgs<T> &a, T *X, double *red) {
     constexpr int PER = BLOCK ? kClPer : 1;
     const int64_t b = blockIdx.x;
     if (a.status[b] != DZO_HYBRIDEF_ACTIVE) return;          // frozen: the whole block
@@ -76,9 +76,9 @@ template <typename T, bool BLOCK> __device__ __forceinline__ void he_run(const H
                 if (live[q]) { X[i] = x[0][q]; X[N + i] = x[1][q]; X[2 * N + i] = x[2][q]; }
             }
             __syncthreads();
-            cl_block_eval<T, LJRadial<T>>(N, tid, X, red, par, E, g[0], g[1], g[2]);
+            cl_block_eval<T, RF>(N, tid, X, red, par, E, g[0], g[1], g[2]);
         } else {
-            cl_wave_eval<T, LJRadial<T>>(N, tid, x[0][0], x[1][0], x[2][0], E, g[0][0], g[1][0], g[2][0]);
+            cl_wave_eval<T, RF>(N, tid, x[0][0], x[1][0], x[2][0], E, g[0][0], g[1][0], g[2][0]);
         }
     };
     // a sum over the particles in every thread, in the order of the sums
@@ -197,18 +197,30 @@ template <typename T, bool BLOCK> __device__ __forceinline__ void he_run(const H
 }
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
-template <typename T> __global__ __launch_bounds__(64) void hybridef_wave_step_kernel(HybridefArgs<T> a) { he_run<T, false>(a, nullptr, nullptr); }
+template <typename T> __global__ __launch_bounds__(64) void hybridef_wave_step_kernel(HybridefArgs<T> a) { he_run<T, LJRadial<T>, false>(a, nullptr, nullptr); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename RF> __global__ __launch_bounds__(64) void rad_hybef_wave_step(HybridefArgs<T> a) { he_run<T, RF, false>(a, nullptr, nullptr); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
 template <typename T> __global__ __launch_bounds__(kBlock) void hybridef_block_step_kernel(HybridefArgs<T> a) {
     __shared__ T X[3 * kClMaxN];
     __shared__ double red[2 * kWaves];
-    he_run<T, true>(a, X, red);
+    he_run<T, LJRadial<T>, true>(a, X, red);
+}
+template <typename T, typename RF> __global__ __launch_bounds__(kBlock) void rad_hybef_block_step(HybridefArgs<T> a) {
+    __shared__ T X[3 * kClMaxN];
+    __shared__ double red[2 * kWaves];
+    he_run<T, RF, true>(a, X, red);
 }
 
-template <typename T> static void he_launch(hipStream_t s, int64_t batch, const HybridefArgs<T> &a) {
-    if (a.N <= 64) hipLaunchKernelGGL((hybridef_wave_step_kernel<T>), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((hybridef_block_step_kernel<T>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+template <typename T, typename RF> static void he_launch_radial(hipStream_t s, int64_t batch, const HybridefArgs<T> &a) {
+    using F = RF;
+    if (a.N <= 64) DZO_LAUNCH_RADIAL2(hybridef_wave_step_kernel, (T), rad_hybef_wave_step, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL2(hybridef_block_step_kernel, (T), rad_hybef_block_step, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+}
+template <typename T> static int32_t he_launch(hipStream_t s, int32_t radial, int64_t batch, const HybridefArgs<T> &a) {
+    DZO_RADIAL_CASES_(radial, (he_launch_radial<T, F>(s, batch, a)))
+    return DZO_OK;
 }
 
 // the argument checks of apply and create
@@ -313,7 +325,7 @@ int32_t dzo_hybridef_batch_apply(int32_t radial, int64_t n_particles, int64_t ba
                      a.x = (T *)points_dev; a.lam_in = (const T *)eigenvalues_dev; a.u_in = (const T *)modes_dev;
                      a.E = (T *)energies_dev; a.g = (T *)gradients_dev; a.F = (T *)projections_dev; a.h = (T *)uphill_steps_dev;
                      a.grms = grms_dev; a.status = status_dev; a.tangent = tangent_counts_dev;
-                     he_launch<T>(c.stream, batch, a));
+                     DZO_TRY(he_launch<T>(c.stream, radial, batch, a)));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));
@@ -336,7 +348,7 @@ int32_t dzo_hybridef_batch_create(int32_t radial, int64_t n_particles, int64_t b
     dzo_hybridef_batch_s *h = new (std::nothrow) dzo_hybridef_batch_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     ClCore &c = h->core;
-    c.device = ctx().device; c.dtype = dtype; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
+    c.device = ctx().device; c.dtype = dtype; c.radial = radial; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
     h->max_step = max_step; h->tangent_steps = tangent_steps; h->tangent_steps_convex = tangent_steps_convex; h->tangent_cap = tangent_cap;
     h->tangent_first = tangent_first; h->krylov = krylov; h->mode_cycles = mode_cycles; h->mode_tol = mode_tol; h->zero_tol = zero_tol;
     h->grad_tol = grad_tol; h->base_seed = base_seed; h->have_modes = dirs_dev != nullptr;
@@ -349,11 +361,11 @@ int32_t dzo_hybridef_batch_create(int32_t radial, int64_t n_particles, int64_t b
                           "the hybrid eigenvector-following state");
     if (rc == DZO_OK)
         rc = cl_finish_create(&c, nullptr, "hybrid eigenvector-following state", "hybrid eigenvector-following constructor", [&](hipStream_t s) -> int32_t {
-            DZO_TRY(lm_prepare(dtype, c.N, krylov, 1));
+            DZO_TRY(lm_prepare(radial, dtype, c.N, krylov, 1));
             DZO_TIMED("hybridef_init", s);
             if (dirs_dev) { DZO_HIP(hipMemcpyAsync(h->u, dirs_dev, es * n3 * B, hipMemcpyDeviceToDevice, s)); }
             // the energies and gradients of the points as given; every other record is zero until the first step
-            DZO_DISPATCH(dtype, cl_launch_eval<T>(s, c.N, batch, (const T *)c.x, (T *)c.f, (T *)c.g));
+            DZO_DISPATCH(dtype, DZO_TRY(cl_launch_eval<T>(s, radial, c.N, batch, (const T *)c.x, (T *)c.f, (T *)c.g)));
             return DZO_OK;
         });
     if (rc != DZO_OK) { he_free(h); return rc; }
@@ -388,12 +400,12 @@ int32_t dzo_hybridef_batch_step(dzo_hybridef_batch_t h, int32_t steps, int32_t *
             {
                 DZO_TIMED("hybridef_mode", s);
                 // mode_cycles cycles refine the vector; the first product of one more measures its eigenvalue and residual
-                DZO_TRY(lm_enqueue(s, c.dtype, c.N, c.B, c.x, 1, h->krylov, h->mode_cycles + 1, h->mode_tol, h->base_seed, h->have_modes ? h->u : nullptr,
+                DZO_TRY(lm_enqueue(s, c.radial, c.dtype, c.N, c.B, c.x, 1, h->krylov, h->mode_cycles + 1, h->mode_tol, h->base_seed, h->have_modes ? h->u : nullptr,
                                    h->basis, h->lam_new, h->u_new, h->res_new, h->info));
             }
             h->have_modes = true;
             DZO_TIMED("hybridef_step", s);
-            DZO_DISPATCH(c.dtype, he_launch<T>(s, c.B, he_args<T>(h)));
+            DZO_DISPATCH(c.dtype, DZO_TRY(he_launch<T>(s, c.radial, c.B, he_args<T>(h))));
             DZO_HIP(hipGetLastError());
         }
         return DZO_OK;

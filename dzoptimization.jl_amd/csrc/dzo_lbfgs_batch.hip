@@ -46,7 +46,7 @@ template <typename T> struct QuenchArgs {
 };
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
-template <typename T, typename F> __global__ __launch_bounds__(64) void quench_wave_eval_kernel(QuenchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void quench_wave_eval_body(QuenchArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
     const int64_t b = blockIdx.x, base = (int64_t)3 * N * b;
     const bool live = lane < N;
@@ -61,10 +61,13 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void quench_w
     if (live) { a.d[base + lane] = px; a.d[base + N + lane] = py; a.d[base + 2 * N + lane] = pz; }
     if (lane == 0) a.stuck[b] = stuck ? 1 : 0;
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void quench_wave_eval_kernel(QuenchArgs<T> a) { quench_wave_eval_body<T, F>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_quench_wave_eval(QuenchArgs<T> a) { quench_wave_eval_body<T, F>(a); }
 
 extern __shared__ __attribute__((aligned(16))) double quench_smem[];
 
-template <typename T, typename F> __global__ __launch_bounds__(64) void quench_wave_step_kernel(QuenchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void quench_wave_step_body(QuenchArgs<T> a) {
     const int64_t b = blockIdx.x;
     if (a.stuck[b]) return;                                  // :456, the whole wave
     const int lane = threadIdx.x, N = a.N, m = a.m;
@@ -117,9 +120,12 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void quench_w
         a.hcount[b] = hc; a.halv[b] = w.halv;
     }
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void quench_wave_step_kernel(QuenchArgs<T> a) { quench_wave_step_body<T, F>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_quench_wave_step(QuenchArgs<T> a) { quench_wave_step_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void quench_block_eval_kernel(QuenchArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void quench_block_eval_body(QuenchArgs<T> a) {
     __shared__ T X[3 * kClMaxN];
     __shared__ double red[2 * kWaves];
     const int tid = threadIdx.x, N = a.N;
@@ -141,9 +147,12 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void quen
     })
     if (tid == 0) a.stuck[b] = stuck ? 1 : 0;
 }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void quench_block_eval_kernel(QuenchArgs<T> a) { quench_block_eval_body<T, F>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_quench_block_eval(QuenchArgs<T> a) { quench_block_eval_body<T, F>(a); }
 
 // HL: the history ring is in LDS (else in a.slab)
-template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void quench_block_step_kernel(QuenchArgs<T> a) {
+template <typename T, typename F, bool HL> __device__ __forceinline__ void quench_block_step_body(QuenchArgs<T> a) {
     const int64_t b = blockIdx.x;
     if (a.stuck[b]) return;                                  // the whole block
     const int tid = threadIdx.x, N = a.N, m = a.m, n3 = 3 * N;
@@ -190,6 +199,9 @@ template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) 
         *ghc_ = hc; *ghalv_ = w.halv;
     }
 }
+template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void quench_block_step_kernel(QuenchArgs<T> a) { quench_block_step_body<T, F, HL>(a); }
+// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void rad_quench_block_step(QuenchArgs<T> a) { quench_block_step_body<T, F, HL>(a); }
 
 // instances that are not stuck: one block, integer sums
 __global__ __launch_bounds__(kBlock) void quench_count_active_kernel(int64_t batch, const int32_t *__restrict__ stuck, int64_t *__restrict__ out) {
@@ -233,31 +245,32 @@ template <typename T> static QuenchArgs<T> qb_args(const dzo_lbfgs_batch_s *h, i
     return a;
 }
 
-template <typename T> static void qb_launch_eval(hipStream_t s, int64_t batch, const QuenchArgs<T> &a) {
-    if (a.N <= 64) hipLaunchKernelGGL((quench_wave_eval_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((quench_block_eval_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+template <typename T, typename F> static void qb_launch_eval(hipStream_t s, int64_t batch, const QuenchArgs<T> &a) {
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(quench_wave_eval_kernel, rad_quench_wave_eval, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL(quench_block_eval_kernel, rad_quench_block_eval, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
-template <typename T> void cl_launch_eval(hipStream_t s, int N, int64_t batch, const T *x, T *f, T *g) {
+template <typename T> int32_t cl_launch_eval(hipStream_t s, int32_t radial, int N, int64_t batch, const T *x, T *f, T *g) {
     QuenchArgs<T> a{};
     a.N = N; a.x = const_cast<T *>(x); a.f = f; a.g = g;
-    qb_launch_eval<T>(s, batch, a);
+    DZO_RADIAL_CASES_(radial, (qb_launch_eval<T, F>(s, batch, a)))
+    return DZO_OK;
 }
-template void cl_launch_eval<double>(hipStream_t, int, int64_t, const double *, double *, double *);
-template void cl_launch_eval<float>(hipStream_t, int, int64_t, const float *, float *, float *);
+template int32_t cl_launch_eval<double>(hipStream_t, int32_t, int, int64_t, const double *, double *, double *);
+template int32_t cl_launch_eval<float>(hipStream_t, int32_t, int, int64_t, const float *, float *, float *);
 
-template <typename T> static const void *qb_step_kernel(const dzo_lbfgs_batch_s *h) {
-    if (h->core.N <= 64) return (const void *)quench_wave_step_kernel<T, LJRadial<T>>;
-    return h->hist_lds ? (const void *)quench_block_step_kernel<T, LJRadial<T>, true> : (const void *)quench_block_step_kernel<T, LJRadial<T>, false>;
+template <typename T, typename F> static const void *qb_step_kernel(const dzo_lbfgs_batch_s *h) {
+    if (h->core.N <= 64) return DZO_RADIAL_KERNEL(quench_wave_step_kernel, rad_quench_wave_step, (T, F));
+    return h->hist_lds ? DZO_RADIAL_KERNEL(quench_block_step_kernel, rad_quench_block_step, (T, F, true)) : DZO_RADIAL_KERNEL(quench_block_step_kernel, rad_quench_block_step, (T, F, false));
 }
 
-template <typename T> static void qb_launch_step(hipStream_t s, const dzo_lbfgs_batch_s *h, int steps) {
+template <typename T, typename F> static void qb_launch_step(hipStream_t s, const dzo_lbfgs_batch_s *h, int steps) {
     const QuenchArgs<T> a = qb_args<T>(h, steps, 0, 0.0);
     const dim3 grid((unsigned)h->core.B);
     const size_t lds = h->core.lds_bytes;
-    if (a.N <= 64) hipLaunchKernelGGL((quench_wave_step_kernel<T, LJRadial<T>>), grid, dim3(64), lds, s, a);
-    else if (h->hist_lds) hipLaunchKernelGGL((quench_block_step_kernel<T, LJRadial<T>, true>), grid, dim3(kBlock), lds, s, a);
-    else hipLaunchKernelGGL((quench_block_step_kernel<T, LJRadial<T>, false>), grid, dim3(kBlock), lds, s, a);
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(quench_wave_step_kernel, rad_quench_wave_step, (T, F), grid, dim3(64), lds, s, a);
+    else if (h->hist_lds) DZO_LAUNCH_RADIAL(quench_block_step_kernel, rad_quench_block_step, (T, F, true), grid, dim3(kBlock), lds, s, a);
+    else DZO_LAUNCH_RADIAL(quench_block_step_kernel, rad_quench_block_step, (T, F, false), grid, dim3(kBlock), lds, s, a);
 }
 
 int32_t cl_count_active(ClCore *c, hipStream_t s, int64_t *active) {
@@ -313,7 +326,7 @@ int32_t dzo_lbfgs_batch_create(int32_t radial, int64_t n_particles, int64_t batc
     dzo_lbfgs_batch_s *h = new (std::nothrow) dzo_lbfgs_batch_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     ClCore &c = h->core;
-    c.device = ctx().device; c.dtype = dtype; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
+    c.device = ctx().device; c.dtype = dtype; c.radial = radial; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
     h->m = history_length;
     const size_t es = dtype_size(dtype), B = (size_t)batch, n3 = 3 * (size_t)n_particles, m = (size_t)history_length;
     const size_t small = 16 * m;                              // rho | alpha
@@ -329,13 +342,14 @@ int32_t dzo_lbfgs_batch_create(int32_t radial, int64_t n_particles, int64_t batc
                            {(void **)&c.stuck, 4 * B}, {(void **)&h->hcount, 4 * B}, {(void **)&c.halv, 4 * B}, {(void **)&c.iters, 8 * B},
                            {(void **)&c.active_dev, 8}, {(void **)&h->rho, 8 * m * B}},
                           "the batched L-BFGS state");
+    const void *step_kernel = nullptr;
+    if (rc == DZO_OK) rc = [&]() -> int32_t { DZO_DISPATCH_RADIAL(radial, dtype, step_kernel = (qb_step_kernel<T, F>(h))); return DZO_OK; }();
     if (rc == DZO_OK)
-        rc = cl_finish_create(&c, dtype == DZO_F64 ? qb_step_kernel<double>(h) : qb_step_kernel<float>(h), "batched L-BFGS state",
-                              "batched L-BFGS constructor", [&](hipStream_t s) -> int32_t {
-                                  DZO_TIMED("lbfgs_batch_init", s);
-                                  DZO_DISPATCH(dtype, qb_launch_eval<T>(s, batch, qb_args<T>(h, 0, 1, initial_step_length)));
-                                  return DZO_OK;
-                              });
+        rc = cl_finish_create(&c, step_kernel, "batched L-BFGS state", "batched L-BFGS constructor", [&](hipStream_t s) -> int32_t {
+            DZO_TIMED("lbfgs_batch_init", s);
+            DZO_DISPATCH_RADIAL(radial, dtype, (qb_launch_eval<T, F>(s, batch, qb_args<T>(h, 0, 1, initial_step_length))));
+            return DZO_OK;
+        });
     if (rc != DZO_OK) { qb_free(h); return rc; }
     *out = h;
     return DZO_OK;
@@ -355,7 +369,7 @@ int32_t dzo_lbfgs_batch_set_max_halvings(dzo_lbfgs_batch_t h, int64_t max_halvin
 int32_t dzo_lbfgs_batch_step(dzo_lbfgs_batch_t h, int32_t steps, int32_t *all_stuck) {
     return cl_step(h, steps, all_stuck, [&](hipStream_t s) -> int32_t {
         DZO_TIMED("lbfgs_batch_step", s);
-        DZO_DISPATCH(h->core.dtype, qb_launch_step<T>(s, h, steps));
+        DZO_DISPATCH_RADIAL(h->core.radial, h->core.dtype, (qb_launch_step<T, F>(s, h, steps)));
         DZO_HIP(hipGetLastError());
         return DZO_OK;
     });
@@ -379,7 +393,7 @@ int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, 
     Context &c = ctx();
     {
         DZO_TIMED("pairwise_batch_energy_gradient", c.stream);
-        DZO_DISPATCH(dtype, cl_launch_eval<T>(c.stream, (int)n_particles, batch, (const T *)points_dev, (T *)energies_dev, (T *)gradients_dev));
+        DZO_DISPATCH(dtype, DZO_TRY(cl_launch_eval<T>(c.stream, radial, (int)n_particles, batch, (const T *)points_dev, (T *)energies_dev, (T *)gradients_dev)));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));

@@ -473,13 +473,16 @@ template <typename T, typename F, bool BLOCK> __device__ __forceinline__ void lm
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
 template <typename T, typename F> __global__ __launch_bounds__(64) void lowmode_wave_kernel(LowmodeArgs<T> a) { lm_run<T, F, false>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_lowm_wave(LowmodeArgs<T> a) { lm_run<T, F, false>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void lowmode_block_kernel(LowmodeArgs<T> a) { lm_run<T, F, true>(a); }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_lowm_block(LowmodeArgs<T> a) { lm_run<T, F, true>(a); }
 
 // ------------------------------------------------------------------------------ host side
-template <typename T> static const void *lm_kernel(bool block) {
-    return block ? (const void *)lowmode_block_kernel<T, LJRadial<T>> : (const void *)lowmode_wave_kernel<T, LJRadial<T>>;
+template <typename T, typename F> static const void *lm_kernel(bool block) {
+    return block ? DZO_RADIAL_KERNEL(lowmode_block_kernel, rad_lowm_block, (T, F)) : DZO_RADIAL_KERNEL(lowmode_wave_kernel, rad_lowm_wave, (T, F));
 }
 
 static size_t lm_lds_bytes(int N, int K, int32_t dtype) {
@@ -487,9 +490,9 @@ static size_t lm_lds_bytes(int N, int K, int32_t dtype) {
     return sizeof(double) * kLmDoubles + ((elems * dtype_size(dtype) + 15) & ~(size_t)15);
 }
 
-template <typename T> static void lm_launch(hipStream_t s, int64_t batch, size_t lds, const LowmodeArgs<T> &a) {
-    if (a.N <= 64) hipLaunchKernelGGL((lowmode_wave_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), lds, s, a);
-    else hipLaunchKernelGGL((lowmode_block_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), lds, s, a);
+template <typename T, typename F> static void lm_launch(hipStream_t s, int64_t batch, size_t lds, const LowmodeArgs<T> &a) {
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(lowmode_wave_kernel, rad_lowm_wave, (T, F), dim3((unsigned)batch), dim3(64), lds, s, a);
+    else DZO_LAUNCH_RADIAL(lowmode_block_kernel, rad_lowm_block, (T, F), dim3((unsigned)batch), dim3(kBlock), lds, s, a);
 }
 
 // ------------------------------------------------------------------------------ the asynchronous path (dzo_chain.h)
@@ -501,22 +504,24 @@ static int lm_krylov(int N, int krylov, int project_rigid) {
 
 // gfx950 has 160 KiB of LDS per CU; dynamic requests above the default need the attribute.  It belongs to the kernel: raised to
 // the limit, so that no later call lowers it
-int32_t lm_prepare(int32_t dtype, int N, int krylov, int project_rigid) {
+int32_t lm_prepare(int32_t radial, int32_t dtype, int N, int krylov, int project_rigid) {
     if (lm_lds_bytes(N, lm_krylov(N, krylov, project_rigid), dtype) > 48 * 1024) {
-        DZO_HIP(hipFuncSetAttribute(dtype == DZO_F64 ? lm_kernel<double>(N > 64) : lm_kernel<float>(N > 64), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kClLdsMax));
+        const void *k = nullptr;
+        DZO_DISPATCH_RADIAL(radial, dtype, k = (lm_kernel<T, F>(N > 64)));
+        DZO_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax));
     }
     return DZO_OK;
 }
 
-int32_t lm_enqueue(hipStream_t s, int32_t dtype, int N, int64_t batch, const void *points, int32_t project_rigid, int32_t krylov, int32_t max_cycles,
+int32_t lm_enqueue(hipStream_t s, int32_t radial, int32_t dtype, int N, int64_t batch, const void *points, int32_t project_rigid, int32_t krylov, int32_t max_cycles,
                    double res_tol, uint64_t base_seed, const void *start, void *basis, void *eigenvalues, void *vectors, double *residuals,
                    int32_t *info) {
     const int K = lm_krylov(N, krylov, project_rigid);
     const size_t lds = lm_lds_bytes(N, K, dtype);
-    DZO_DISPATCH(dtype, lm_launch<T>(s, batch, lds,
-                                     LowmodeArgs<T>{N, K, max_cycles, project_rigid != 0, res_tol, base_seed, (const T *)points, (const T *)start,
-                                                    (T *)basis, (T *)eigenvalues, (T *)vectors, residuals, info}));
+    DZO_DISPATCH_RADIAL(radial, dtype,
+                        (lm_launch<T, F>(s, batch, lds,
+                                         LowmodeArgs<T>{N, K, max_cycles, project_rigid != 0, res_tol, base_seed, (const T *)points, (const T *)start,
+                                                        (T *)basis, (T *)eigenvalues, (T *)vectors, residuals, info})));
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
@@ -555,10 +560,10 @@ int32_t dzo_pairwise_batch_lowest_mode(int32_t radial, int64_t n_particles, int6
         }
         DZO_HIP(e);
     }
-    int32_t rc = lm_prepare(dtype, N, krylov, project_rigid);
+    int32_t rc = lm_prepare(radial, dtype, N, krylov, project_rigid);
     if (rc == DZO_OK) {
         DZO_TIMED("lowmode", c.stream);
-        rc = lm_enqueue(c.stream, dtype, N, batch, points_dev, project_rigid, krylov, max_cycles, res_tol, base_seed, start_dev, work, eigenvalues_dev,
+        rc = lm_enqueue(c.stream, radial, dtype, N, batch, points_dev, project_rigid, krylov, max_cycles, res_tol, base_seed, start_dev, work, eigenvalues_dev,
                         vectors_dev, residuals_dev, info_dev);
     }
     hipError_t e = hipSuccess;

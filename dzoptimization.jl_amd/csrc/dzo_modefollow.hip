@@ -67,8 +67,8 @@ template <typename T> __device__ __forceinline__ void mf_record(const Modefollow
     a.status[b] = r.status;
 }
 
-// grid batch, block 256
-template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_kernel(ModefollowArgs<T> a) {
+// grid batch, block 256; RF is the radial functor (F is the projections' name here)
+template <typename T, typename RF> __device__ __forceinline__ void modefollow_step_body(ModefollowArgs<T> a) {
     __shared__ T S[6 * kMfMaxDim];                           // X | G | L | F | H | W, n elements each
     __shared__ double ov[kMfMaxDim];                         // |V[:,c].w|
     __shared__ double red[2 * kWaves];
@@ -99,7 +99,7 @@ template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_
             const bool live = lane < N;
             const T x = live ? X[lane] : T(0), y = live ? X[N + lane] : T(0), z = live ? X[2 * N + lane] : T(0);
             T e0, gx, gy, gz;
-            cl_wave_eval<T, LJRadial<T>>(N, lane, x, y, z, e0, gx, gy, gz);
+            cl_wave_eval<T, RF>(N, lane, x, y, z, e0, gx, gy, gz);
             if (live) { G[lane] = gx; G[N + lane] = gy; G[2 * N + lane] = gz; }
             if (lane == 0) Es = e0;
         }
@@ -107,7 +107,7 @@ template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_
         E = Es;
     } else {
         T gx[kClPer], gy[kClPer], gz[kClPer];
-        cl_block_eval<T, LJRadial<T>>(N, tid, X, red, par, E, gx, gy, gz);
+        cl_block_eval<T, RF>(N, tid, X, red, par, E, gx, gy, gz);
         CL_FOR_OWN(i, G[i] = gx[q]; G[N + i] = gy[q]; G[2 * N + i] = gz[q];)
         __syncthreads();
     }
@@ -235,9 +235,13 @@ template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_
     rec.steplen = capped ? a.max_step : hn;
     if (tid == 0) mf_record(a, b, rec);
 }
+template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_kernel(ModefollowArgs<T> a) { modefollow_step_body<T, LJRadial<T>>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename RF> __global__ __launch_bounds__(kBlock) void rad_mfollow_step(ModefollowArgs<T> a) { modefollow_step_body<T, RF>(a); }
 
-template <typename T> static void mf_launch(hipStream_t s, int64_t batch, const ModefollowArgs<T> &a) {
-    hipLaunchKernelGGL((modefollow_step_kernel<T>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+template <typename T, typename RF> static void mf_launch(hipStream_t s, int64_t batch, const ModefollowArgs<T> &a) {
+    using F = RF;
+    DZO_LAUNCH_RADIAL2(modefollow_step_kernel, (T), rad_mfollow_step, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 // the argument checks of apply and create
@@ -334,7 +338,7 @@ int32_t dzo_modefollow_batch_apply(int32_t radial, int64_t n_particles, int64_t 
     {
         DZO_TIMED("modefollow_step", c.stream);
         DZO_HIP(hipMemsetAsync(status_dev, 0, 4 * (size_t)batch, c.stream));   // every instance ACTIVE
-        DZO_DISPATCH(dtype, ModefollowArgs<T> a;
+        DZO_DISPATCH_RADIAL(radial, dtype, ModefollowArgs<T> a;
                      a.N = (int)n_particles; a.target_index = target_index; a.start_mode = start_mode;
                      a.zero_tol = (T)zero_tol; a.max_step = max_step; a.grad_tol = grad_tol;
                      a.x = (T *)points_dev; a.lam = (const T *)eigenvalues_dev; a.V = (const T *)eigenvectors_dev;
@@ -342,7 +346,7 @@ int32_t dzo_modefollow_batch_apply(int32_t radial, int64_t n_particles, int64_t 
                      a.E = (T *)energies_dev; a.g = (T *)gradients_dev; a.F = (T *)projections_dev;
                      a.grms = grms_dev; a.steplen = step_lengths_dev;
                      a.status = status_dev; a.index = index_dev; a.zeros = zeros_dev; a.followed = followed_dev; a.iters = nullptr;
-                     mf_launch<T>(c.stream, batch, a));
+                     (mf_launch<T, F>(c.stream, batch, a)));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));
@@ -360,7 +364,7 @@ int32_t dzo_modefollow_batch_create(int32_t radial, int64_t n_particles, int64_t
     dzo_modefollow_batch_s *h = new (std::nothrow) dzo_modefollow_batch_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     ClCore &c = h->core;
-    c.device = ctx().device; c.dtype = dtype; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
+    c.device = ctx().device; c.dtype = dtype; c.radial = radial; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
     h->target_index = target_index; h->max_step = max_step; h->zero_tol = zero_tol; h->grad_tol = grad_tol;
     const size_t es = dtype_size(dtype), B = (size_t)batch, n3 = 3 * (size_t)n_particles;
     const bool in_memory = symeig_plan((int64_t)n3, dtype).storage == DZO_SYMEIG_STORAGE_MEMORY;
@@ -375,7 +379,7 @@ int32_t dzo_modefollow_batch_create(int32_t radial, int64_t n_particles, int64_t
             DZO_TRY(se_prepare((int64_t)n3, dtype));
             DZO_TIMED("modefollow_init", s);
             // the energies and gradients of the points as given; every other record is zero until the first step
-            DZO_DISPATCH(dtype, cl_launch_eval<T>(s, c.N, batch, (const T *)c.x, (T *)c.f, (T *)c.g));
+            DZO_DISPATCH(dtype, DZO_TRY(cl_launch_eval<T>(s, radial, c.N, batch, (const T *)c.x, (T *)c.f, (T *)c.g)));
             return DZO_OK;
         });
     if (rc != DZO_OK) { mf_free(h); return rc; }
@@ -417,14 +421,14 @@ int32_t dzo_modefollow_batch_step(dzo_modefollow_batch_t h, int32_t steps, int32
         for (int32_t k = 0; k < steps; ++k) {
             {
                 DZO_TIMED("modefollow_hessian", s);
-                DZO_TRY(hb_enqueue_hessian(s, c.dtype, c.N, c.B, c.x, h->hess));
+                DZO_TRY(hb_enqueue_hessian(s, c.radial, c.dtype, c.N, c.B, c.x, h->hess));
             }
             {
                 DZO_TIMED("modefollow_eigen", s);
                 DZO_TRY(se_enqueue(s, 3 * (int64_t)c.N, c.B, c.dtype, h->hess, h->work, h->lam, h->V, h->sweeps, 0));
             }
             DZO_TIMED("modefollow_step", s);
-            DZO_DISPATCH(c.dtype, mf_launch<T>(s, c.B, mf_args<T>(h)));
+            DZO_DISPATCH_RADIAL(c.radial, c.dtype, (mf_launch<T, F>(s, c.B, mf_args<T>(h))));
             DZO_HIP(hipGetLastError());
         }
         return DZO_OK;

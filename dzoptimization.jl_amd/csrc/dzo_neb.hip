@@ -48,7 +48,7 @@ template <typename T> struct NebArgs {
     int64_t *iters;            // (batch) moves made so far; null: none
 };
 
-template <typename T, bool BLOCK> __device__ __forceinline__ void neb_run(const NebArgs<T> &a) {
+template <typename T, typename F, bool BLOCK> __device__ __forceinline__ void neb_run(const NebArgs<T> &a) {
     constexpr int PER = BLOCK ? kClPer : 1;
     const int64_t b = blockIdx.x;
     if (a.status[b] != DZO_NEB_ACTIVE) return;               // frozen: the whole block
@@ -115,9 +115,9 @@ template <typename T, bool BLOCK> __device__ __forceinline__ void neb_run(const 
         if constexpr (BLOCK) {
             store(stage, x);
             __syncthreads();
-            cl_block_eval<T, LJRadial<T>>(N, tid, stage, red, par, E, g[0], g[1], g[2]);
+            cl_block_eval<T, F>(N, tid, stage, red, par, E, g[0], g[1], g[2]);
         } else {
-            cl_wave_eval<T, LJRadial<T>>(N, own, x[0][0], x[1][0], x[2][0], E, g[0][0], g[1][0], g[2][0]);
+            cl_wave_eval<T, F>(N, own, x[0][0], x[1][0], x[2][0], E, g[0][0], g[1][0], g[2][0]);
         }
         if (keep_g) store(Fb + (size_t)m * n, g);
         if (grad) store(grad + base + (int64_t)m * n, g);
@@ -294,8 +294,11 @@ template <typename T, bool BLOCK> __device__ __forceinline__ void neb_run(const 
 }
 
 // ------------------------------------------------------------------------------ the two shapes: grid batch, block 256
-template <typename T> __global__ __launch_bounds__(kBlock) void neb_wave_kernel(NebArgs<T> a) { neb_run<T, false>(a); }
-template <typename T> __global__ __launch_bounds__(kBlock) void neb_block_kernel(NebArgs<T> a) { neb_run<T, true>(a); }
+template <typename T> __global__ __launch_bounds__(kBlock) void neb_wave_kernel(NebArgs<T> a) { neb_run<T, LJRadial<T>, false>(a); }
+template <typename T> __global__ __launch_bounds__(kBlock) void neb_block_kernel(NebArgs<T> a) { neb_run<T, LJRadial<T>, true>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_band_wave(NebArgs<T> a) { neb_run<T, F, false>(a); }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_band_block(NebArgs<T> a) { neb_run<T, F, true>(a); }
 
 // x_m = fma(T(m / (M - 1)), b - a, a) for the interior images, copies of a and b at the ends: one thread per element
 template <typename T> __global__ __launch_bounds__(kBlock) void neb_interp_kernel(int n, int M, int64_t total, const T *a, const T *b, T *band) {
@@ -309,18 +312,25 @@ template <typename T> __global__ __launch_bounds__(kBlock) void neb_interp_kerne
     band[idx] = m == 0 ? xa : m == M - 1 ? xb : dfma<T>(t, xb - xa, xa);
 }
 
-// the LDS attribute of the kernel that serves (N, M, dtype), once per call that launches it: it belongs to the kernel and is
+template <typename T, typename F> static const void *neb_kernel(const NebPlan &plan) {
+    return plan.shape == DZO_NEB_SHAPE_WAVE ? DZO_RADIAL_KERNEL2(neb_wave_kernel, (T), rad_band_wave, (T, F)) : DZO_RADIAL_KERNEL2(neb_block_kernel, (T), rad_band_block, (T, F));
+}
+
+// the LDS attribute of the kernel that serves (radial, N, M, dtype), once per call that launches it: it belongs to the kernel and is
 // raised to the limit, so that a later, smaller request does not lower it
-static int32_t neb_prepare(int32_t dtype, const NebPlan &plan) {
+static int32_t neb_prepare(int32_t radial, int32_t dtype, const NebPlan &plan) {
     if (plan.lds_bytes <= 48 * 1024) return DZO_OK;
-    DZO_DISPATCH(dtype, const void *k = plan.shape == DZO_NEB_SHAPE_WAVE ? (const void *)neb_wave_kernel<T> : (const void *)neb_block_kernel<T>;
-                 DZO_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax)));
+    DZO_DISPATCH_RADIAL(radial, dtype, DZO_HIP(hipFuncSetAttribute((neb_kernel<T, F>(plan)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax)));
     return DZO_OK;
 }
 
-template <typename T> static void neb_launch(hipStream_t s, int64_t batch, const NebPlan &plan, const NebArgs<T> &a) {
-    if (plan.shape == DZO_NEB_SHAPE_WAVE) hipLaunchKernelGGL((neb_wave_kernel<T>), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
-    else hipLaunchKernelGGL((neb_block_kernel<T>), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
+template <typename T, typename F> static void neb_launch_radial(hipStream_t s, int64_t batch, const NebPlan &plan, const NebArgs<T> &a) {
+    if (plan.shape == DZO_NEB_SHAPE_WAVE) DZO_LAUNCH_RADIAL2(neb_wave_kernel, (T), rad_band_wave, (T, F), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
+    else DZO_LAUNCH_RADIAL2(neb_block_kernel, (T), rad_band_block, (T, F), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
+}
+template <typename T> static int32_t neb_launch(hipStream_t s, int32_t radial, int64_t batch, const NebPlan &plan, const NebArgs<T> &a) {
+    DZO_RADIAL_CASES_(radial, (neb_launch_radial<T, F>(s, batch, plan, a)))
+    return DZO_OK;
 }
 
 // the argument checks of every entry point (the ones without a radial pass Lennard-Jones)
@@ -442,7 +452,7 @@ int32_t dzo_neb_batch_apply(int32_t radial, int64_t n_particles, int32_t n_image
     DZO_TRY(require_same_backend(where, cite, highest_dev, "highest", nullptr, ""));
     Context &c = ctx();
     const NebPlan plan = neb_plan(n_particles, n_images, dtype);
-    DZO_TRY(neb_prepare(dtype, plan));
+    DZO_TRY(neb_prepare(radial, dtype, plan));
     void *work = nullptr;                                    // MEMORY storage iterates on the forces: they need a home
     if (plan.storage == DZO_NEB_STORAGE_MEMORY && !forces_dev)
         DZO_TRY(device_alloc(&work, dtype_size(dtype) * 3 * (size_t)n_particles * (size_t)n_images * (size_t)batch, "the elastic band's forces", false));
@@ -456,7 +466,7 @@ int32_t dzo_neb_batch_apply(int32_t radial, int64_t n_particles, int32_t n_image
                          a.band = (T *)band_dev; a.vel = (T *)velocities_dev; a.force = (T *)(forces_dev ? forces_dev : work);
                          a.tan = (T *)tangents_dev; a.grad = (T *)gradients_dev; a.E = (T *)energies_dev; a.frms = force_rms_dev; a.res = residuals_dev;
                          a.climbing = climbing_dev; a.highest = highest_dev; a.status = status_dev; a.iters = nullptr;
-                         neb_launch<T>(c.stream, batch, plan, a));
+                         DZO_TRY(neb_launch<T>(c.stream, radial, batch, plan, a)));
             DZO_HIP(hipGetLastError());
         }
         DZO_HIP(hipStreamSynchronize(c.stream));
@@ -478,7 +488,7 @@ int32_t dzo_neb_batch_create(int32_t radial, int64_t n_particles, int32_t n_imag
     dzo_neb_batch_s *h = new (std::nothrow) dzo_neb_batch_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     ClCore &c = h->core;
-    c.device = ctx().device; c.dtype = dtype; c.N = (int)n_particles; c.B = batch; c.x = band_dev;
+    c.device = ctx().device; c.dtype = dtype; c.radial = radial; c.N = (int)n_particles; c.B = batch; c.x = band_dev;
     h->M = n_images; h->climb = climb != 0; h->climb_after = climb_after; h->spring = spring; h->dt = dt; h->max_move = max_move; h->force_tol = force_tol;
     h->plan = neb_plan(n_particles, n_images, dtype);
     const size_t es = dtype_size(dtype), B = (size_t)batch, M = (size_t)n_images, n3 = 3 * (size_t)n_particles;
@@ -486,13 +496,13 @@ int32_t dzo_neb_batch_create(int32_t radial, int64_t n_particles, int32_t n_imag
                            {&h->vel, es * n3 * M * B}, {&h->force, es * n3 * M * B}, {&h->tan, es * n3 * M * B}, {(void **)&h->frms, 8 * M * B},
                            {(void **)&h->res, 8 * B}, {(void **)&h->climbing, 4 * B}, {(void **)&h->highest, 4 * B}},
                           "the elastic-band state");
-    if (rc == DZO_OK) rc = neb_prepare(dtype, h->plan);
+    if (rc == DZO_OK) rc = neb_prepare(radial, dtype, h->plan);
     if (rc == DZO_OK)
         rc = cl_finish_create(&c, nullptr, "elastic-band state", "elastic-band constructor", [&](hipStream_t s) -> int32_t {
             DZO_TIMED("neb_init", s);
             DZO_HIP(hipMemsetAsync(h->climbing, 0xff, 4 * B, s));   // -1: no image climbs yet
             // the energies of the fixed ends; every other record is zero until the first iteration
-            DZO_DISPATCH(dtype, neb_launch<T>(s, batch, h->plan, neb_args<T>(h, 0, 1)));
+            DZO_DISPATCH(dtype, DZO_TRY(neb_launch<T>(s, radial, batch, h->plan, neb_args<T>(h, 0, 1))));
             return DZO_OK;
         });
     if (rc != DZO_OK) { neb_free(h); return rc; }
@@ -513,7 +523,7 @@ int32_t dzo_neb_batch_step(dzo_neb_batch_t h, int32_t steps, int32_t *all_done) 
     return cl_step(h, steps, all_done, [&](hipStream_t s) -> int32_t {
         const ClCore &c = h->core;
         DZO_TIMED("neb_step", s);
-        DZO_DISPATCH(c.dtype, neb_launch<T>(s, c.B, h->plan, neb_args<T>(h, steps, 0)));
+        DZO_DISPATCH(c.dtype, DZO_TRY(neb_launch<T>(s, c.radial, c.B, h->plan, neb_args<T>(h, steps, 0))));
         DZO_HIP(hipGetLastError());
         return DZO_OK;
     });

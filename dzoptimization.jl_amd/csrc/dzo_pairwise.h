@@ -56,6 +56,81 @@ template <typename T> struct LJRadial {
     }
 };
 
+// The Morse pair term in reduced units (pair minimum at r = 1, depth 1): E(r) = t^2 - 2 t, t = exp(RHO (1 - r)), as functions of
+// r2 like the above (derivatives with respect to r2, not r).  RHO is a template integer: one more range is one more line in
+// DZO_RADIAL_CASES_ and one more constant in include/dzo.h.  One fixed operation order, every fma written out:
+//   r = sqrt(r2) (IEEE), a = RHO * (1 - r), t = exp(a) (the device library's exp / expf), tm1 = t - 1
+//   energy = fma(t, t, -(t + t))
+//   first  = ((-RHO * t) * tm1) / r                                      dE/d(r2) = -RHO t (t - 1) / r
+//   second = ((RHO * t) * fma(RHO * r, (t + t) - 1, tm1)) / ((r2 + r2) * r)   d2E/d(r2)2 = RHO t (RHO r (2t - 1) + (t - 1)) / (2 r2 r)
+// r, t and tm1 are the same expressions in all three members, so a kernel that calls two of them on one r2 computes one square
+// root and one exp per pair (checked in the gfx950 code of the quench, hvp and tempering kernels).
+// At r2 = 0 (self term, padding) first and second are infinite or NaN and the energy is finite; all three are dropped by the
+// caller's select like the Lennard-Jones values.
+template <typename T> __device__ __forceinline__ T pw_sqrt(T v);
+template <> __device__ __forceinline__ double pw_sqrt<double>(double v) { return __builtin_sqrt(v); }
+template <> __device__ __forceinline__ float pw_sqrt<float>(float v) { return __builtin_sqrtf(v); }
+template <typename T> __device__ __forceinline__ T pw_exp(T v);
+template <> __device__ __forceinline__ double pw_exp<double>(double v) { return ::exp(v); }
+template <> __device__ __forceinline__ float pw_exp<float>(float v) { return ::expf(v); }
+
+template <typename T, int RHO> struct MorseRadial {
+    static __device__ __forceinline__ T decay(T r) { return pw_exp<T>(T(RHO) * (T(1) - r)); }   // t
+    static __device__ __forceinline__ T energy(T r2) {
+        const T t = decay(pw_sqrt<T>(r2));
+        return dfma<T>(t, t, -pw_twice(t));
+    }
+    static __device__ __forceinline__ T first(T r2) {
+        const T r = pw_sqrt<T>(r2);
+        const T t = decay(r);
+        const T tm1 = t - T(1);
+        return ((T(-RHO) * t) * tm1) / r;                    // IEEE division
+    }
+    static __device__ __forceinline__ T second(T r2) {
+        const T r = pw_sqrt<T>(r2);
+        const T t = decay(r);
+        const T tm1 = t - T(1);
+        const T inner = dfma<T>(T(RHO) * r, pw_twice(t) - T(1), tm1);
+        return ((T(RHO) * t) * inner) / (pw_twice(r2) * r);
+    }
+};
+
+// (radial, dtype) -> (T, F): the statement runs with `using T` and `using F` of the selected pair; an unknown selector or type
+// leaves the calling function with DZO_ERR_INVALID (pw_check_args has the message for callers that check first).  Every
+// launch and every kernel-pointer lookup that depends on the radial goes through this one table.
+#define DZO_RADIAL_CASES_(radial, ...)                                                                    \
+    if ((radial) == DZO_RADIAL_LENNARD_JONES) { using F = ::dzo::LJRadial<T>; __VA_ARGS__; }              \
+    else if ((radial) == DZO_RADIAL_MORSE_RHO6) { using F = ::dzo::MorseRadial<T, 6>; __VA_ARGS__; }      \
+    else if ((radial) == DZO_RADIAL_MORSE_RHO14) { using F = ::dzo::MorseRadial<T, 14>; __VA_ARGS__; }    \
+    else { ::dzo::set_error("unknown radial function %d", (int)(radial)); return DZO_ERR_INVALID; }
+// Which kernel serves (T, F).  The Lennard-Jones instantiation of every cluster kernel keeps the entry point it always had; the
+// other radials run the SAME body (a __device__ function, or the unit's run function) through a second entry point with a name
+// of its own, rad_*.  So the set of Lennard-Jones kernels, their names and their code do not depend on how many radials
+// there are.  LJK and RADK are the two templates, TARGS their parenthesised template arguments.
+template <typename T, typename F> struct PwIsLJ { static constexpr bool value = false; };
+template <typename T> struct PwIsLJ<T, LJRadial<T>> { static constexpr bool value = true; };
+#define DZO_UNPAREN(...) __VA_ARGS__
+#define DZO_RADIAL_KERNEL2(LJK, LJARGS, RADK, RADARGS)                                                    \
+    ([]() -> const void * {                                                                               \
+        if constexpr (::dzo::PwIsLJ<T, F>::value) return (const void *)LJK<DZO_UNPAREN LJARGS>;           \
+        else return (const void *)RADK<DZO_UNPAREN RADARGS>;                                              \
+    }())
+#define DZO_LAUNCH_RADIAL2(LJK, LJARGS, RADK, RADARGS, grid, block, lds, s, ...)                          \
+    do {                                                                                                  \
+        if constexpr (::dzo::PwIsLJ<T, F>::value) hipLaunchKernelGGL((LJK<DZO_UNPAREN LJARGS>), grid, block, lds, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL((RADK<DZO_UNPAREN RADARGS>), grid, block, lds, s, __VA_ARGS__);           \
+    } while (0)
+// (the units whose Lennard-Jones kernels are templates of T alone pass (T) and (T, F))
+#define DZO_RADIAL_KERNEL(LJK, RADK, TARGS) DZO_RADIAL_KERNEL2(LJK, TARGS, RADK, TARGS)
+#define DZO_LAUNCH_RADIAL(LJK, RADK, TARGS, ...) DZO_LAUNCH_RADIAL2(LJK, TARGS, RADK, TARGS, __VA_ARGS__)
+
+#define DZO_DISPATCH_RADIAL(radial, dtype, ...)                                                           \
+    do {                                                                                                  \
+        if ((dtype) == DZO_F64) { using T = double; DZO_RADIAL_CASES_(radial, __VA_ARGS__) }              \
+        else if ((dtype) == DZO_F32) { using T = float; DZO_RADIAL_CASES_(radial, __VA_ARGS__) }          \
+        else { ::dzo::set_error("bad dtype %d", (int)(dtype)); return DZO_ERR_INVALID; }                  \
+    } while (0)
+
 // `self ? 0 : e(r2)` as a select of two computed values: the term is evaluated in every lane and then dropped (ifelse, :145),
 // never branched around -- a conditional EXPRESSION is a branch in the source, and the compiler keeps a branch around a
 // division sequence ("skip the expensive operand"): an exec-mask save / restore per pair that is never taken and that keeps

@@ -289,7 +289,8 @@ int32_t device_alloc(void **p, size_t bytes, const char *what_for, bool zero_fil
 
 int32_t pw_check_args(int32_t radial, int32_t dtype, int64_t N, int64_t count, const char *count_name, int64_t max_particles, int32_t over_max,
                       const char *holder) {
-    DZO_REQUIRE(radial == DZO_RADIAL_LENNARD_JONES, DZO_ERR_INVALID, "unknown radial function %d (DZO_RADIAL_LENNARD_JONES = 0 is the one built in)", radial);
+    DZO_REQUIRE(radial == DZO_RADIAL_LENNARD_JONES || radial == DZO_RADIAL_MORSE_RHO6 || radial == DZO_RADIAL_MORSE_RHO14, DZO_ERR_INVALID,
+                "unknown radial function %d (built in: DZO_RADIAL_LENNARD_JONES = 0, DZO_RADIAL_MORSE_RHO6 = 2, DZO_RADIAL_MORSE_RHO14 = 3)", radial);
     DZO_REQUIRE(dtype == DZO_F32 || dtype == DZO_F64, DZO_ERR_INVALID, "bad dtype %d", dtype);
     DZO_REQUIRE(N >= 1, DZO_ERR_INVALID, "n_particles must be at least 1 (got %lld)", (long long)N);
     DZO_REQUIRE(count >= 1 && count <= ((int64_t)1 << 30), DZO_ERR_INVALID, "%s must be in 1 .. 2^30 (got %lld)", count_name, (long long)count);
@@ -314,16 +315,15 @@ static int32_t pw_check_common(int32_t radial, int64_t N, int32_t dtype) {
 int32_t pairwise_energy_async(hipStream_t s, int32_t radial, int64_t N, int32_t dtype, const void *x, const void *y, const void *z,
                               double *ws, double *result_dev) {
     DZO_TRY(pw_check_common(radial, N, dtype));
-    DZO_DISPATCH(dtype, return (pw_energy_t<T, LJRadial<T>>(s, N, (const T *)x, (const T *)y, (const T *)z, ws, result_dev)));
+    DZO_DISPATCH_RADIAL(radial, dtype, return (pw_energy_t<T, F>(s, N, (const T *)x, (const T *)y, (const T *)z, ws, result_dev)));
     return DZO_OK;
 }
 
 int32_t pairwise_gradient_async(hipStream_t s, int32_t radial, int64_t N, int32_t dtype, void *gx, void *gy, void *gz, const void *x,
                                 const void *y, const void *z, double *ws) {
     DZO_TRY(pw_check_common(radial, N, dtype));
-    DZO_DISPATCH(dtype, return (pw_rows_t<T, LJRadial<T>, kPwGradient>(s, N, (T *)gx, (T *)gy, (T *)gz, (const T *)x, (const T *)y,
-                                                                         (const T *)z, (const T *)nullptr, (const T *)nullptr,
-                                                                         (const T *)nullptr, ws)));
+    DZO_DISPATCH_RADIAL(radial, dtype, return (pw_rows_t<T, F, kPwGradient>(s, N, (T *)gx, (T *)gy, (T *)gz, (const T *)x, (const T *)y, (const T *)z,
+                                                                            (const T *)nullptr, (const T *)nullptr, (const T *)nullptr, ws)));
     return DZO_OK;
 }
 
@@ -409,9 +409,9 @@ int32_t dzo_pairwise_hvp(int32_t radial, int64_t n_particles, int32_t dtype, voi
     DZO_TRY(pw_ctx_workspace(n_particles, &ws));
     {
         DZO_TIMED("pairwise_hvp", c.stream);
-        DZO_DISPATCH(dtype, DZO_TRY((pw_rows_t<T, LJRadial<T>, kPwHvp>(c.stream, n_particles, (T *)px_dev, (T *)py_dev, (T *)pz_dev,
-                                                                        (const T *)x_dev, (const T *)y_dev, (const T *)z_dev,
-                                                                        (const T *)u_dev, (const T *)v_dev, (const T *)w_dev, ws))));
+        DZO_DISPATCH_RADIAL(radial, dtype, DZO_TRY((pw_rows_t<T, F, kPwHvp>(c.stream, n_particles, (T *)px_dev, (T *)py_dev, (T *)pz_dev,
+                                                                            (const T *)x_dev, (const T *)y_dev, (const T *)z_dev,
+                                                                            (const T *)u_dev, (const T *)v_dev, (const T *)w_dev, ws))));
     }
     DZO_HIP(hipStreamSynchronize(c.stream));
     return DZO_OK;
@@ -430,8 +430,9 @@ int32_t dzo_pairwise_energy_delta(int32_t radial, int64_t n_particles, int32_t d
     Context &c = ctx();
     {
         DZO_TIMED("pairwise_energy_delta", c.stream);
-        DZO_DISPATCH(dtype, hipLaunchKernelGGL((pairwise_energy_delta_kernel<T, LJRadial<T>>), dim3(1), dim3(kBlock), 0, c.stream, n_particles,
-                                               (const T *)x_dev, (const T *)y_dev, (const T *)z_dev, i, (T)x_new, (T)y_new, (T)z_new, c.scratch));
+        DZO_DISPATCH_RADIAL(radial, dtype, hipLaunchKernelGGL((pairwise_energy_delta_kernel<T, F>), dim3(1), dim3(kBlock), 0, c.stream, n_particles,
+                                                              (const T *)x_dev, (const T *)y_dev, (const T *)z_dev, i, (T)x_new, (T)y_new, (T)z_new,
+                                                              c.scratch));
         DZO_HIP(hipGetLastError());
     }
     DZO_TRY(copy_blocking(c.host_scalar, c.scratch, sizeof(double), hipMemcpyDeviceToHost));

@@ -103,7 +103,7 @@ __host__ __device__ __forceinline__ int sk_pow2(int n) {
 }
 
 // ------------------------------------------------------------------------------ fingerprints, WAVE shape: grid batch, block 64
-template <typename T, typename F> __global__ __launch_bounds__(64) void structfp_wave_kernel(StructFpArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void structfp_wave_body(StructFpArgs<T> a) {
     using Key = typename StructKey<T>::type;
     const int lane = threadIdx.x, N = a.N;
     const int64_t b = blockIdx.x, base = (int64_t)3 * N * b, obase = (int64_t)2 * N * b;
@@ -130,9 +130,12 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void structfp
     if (live) { a.fp[obase + lane] = sk_value<T>(ke); a.fp[obase + N + lane] = sk_value<T>(kd); }
     if (a.energy && lane == 0) a.energy[b] = E;
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void structfp_wave_kernel(StructFpArgs<T> a) { structfp_wave_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_sfp_wave(StructFpArgs<T> a) { structfp_wave_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ fingerprints, BLOCK shape: grid batch, block 256
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void structfp_block_kernel(StructFpArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void structfp_block_body(StructFpArgs<T> a) {
     using Key = typename StructKey<T>::type;
     static_assert(sizeof(Key) == sizeof(T), "the sort buffers take the place of the point");
     __shared__ T X[3 * kStructMaxN];
@@ -192,6 +195,9 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void stru
     for (int i = tid; i < N; i += kBlock) { a.fp[obase + i] = sk_value<T>(KE[i]); a.fp[obase + N + i] = sk_value<T>(KD[i]); }
     if (a.energy && tid == 0) a.energy[b] = E;
 }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void structfp_block_kernel(StructFpArgs<T> a) { structfp_block_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_sfp_block(StructFpArgs<T> a) { structfp_block_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ the match matrix: grid (words / 4, batch), block 256
 // wave (k, w) forms word w of row k: bit l is the pair (k, j = 64 w + l)
@@ -254,9 +260,9 @@ __global__ __launch_bounds__(64) void structlabel_kernel(int batch, int words, c
 }
 
 // ------------------------------------------------------------------------------ host side
-template <typename T> static void sf_launch(hipStream_t s, int64_t batch, const StructFpArgs<T> &a) {
-    if (a.N <= 64) hipLaunchKernelGGL((structfp_wave_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((structfp_block_kernel<T, LJRadial<T>>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+template <typename T, typename F> static void sf_launch(hipStream_t s, int64_t batch, const StructFpArgs<T> &a) {
+    if (a.N <= 64) DZO_LAUNCH_RADIAL(structfp_wave_kernel, rad_sfp_wave, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL(structfp_block_kernel, rad_sfp_block, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 template <typename T> static void sf_launch_cmp(hipStream_t s, int64_t length, int batch, int words, double tol, const void *fp, unsigned long long *bits) {
@@ -282,7 +288,8 @@ int32_t dzo_structure_batch_fingerprint(int32_t radial, int64_t n_particles, int
     Context &c = ctx();
     {
         DZO_TIMED("structure_fingerprint", c.stream);
-        DZO_DISPATCH(dtype, sf_launch<T>(c.stream, batch, StructFpArgs<T>{(int)n_particles, (const T *)points_dev, (T *)fingerprints_dev, (T *)energies_dev}));
+        DZO_DISPATCH_RADIAL(radial, dtype,
+                            (sf_launch<T, F>(c.stream, batch, StructFpArgs<T>{(int)n_particles, (const T *)points_dev, (T *)fingerprints_dev, (T *)energies_dev})));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));

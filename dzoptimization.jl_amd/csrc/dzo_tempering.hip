@@ -104,7 +104,7 @@ template <typename T> struct McEnd {
 };
 
 // ------------------------------------------------------------------------------ WAVE shape: grid R, block 64
-template <typename T, typename F> __global__ __launch_bounds__(64) void temper_wave_kernel(TemperArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void temper_wave_body(TemperArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
     const int64_t k = blockIdx.x;
     T *rep = a.replicas + (int64_t)3 * N * k;
@@ -148,9 +148,12 @@ template <typename T, typename F> __global__ __launch_bounds__(64) void temper_w
     if (live) { rep[lane] = x; rep[N + lane] = y; rep[2 * N + lane] = z; }
     if (lane == 0) end.store(radius, acc, rej, s);
 }
+template <typename T, typename F> __global__ __launch_bounds__(64) void temper_wave_kernel(TemperArgs<T> a) { temper_wave_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(64) void rad_temper_wave(TemperArgs<T> a) { temper_wave_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid R, block 256
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temper_block_kernel(TemperArgs<T> a) {
+template <typename T, typename F> __device__ __forceinline__ void temper_block_body(TemperArgs<T> a) {
     __shared__ T cx[kTemperMaxN], cy[kTemperMaxN], cz[kTemperMaxN];
     __shared__ double red[2 * kWaves];
     const int tid = threadIdx.x, N = a.N;
@@ -215,6 +218,9 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
     for (int j = tid; j < N; j += kBlock) { rep[j] = cx[j]; rep[N + j] = cy[j]; rep[2 * N + j] = cz[j]; }
     if (tid == 0) end.store(radius, acc, rej, s);
 }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temper_block_kernel(TemperArgs<T> a) { temper_block_body<T, F>(a); }
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_temper_block(TemperArgs<T> a) { temper_block_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ swap (:89-136): grid ceil(R / 2), block 256
 // Block b owns the pair (a, a + 1), a = 2 b + odd, when a + 1 < R, and the record slots a and a + 1 (block 0 also slot 0 when
@@ -222,8 +228,8 @@ template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temp
 extern __shared__ double tempering_smem[];
 
 template <typename T, typename F>
-__global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd, T *__restrict__ replicas, const T *__restrict__ inv_temps,
-                                                      uint64_t *__restrict__ rng, int8_t *__restrict__ rec_swap, T *__restrict__ rec_logp) {
+__device__ __forceinline__ void swap_body(int N, int64_t R, int odd, T *__restrict__ replicas, const T *__restrict__ inv_temps,
+                                          uint64_t *__restrict__ rng, int8_t *__restrict__ rec_swap, T *__restrict__ rec_logp) {
     __shared__ double red[2 * kWaves];
     T *c = reinterpret_cast<T *>(tempering_smem);
     const int tid = threadIdx.x;
@@ -267,6 +273,17 @@ __global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd,
         for (int t = tid; t < n3; t += kBlock) { ra[t] = c[n3 + t]; ra[n3 + t] = c[t]; }
     }
 }
+template <typename T, typename F>
+__global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd, T *__restrict__ replicas, const T *__restrict__ inv_temps,
+                                                      uint64_t *__restrict__ rng, int8_t *__restrict__ rec_swap, T *__restrict__ rec_logp) {
+    swap_body<T, F>(N, R, odd, replicas, inv_temps, rng, rec_swap, rec_logp);
+}
+// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
+template <typename T, typename F>
+__global__ __launch_bounds__(kBlock) void rad_swap(int N, int64_t R, int odd, T *__restrict__ replicas, const T *__restrict__ inv_temps,
+                                                   uint64_t *__restrict__ rng, int8_t *__restrict__ rec_swap, T *__restrict__ rec_logp) {
+    swap_body<T, F>(N, R, odd, replicas, inv_temps, rng, rec_swap, rec_logp);
+}
 
 // ------------------------------------------------------------------------------ analyze (:139-180): grid R, block 256
 // out[5 k ..] = cv, cv_prime, V1, V2, V3
@@ -304,7 +321,7 @@ using namespace dzo;
 
 struct dzo_tempering_s {
     int device = -1;
-    int32_t dtype = DZO_F64;
+    int32_t dtype = DZO_F64, radial = DZO_RADIAL_LENNARD_JONES;
     int N = 0;
     int64_t R = 0;
     void *replicas = nullptr;        // the caller's
@@ -340,7 +357,7 @@ static void tp_free(dzo_tempering_s *h) {
 
 static int32_t tp_alloc(void **p, size_t bytes) { return device_alloc(p, bytes, "the tempering state", false); }
 
-template <typename T> static int32_t tp_temper_t(dzo_tempering_s *h, hipStream_t s, int64_t num_steps, void *energies, int64_t ld) {
+template <typename T, typename F> static int32_t tp_temper_t(dzo_tempering_s *h, hipStream_t s, int64_t num_steps, void *energies, int64_t ld) {
     TemperArgs<T> a;
     a.N = h->N;
     a.num_steps = num_steps;
@@ -359,24 +376,28 @@ template <typename T> static int32_t tp_temper_t(dzo_tempering_s *h, hipStream_t
     a.rec_normals = (T *)h->rec_normals;
     a.rec_uniform = (T *)h->rec_uniform;
     a.rec_code = h->rec_code;
-    if (h->N <= 64) hipLaunchKernelGGL((temper_wave_kernel<T, LJRadial<T>>), dim3((unsigned)h->R), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((temper_block_kernel<T, LJRadial<T>>), dim3((unsigned)h->R), dim3(kBlock), 0, s, a);
+    if (h->N <= 64) DZO_LAUNCH_RADIAL(temper_wave_kernel, rad_temper_wave, (T, F), dim3((unsigned)h->R), dim3(64), 0, s, a);
+    else DZO_LAUNCH_RADIAL(temper_block_kernel, rad_temper_block, (T, F), dim3((unsigned)h->R), dim3(kBlock), 0, s, a);
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
 
 static int32_t tp_temper(dzo_tempering_s *h, hipStream_t s, int64_t num_steps, void *energies, int64_t ld) {
     DZO_TIMED("tempering_temper", s);
-    DZO_DISPATCH(h->dtype, return tp_temper_t<T>(h, s, num_steps, energies, ld));
+    DZO_DISPATCH_RADIAL(h->radial, h->dtype, return (tp_temper_t<T, F>(h, s, num_steps, energies, ld)));
     return DZO_OK;
+}
+
+template <typename T, typename F> static void tp_launch_swap(dzo_tempering_s *h, hipStream_t s, unsigned grid, size_t lds, int32_t odd) {
+    DZO_LAUNCH_RADIAL(swap_kernel, rad_swap, (T, F), dim3(grid), dim3(kBlock), lds, s, h->N, h->R, odd ? 1 : 0, (T *)h->replicas, (const T *)h->inv_temps,
+                      h->rng, h->rec_swap, (T *)h->rec_logp);
 }
 
 static int32_t tp_swap(dzo_tempering_s *h, hipStream_t s, int32_t odd) {
     DZO_TIMED("tempering_swap", s);
     const unsigned grid = (unsigned)((h->R + 1) / 2);
     const size_t lds = (size_t)6 * h->N * dtype_size(h->dtype);
-    DZO_DISPATCH(h->dtype, hipLaunchKernelGGL((swap_kernel<T, LJRadial<T>>), dim3(grid), dim3(kBlock), lds, s, h->N, h->R, odd ? 1 : 0,
-                                              (T *)h->replicas, (const T *)h->inv_temps, h->rng, h->rec_swap, (T *)h->rec_logp));
+    DZO_DISPATCH_RADIAL(h->radial, h->dtype, (tp_launch_swap<T, F>(h, s, grid, lds, odd)));
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
@@ -432,7 +453,7 @@ int32_t dzo_tempering_create(int32_t radial, int64_t n_particles, int64_t n_repl
     Context &c = ctx();
     dzo_tempering_s *h = new (std::nothrow) dzo_tempering_s();
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
-    h->device = c.device; h->dtype = dtype; h->N = (int)n_particles; h->R = n_replicas; h->replicas = replicas_dev;
+    h->device = c.device; h->dtype = dtype; h->radial = radial; h->N = (int)n_particles; h->R = n_replicas; h->replicas = replicas_dev;
     h->constraining_radius = constraining_radius;
     h->fac = dtype == DZO_F64 ? mc_fac<double>() : mc_fac<float>();
     const size_t es = dtype_size(dtype), R = (size_t)n_replicas;

@@ -27,6 +27,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        update_inverse_hessian!, reset_inverse_hessian!, synchronize,
        norm2, inv_norm, negate!, scale!, HipBackend, install_state!, ShardComm, all_done, read_field,
        lj_energy, lj_first_derivative, lj_second_derivative, PairwiseLennardJones,
+       DZO_RADIAL_LENNARD_JONES, DZO_RADIAL_MORSE_RHO6, DZO_RADIAL_MORSE_RHO14,
        accelerated_pairwise_radial_energy, accelerated_pairwise_radial_gradient!, accelerated_pairwise_radial_hvp!,
        pairwise_radial_energy_delta,
        ParallelTempering, parallel_temper!, parallel_swap!, run_batches!, analyze, perturbation_radii,
@@ -252,38 +253,42 @@ end
     return T(48) * muladd(T(7) / T(2), _square(inv_r8), -inv_r10)
 end
 const DZO_RADIAL_LENNARD_JONES = Cint(0)
+# E(r) = t^2 - 2 t, t = exp(rho (1 - r)): pair minimum at r = 1, depth 1; rho is compile-time in the library (include/dzo.h).
+# Every function below that reaches a radial takes `radial=` (the Lennard-Jones selector by default).
+const DZO_RADIAL_MORSE_RHO6 = Cint(2)
+const DZO_RADIAL_MORSE_RHO14 = Cint(3)
 
 """`accelerated_pairwise_radial_energy(lj_energy, x, y, z)` on device vectors (src/ExampleFunctions.jl:152-173)."""
-function accelerated_pairwise_radial_energy(::typeof(lj_energy), x::HipVector{T}, y::HipVector{T}, z::HipVector{T}) where {T}
+function accelerated_pairwise_radial_energy(::typeof(lj_energy), x::HipVector{T}, y::HipVector{T}, z::HipVector{T}; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     e = Ref{Cdouble}(0)
     check(ccall((:dzo_pairwise_energy, libdzo), Cint, (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cdouble}),
-                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, e))
+                Cint(radial), x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, e))
     return T(e[])
 end
 """`accelerated_pairwise_radial_gradient!(gx, gy, gz, lj_first_derivative, x, y, z)` (src/ExampleFunctions.jl:265-294)."""
 function accelerated_pairwise_radial_gradient!(gx::HipVector{T}, gy::HipVector{T}, gz::HipVector{T}, ::typeof(lj_first_derivative),
-                                               x::HipVector{T}, y::HipVector{T}, z::HipVector{T}) where {T}
+                                               x::HipVector{T}, y::HipVector{T}, z::HipVector{T}; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     check(ccall((:dzo_pairwise_gradient, libdzo), Cint,
                 (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), gx.ptr, gy.ptr, gz.ptr, x.ptr, y.ptr, z.ptr))
+                Cint(radial), x.len, dtype_code(T), gx.ptr, gy.ptr, gz.ptr, x.ptr, y.ptr, z.ptr))
     return nothing
 end
 """`accelerated_pairwise_radial_hvp!(px, py, pz, lj_first_derivative, lj_second_derivative, x, y, z, u, v, w)` (:427-468)."""
 function accelerated_pairwise_radial_hvp!(px::HipVector{T}, py::HipVector{T}, pz::HipVector{T}, ::typeof(lj_first_derivative),
                                           ::typeof(lj_second_derivative), x::HipVector{T}, y::HipVector{T}, z::HipVector{T},
-                                          u::HipVector{T}, v::HipVector{T}, w::HipVector{T}) where {T}
+                                          u::HipVector{T}, v::HipVector{T}, w::HipVector{T}; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     check(ccall((:dzo_pairwise_hvp, libdzo), Cint,
                 (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), px.ptr, py.ptr, pz.ptr, x.ptr, y.ptr, z.ptr, u.ptr, v.ptr, w.ptr))
+                Cint(radial), x.len, dtype_code(T), px.ptr, py.ptr, pz.ptr, x.ptr, y.ptr, z.ptr, u.ptr, v.ptr, w.ptr))
     return nothing
 end
 """`pairwise_radial_energy_delta(lj_energy, x, y, z, i, x_new, y_new, z_new)` (:477-534); `i` is 1-based like the reference's."""
 function pairwise_radial_energy_delta(::typeof(lj_energy), x::HipVector{T}, y::HipVector{T}, z::HipVector{T}, i::Integer,
-                                      x_new::Real, y_new::Real, z_new::Real) where {T}
+                                      x_new::Real, y_new::Real, z_new::Real; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     d = Ref{Cdouble}(0)
     check(ccall((:dzo_pairwise_energy_delta, libdzo), Cint,
                 (Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cdouble, Cdouble, Cdouble, Ref{Cdouble}),
-                DZO_RADIAL_LENNARD_JONES, x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, i - 1, Float64(x_new), Float64(y_new), Float64(z_new), d))
+                Cint(radial), x.len, dtype_code(T), x.ptr, y.ptr, z.ptr, i - 1, Float64(x_new), Float64(y_new), Float64(z_new), d))
     return T(d[])
 end
 
@@ -306,7 +311,7 @@ end
 """`ParallelTempering(lj_energy, replicas, n_particles, inverse_temperatures, perturbation_radii, constraining_radius; seed)`:
 the arguments of `parallel_temper!` (scripts/MonteCarlo.jl:8-15)."""
 function ParallelTempering(::typeof(lj_energy), replicas::HipVector{T}, n_particles::Integer, inverse_temperatures::AbstractVector,
-                           perturbation_radii::AbstractVector, constraining_radius::Real; seed::Integer=0) where {T}
+                           perturbation_radii::AbstractVector, constraining_radius::Real; seed::Integer=0, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     n_replicas = length(inverse_temperatures)
     @assert length(perturbation_radii) == n_replicas                       # :33
@@ -315,7 +320,7 @@ function ParallelTempering(::typeof(lj_energy), replicas::HipVector{T}, n_partic
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:dzo_tempering_create, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, UInt64, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, n_replicas, dtype_code(T), replicas.ptr, beta, radii, Float64(constraining_radius), UInt64(seed), h))
+                Cint(radial), n_particles, n_replicas, dtype_code(T), replicas.ptr, beta, radii, Float64(constraining_radius), UInt64(seed), h))
     pt = ParallelTempering{T}(h[], replicas, n_particles, n_replicas)
     finalizer(pt) do w
         w.handle != C_NULL && ccall((:dzo_tempering_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
@@ -376,14 +381,14 @@ end
 
 """`BatchedLBFGSOptimizer(lj_energy, points, n_particles, initial_step_length, history_length)` (:400-427 per instance)."""
 function BatchedLBFGSOptimizer(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, initial_step_length::Real,
-                               history_length::Integer) where {T}
+                               history_length::Integer; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     batch = div(length(points), 3 * n_particles)
     @assert length(points) == 3 * n_particles * batch
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:dzo_lbfgs_batch_create, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cdouble, Cint, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), history_length, h))
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), history_length, h))
     opt = BatchedLBFGSOptimizer{T}(h[], points, n_particles, batch, history_length)
     finalizer(opt) do w
         w.handle != C_NULL && ccall((:dzo_lbfgs_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
@@ -444,10 +449,10 @@ end
 
 """`pairwise_batch_energy_gradient!(energies, gradients, points, n_particles)`: energy and gradient of every instance by the
 optimizer's own device routine (the objective_function / gradient_function! of :416-421); blocks."""
-function pairwise_batch_energy_gradient!(energies::HipVector{T}, gradients::HipVector{T}, points::HipVector{T}, n_particles::Integer) where {T}
+function pairwise_batch_energy_gradient!(energies::HipVector{T}, gradients::HipVector{T}, points::HipVector{T}, n_particles::Integer; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(points), 3 * n_particles)
     check(ccall((:dzo_pairwise_batch_energy_gradient, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, energies.ptr, gradients.ptr))
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, energies.ptr, gradients.ptr))
     return energies
 end
 
@@ -456,21 +461,21 @@ accelerated_pairwise_radial_hvp! (src/ExampleFunctions.jl:367-468) of every inst
 `HipVector{Float64}` of 2 * batch elements for u.Hu and u.u of each instance.  `shared_point`: `points` holds one point to which
 every direction is applied.  Blocks."""
 function pairwise_batch_hvp!(products::HipVector{T}, points::HipVector{T}, directions::HipVector{T}, n_particles::Integer;
-                             curvatures::Union{Nothing,HipVector{Float64}}=nothing, shared_point::Bool=false) where {T}
+                             curvatures::Union{Nothing,HipVector{Float64}}=nothing, shared_point::Bool=false, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(directions), 3 * n_particles)
     check(ccall((:dzo_pairwise_batch_hvp, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, shared_point ? 0 : 3 * n_particles,
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, shared_point ? 0 : 3 * n_particles,
                 directions.ptr, products.ptr, curvatures === nothing ? C_NULL : curvatures.ptr))
     return products
 end
 
 """`pairwise_batch_hessian!(hessians, points, n_particles)`: the dense 3N x 3N Hessian of every instance, column-major per
 instance (`reshape(Array(hessians), 3N, 3N, batch)`), from one launch.  Blocks."""
-function pairwise_batch_hessian!(hessians::HipVector{T}, points::HipVector{T}, n_particles::Integer) where {T}
+function pairwise_batch_hessian!(hessians::HipVector{T}, points::HipVector{T}, n_particles::Integer; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(points), 3 * n_particles)
     check(ccall((:dzo_pairwise_batch_hessian, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, hessians.ptr))
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, hessians.ptr))
     return hessians
 end
 
@@ -521,7 +526,7 @@ out.  `res_tol === nothing`: 4.3e-15 for Float64, 7.0e-7 for Float32 (DESIGN.md)
 or `nothing` to draw them in the kernel from `seed`.  Returns `(eigenvalues::Vector{T}, vectors::HipVector{T}, residuals::Vector{Float64},
 status, cycles, products)`, the last three `Vector{Int32}`.  Blocks."""
 function lowest_modes(points::HipVector{T}, n_particles::Integer; project_rigid::Bool=true, krylov::Integer=32, max_cycles::Integer=40,
-                      res_tol::Union{Nothing,Real}=nothing, start::Union{Nothing,HipVector{T}}=nothing, seed::Integer=0) where {T}
+                      res_tol::Union{Nothing,Real}=nothing, start::Union{Nothing,HipVector{T}}=nothing, seed::Integer=0, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(points), 3 * n_particles)
     tol = res_tol === nothing ? (T === Float64 ? 4.3e-15 : 7.0e-7) : Float64(res_tol)
     eigenvalues = HipVector{T}(undef, batch)
@@ -530,7 +535,7 @@ function lowest_modes(points::HipVector{T}, n_particles::Integer; project_rigid:
     info = HipVector{Float32}(undef, 3 * batch)              # four bytes per record: read back as Int32
     check(ccall((:dzo_pairwise_batch_lowest_mode, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cint, Cint, Cint, Cdouble, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, project_rigid ? 1 : 0, krylov, max_cycles, tol,
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, project_rigid ? 1 : 0, krylov, max_cycles, tol,
                 UInt64(seed), start === nothing ? C_NULL : start.ptr, eigenvalues.ptr, vectors.ptr, residuals.ptr, info.ptr))
     records = reshape(collect(reinterpret(Int32, Array(info))), 3, batch)
     return Array(eigenvalues), vectors, Array(residuals), records[1, :], records[2, :], records[3, :]
@@ -561,7 +566,7 @@ end
 initial_step_length=0.01, history_length=10, quench_steps=400, seed=0)`.  Does not wait for the quench of `points`."""
 function BasinHopping(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, inverse_temperatures::AbstractVector,
                       perturbation_radii::AbstractVector, constraining_radius::Real; initial_step_length::Real=0.01,
-                      history_length::Integer=10, quench_steps::Integer=400, seed::Integer=0) where {T}
+                      history_length::Integer=10, quench_steps::Integer=400, seed::Integer=0, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     batch = length(inverse_temperatures)
     @assert length(perturbation_radii) == batch
@@ -570,7 +575,7 @@ function BasinHopping(::typeof(lj_energy), points::HipVector{T}, n_particles::In
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:dzo_basin_hopping_create, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cint, Cint, UInt64, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, beta, radii, Float64(constraining_radius),
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, beta, radii, Float64(constraining_radius),
                 Float64(initial_step_length), history_length, quench_steps, UInt64(seed), h))
     bh = BasinHopping{T}(h[], points, n_particles, batch, 0)
     finalizer(bh) do w
@@ -656,14 +661,14 @@ end
 
 """`ModeFollowing(lj_energy, points, n_particles; target_index=0, max_step=0.2, zero_tol=1e-4, grad_tol=1e-10)`."""
 function ModeFollowing(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer; target_index::Integer=0, max_step::Real=0.2,
-                       zero_tol::Real=1e-4, grad_tol::Real=1e-10) where {T}
+                       zero_tol::Real=1e-4, grad_tol::Real=1e-10, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     batch = div(length(points), 3 * n_particles)
     @assert length(points) == 3 * n_particles * batch
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:dzo_modefollow_batch_create, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, target_index, Float64(max_step), Float64(zero_tol),
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, target_index, Float64(max_step), Float64(zero_tol),
                 Float64(grad_tol), h))
     mf = ModeFollowing{T}(h[], points, n_particles, batch)
     finalizer(mf) do w
@@ -728,13 +733,13 @@ supplies (`dzo_modefollow_batch_apply`); `points` is moved.  `target_index=1` ne
 instance as a `Vector{Int32}`.  Blocks."""
 function modefollow_apply!(points::HipVector{T}, eigenvalues::HipVector{T}, eigenvectors::HipVector{T}, n_particles::Integer;
                            target_index::Integer=0, start_mode::Integer=0, max_step::Real=0.2, zero_tol::Real=1e-4, grad_tol::Real=0.0,
-                           follow::Union{Nothing,HipVector{T}}=nothing, follow_set::Union{Nothing,HipVector{Float32}}=nothing) where {T}
+                           follow::Union{Nothing,HipVector{T}}=nothing, follow_set::Union{Nothing,HipVector{Float32}}=nothing, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(points), 3 * n_particles)
     status = HipVector{Float32}(undef, batch)               # four bytes per instance: read back as Int32
     check(ccall((:dzo_modefollow_batch_apply, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Cdouble,
                  Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, eigenvalues.ptr, eigenvectors.ptr,
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, eigenvalues.ptr, eigenvectors.ptr,
                 follow === nothing ? C_NULL : follow.ptr, follow_set === nothing ? C_NULL : follow_set.ptr, target_index, start_mode,
                 Float64(max_step), Float64(zero_tol), Float64(grad_tol), C_NULL, C_NULL, C_NULL, C_NULL, status.ptr, C_NULL, C_NULL, C_NULL,
                 C_NULL))
@@ -805,7 +810,7 @@ tangent_cap=0.05, tangent_first=0.01, krylov=8, mode_cycles=1, mode_tol=1e-3, ze
 function HybridModeFollowing(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer; directions::Union{Nothing,HipVector{T}}=nothing,
                              max_step::Real=0.1, tangent_steps::Integer=10, tangent_steps_convex::Integer=2, tangent_cap::Real=0.05,
                              tangent_first::Real=0.01, krylov::Integer=8, mode_cycles::Integer=1, mode_tol::Real=1e-3, zero_tol::Real=1e-4,
-                             grad_tol::Real=1e-10, seed::Integer=0) where {T}
+                             grad_tol::Real=1e-10, seed::Integer=0, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     batch = div(length(points), 3 * n_particles)
     @assert length(points) == 3 * n_particles * batch
@@ -813,7 +818,7 @@ function HybridModeFollowing(::typeof(lj_energy), points::HipVector{T}, n_partic
     check(ccall((:dzo_hybridef_batch_create, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Cint, Cdouble, Cdouble, Cint, Cint, Cdouble, Cdouble, Cdouble,
                  UInt64, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, directions === nothing ? C_NULL : directions.ptr,
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, directions === nothing ? C_NULL : directions.ptr,
                 Float64(max_step), tangent_steps, tangent_steps_convex, Float64(tangent_cap), Float64(tangent_first), krylov, mode_cycles,
                 Float64(mode_tol), Float64(zero_tol), Float64(grad_tol), UInt64(seed), h))
     hf = HybridModeFollowing{T}(h[], points, n_particles, batch)
@@ -873,13 +878,13 @@ end
 moved.  Returns the status of every instance as a `Vector{Int32}`.  Blocks."""
 function hybridef_apply!(points::HipVector{T}, eigenvalues::HipVector{T}, modes::HipVector{T}, n_particles::Integer; max_step::Real=0.1,
                          tangent_steps::Integer=10, tangent_steps_convex::Integer=2, tangent_cap::Real=0.05, tangent_first::Real=0.01,
-                         zero_tol::Real=1e-4, grad_tol::Real=0.0) where {T}
+                         zero_tol::Real=1e-4, grad_tol::Real=0.0, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(points), 3 * n_particles)
     status = HipVector{Float32}(undef, batch)               # four bytes per instance: read back as Int32
     check(ccall((:dzo_hybridef_batch_apply, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble,
                  Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, eigenvalues.ptr, modes.ptr, Float64(max_step),
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, eigenvalues.ptr, modes.ptr, Float64(max_step),
                 tangent_steps, tangent_steps_convex, Float64(tangent_cap), Float64(tangent_first), Float64(zero_tol), Float64(grad_tol),
                 C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, status.ptr, C_NULL))
     return collect(reinterpret(Int32, Array(status)))
@@ -931,13 +936,13 @@ end
 fingerprints"): per-particle energies sorted ascending, then squared distances from the centroid sorted ascending.  Unchanged
 by rotation, translation, reflection and relabelling beyond rounding; blind to mirror images.  Returns
 `(fingerprints::HipVector{T} (2N, batch), energies::Vector{T})`.  Blocks."""
-function structure_fingerprints(points::HipVector{T}, n_particles::Integer) where {T}
+function structure_fingerprints(points::HipVector{T}, n_particles::Integer; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(points), 3 * n_particles)
     @assert length(points) == 3 * n_particles * batch && batch >= 1
     fingerprints = HipVector{T}(undef, 2 * n_particles * batch)
     energies = HipVector{T}(undef, batch)
     check(ccall((:dzo_structure_batch_fingerprint, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, fingerprints.ptr, energies.ptr))
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, fingerprints.ptr, energies.ptr))
     return fingerprints, Array(energies)
 end
 
@@ -1059,14 +1064,14 @@ end
 """`ElasticBand(lj_energy, band, n_particles, n_images; force_tol, spring=1.0, dt=0.02, max_move=0.1, climb=true, climb_after=50)`.
 `force_tol` has no default: what a band can reach depends on the element type."""
 function ElasticBand(::typeof(lj_energy), band::HipVector{T}, n_particles::Integer, n_images::Integer; force_tol::Real, spring::Real=1.0,
-                     dt::Real=0.02, max_move::Real=0.1, climb::Bool=true, climb_after::Integer=50) where {T}
+                     dt::Real=0.02, max_move::Real=0.1, climb::Bool=true, climb_after::Integer=50, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     batch = div(length(band), 3 * n_particles * n_images)
     @assert length(band) == 3 * n_particles * n_images * batch
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:dzo_neb_batch_create, libdzo), Cint,
                 (Cint, Int64, Cint, Int64, Cint, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Int64, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, n_images, batch, dtype_code(T), band.ptr, Float64(spring), Float64(dt), Float64(max_move),
+                Cint(radial), n_particles, n_images, batch, dtype_code(T), band.ptr, Float64(spring), Float64(dt), Float64(max_move),
                 Float64(force_tol), climb ? 1 : 0, climb_after, h))
     eb = ElasticBand{T}(h[], band, n_particles, n_images, batch)
     finalizer(eb) do w
@@ -1116,7 +1121,7 @@ end
 given (`dzo_neb_batch_apply`), both moved.  Returns the status of every band as a `Vector{Int32}`; the other records of the
 entry point (energies, gradients, forces, tangents, ...) are not asked for here: an `ElasticBand` stepped once has them.  Blocks."""
 function neb_apply!(band::HipVector{T}, velocities::HipVector{T}, n_particles::Integer, n_images::Integer; spring::Real=1.0, dt::Real=0.02,
-                    max_move::Real=0.1, force_tol::Real=0.0, climb::Bool=true) where {T}
+                    max_move::Real=0.1, force_tol::Real=0.0, climb::Bool=true, radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     batch = div(length(band), 3 * n_particles * n_images)
     @assert length(band) == 3 * n_particles * n_images * batch && length(velocities) == length(band)
     # HipVector holds the two floating-point types only: four bytes per band, written as int32 by the kernel and read back as such
@@ -1124,7 +1129,7 @@ function neb_apply!(band::HipVector{T}, velocities::HipVector{T}, n_particles::I
     check(ccall((:dzo_neb_batch_apply, libdzo), Cint,
                 (Cint, Int64, Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cdouble, Cint,
                  Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, n_images, batch, dtype_code(T), band.ptr, velocities.ptr, Float64(spring), Float64(dt),
+                Cint(radial), n_particles, n_images, batch, dtype_code(T), band.ptr, velocities.ptr, Float64(spring), Float64(dt),
                 Float64(max_move), Float64(force_tol), climb ? 1 : 0,
                 C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, status.ptr))
     return collect(reinterpret(Int32, Array(status)))
@@ -1259,14 +1264,14 @@ mutable struct BatchedAdGDOptimizer{T}
 end
 
 """`BatchedAdGDOptimizer(lj_energy, points, n_particles, initial_step_length)` (:245-271 per instance)."""
-function BatchedAdGDOptimizer(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, initial_step_length::Real) where {T}
+function BatchedAdGDOptimizer(::typeof(lj_energy), points::HipVector{T}, n_particles::Integer, initial_step_length::Real; radial::Integer=DZO_RADIAL_LENNARD_JONES) where {T}
     ensure_init()
     batch = div(length(points), 3 * n_particles)
     @assert length(points) == 3 * n_particles * batch
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:dzo_adgd_batch_create, libdzo), Cint,
                 (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cdouble, Ref{Ptr{Cvoid}}),
-                DZO_RADIAL_LENNARD_JONES, n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), h))
+                Cint(radial), n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), h))
     opt = BatchedAdGDOptimizer{T}(h[], points, n_particles, batch)
     finalizer(opt) do w
         w.handle != C_NULL && ccall((:dzo_adgd_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)

@@ -63,6 +63,11 @@ extern "C" {
 
 /* radial functions of the pairwise objective (the reference is generic over energy_function::F) */
 #define DZO_RADIAL_LENNARD_JONES 0      /* lj_energy / lj_first_derivative / lj_second_derivative, src/ExampleFunctions.jl:16-72 */
+/* The Morse pair term E(r) = t^2 - 2 t with t = exp(rho (1 - r)), r = sqrt(r2), in reduced units: the pair minimum is at r = 1
+ * and its depth is 1.  first = dE/d(r2) = -rho t (t - 1) / r, second = d2E/d(r2)2 = rho t (rho r (2t - 1) + (t - 1)) / (2 r2 r).
+ * rho is a compile-time constant of the kernels: one selector per range, every unit that takes `radial` takes these. */
+#define DZO_RADIAL_MORSE_RHO6 2         /* (1 is not a selector) */
+#define DZO_RADIAL_MORSE_RHO14 3
 
 /* how compute_lbfgs_step_direction! is executed on the device */
 #define DZO_TWOLOOP_CHAIN 0 /* 2k+1 fused axpy+dot links in the reference's op order */
@@ -219,7 +224,7 @@ int32_t dzo_problem_constraint_cb(void *problem, void *x_dev);
 /* ---------------------------------------------------------------------------------------
  * pairwise radial N-body functions (src/ExampleFunctions.jl): the reference's own GPU kernels.
  * SoA coordinates x, y, z of n_particles particles, e = the radial function of r2 = |r_i - r_j|^2 selected by `radial`
- * (DZO_RADIAL_LENNARD_JONES).  Per pair the arithmetic is the reference's, operation by operation; the self term is removed
+ * (DZO_RADIAL_LENNARD_JONES, DZO_RADIAL_MORSE_RHO6, DZO_RADIAL_MORSE_RHO14).  Per pair the arithmetic is the reference's, operation by operation; the self term is removed
  * by a select.  Sums over j run in a fixed order (no floating-point atomics): the same input gives the same bits on every
  * call.  Blocking.  The pointers need no alignment beyond the element's.  Unknown radial, null pointers, i outside
  * 0 .. N-1: DZO_ERR_INVALID; a host pointer where the reference asserts get_backend equality: DZO_ERR_ASSERT.
