@@ -40,7 +40,7 @@ LINE_SEARCH_BACKTRACKING, LINE_SEARCH_WOLFE = 0, 1
 STEP_NULL, STEP_GRADIENT_DESCENT, STEP_BFGS = 0, 1, 2
 
 _ERR = {1: "invalid argument", 2: "HIP runtime error", 3: "reference @assert", 4: "out of memory",
-        5: "unsupported", 6: "bad call sequence"}
+        5: "unsupported", 6: "bad call sequence", 7: "more candidates than the capacity"}
 
 
 class DzoError(RuntimeError):
@@ -227,6 +227,7 @@ ABI = {
     "dzo_neb_batch_get_ptr": [_vp, _i32, _P(_vp)], "dzo_neb_batch_read": [_vp, _i32, _vp],
     "dzo_align_batch_assign": [_i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "dzo_align_batch_pairs": [_i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dzo_pathway_batch_candidates": [_i64, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _P(_i64)],
     "dzo_structure_batch_fingerprint": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
     "dzo_structure_batch_classify": [_i64, _i64, _i32, _vp, _dbl, _vp, _P(_i32)],
     "dzo_malloc": [_P(_vp), _i64], "dzo_free": [_vp], "dzo_memcpy_h2d": [_vp, _vp, _i64],
@@ -1350,7 +1351,7 @@ def quench_to_rest(points, n_particles, history_length=10, initial_step_length=0
 
 
 def connect_saddles(saddles, modes, n_particles, displacement, tol, known_minima=None, history_length=10, initial_step_length=0.01,
-                    steps_per_launch=50, max_steps=2000, radial=RADIAL_LENNARD_JONES):
+                    steps_per_launch=50, max_steps=2000, radial=RADIAL_LENNARD_JONES, descent_steps=0):
     """Which two minima every transition state joins.  ``saddles`` and ``modes`` are DeviceArrays of ``3 * n_particles * batch``
     elements (for instance the points and ``HYBRIDEF_MODES`` of ``find_saddles_hybrid``); neither is changed.  The 2 batch points
     ``saddle +- displacement * mode`` are formed on the device, quenched together by ``quench_to_rest`` (``BatchedLBFGS`` until
@@ -1364,7 +1365,13 @@ def connect_saddles(saddles, modes, n_particles, displacement, tol, known_minima
     README.md, profiles/structure_bench.json): in fp64 copies of one minimum at rest are at most 9.2e-7 apart and two minima of
     different energy at least 2.0e-2, so anything from 1e-5 to 1e-3 serves; in fp32 the two figures are NOT a factor 100 apart
     (instances that energy and spectrum call one minimum are up to 1.2e-1 apart, minima of different energy as close as 8.1e-3),
-    so no ``tol`` identifies fp32 minima of that size reliably: bring them to rest in fp64 first.  Of the displacements 1e-3 .. 1e-1, 3e-2 and 1e-1 gave every saddle two different ends in fp64."""
+    so no ``tol`` identifies fp32 minima of that size reliably: bring them to rest in fp64 first.  Of the displacements 1e-3 .. 1e-1, 3e-2 and 1e-1 gave every saddle two different ends in fp64.
+
+    ``descent_steps`` > 0: before the L-BFGS quench every end first takes up to that many steps of ``BatchedAdGD`` (a plain
+    gradient method with a step from the local curvature).  The minima a saddle joins are those its two steepest-descent paths
+    end in; L-BFGS does not follow them, and from the shoulder of a saddle its long early steps can cross a low neighbouring
+    barrier (seen on the 13-atom cluster: an end that steepest descent takes to the minimum at -40.3489 quenched into the
+    icosahedron).  0, the default, is the quench alone."""
     n, batch = _batch_of(saddles, n_particles, "saddles", least=1)
     n3 = 3 * n
     assert modes.size == saddles.size and modes.dtype == saddles.dtype, "modes must be laid out like saddles"
@@ -1381,6 +1388,16 @@ def connect_saddles(saddles, modes, n_particles, displacement, tol, known_minima
         end = ends.view(side * batch * n3, (batch * n3,))
         _check(lib().dzo_memcpy_d2d(end.ptr, saddles.ptr, saddles.nbytes))
         axpy_(sign * float(displacement), modes, end)
+    if descent_steps > 0:
+        descent = BatchedAdGD(ends, n, initial_step_length, radial)
+        try:
+            taken, done = 0, False
+            while not done and taken < int(descent_steps):
+                k = min(int(steps_per_launch), int(descent_steps) - taken)
+                done = descent.step(k)
+                taken += k
+        finally:
+            descent.close()
     stuck = quench_to_rest(ends, n, history_length, initial_step_length, steps_per_launch, max_steps, radial)
     fp, energies = structure_fingerprints(both, n, radial)
     for k in np.flatnonzero(~stuck):                         # an end that is still moving names no minimum
@@ -1633,6 +1650,399 @@ def align_pairs(a, b, n_particles, trials=ALIGN_TRIAL_IDENTITY | ALIGN_TRIAL_PRI
     return Alignment(aligned=aligned, permutations=perm.to_host(), rotations=rot.to_host(), distances=dist.to_host(),
                      best_trials=best.to_host(), cycles=cycles.to_host(), status=status.to_host(),
                      trial_distances=per_trial.to_host() if want_trials else None)
+
+
+# ------------------------------------------------------------------------------ multi-step pathways: candidates, graph, connect cycle
+PATHWAY_MAX_PARTICLES = 1024
+PATHWAY_MAX_IMAGES = 32
+PATHWAY_MAX_BATCH = 1048576
+PATHWAY_OVERFLOW = 7
+
+
+class BandCandidates:
+    """What ``band_candidates`` returns.  ``count``; ``points`` and ``tangents`` (DeviceArrays ``(count, 3N)``: the candidate
+    images and the band's unit tangents there); ``energies`` (host ``(count,)``); ``band_index`` and ``image_index`` (host
+    int32 ``(count,)``); ``offsets`` (host int32 ``(batch + 1,)``: the candidates of band b are
+    ``offsets[b] .. offsets[b + 1] - 1``); ``band_energies`` (host ``(batch, M)``: the profiles the candidates were taken from)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def band_candidates(band, n_particles, n_images, energies=None, radial=RADIAL_LENNARD_JONES):
+    """``dzo_pathway_batch_candidates`` (include/dzo.h states the rule): the transition-state candidates of every band of
+    ``band`` (a DeviceArray of ``3 * n_particles * n_images * batch`` elements, the layout of ``ElasticBand``; not changed).
+    Interior image m is a candidate iff ``E[m] > E[m - 1]`` and ``E[m] >= E[m + 1]``; a band need not have converged, or be
+    ACTIVE, to have some.  ``energies``: a DeviceArray ``(batch, n_images)`` of the band's element type (for instance an
+    ``ElasticBand``'s record); None evaluates the band as it stands as ``n_images * batch`` points with
+    ``pairwise_batch_energy_gradient``'s routine, and only that path takes ``radial``.  Returns a ``BandCandidates``,
+    compacted band-major with the image index ascending inside a band; a tangent is bit for bit the one ``neb_apply`` records
+    for that image of that band."""
+    n, m, batch = _bands_of(band, n_particles, n_images)
+    t = band.dtype
+    if energies is None:
+        energies = DeviceArray((batch, m), t)
+        _check(lib().dzo_pairwise_batch_energy_gradient(radial, n, batch * m, _dt(t), band.ptr, energies.ptr, None))
+    assert energies.size == batch * m and energies.dtype == t, "energies must hold n_images * batch elements of the band's type"
+    capacity = batch * ((m - 1) // 2)                        # the most the bands can hold
+    points, tangents = DeviceArray((capacity, 3 * n), t), DeviceArray((capacity, 3 * n), t)
+    e = DeviceArray((capacity,), t)
+    bi, ii = DeviceArray((capacity,), np.int32), DeviceArray((capacity,), np.int32)
+    offsets = DeviceArray((batch + 1,), np.int32)
+    count = C.c_int64(0)
+    _check(lib().dzo_pathway_batch_candidates(n, m, batch, _dt(t), band.ptr, energies.ptr, capacity, points.ptr, tangents.ptr, e.ptr,
+                                              bi.ptr, ii.ptr, offsets.ptr, C.byref(count)))
+    k = int(count.value)
+    return BandCandidates(count=k, points=points.view(0, (k, 3 * n)), tangents=tangents.view(0, (k, 3 * n)),
+                          energies=e.to_host()[:k], band_index=bi.to_host()[:k], image_index=ii.to_host()[:k],
+                          offsets=offsets.to_host(), band_energies=energies.to_host().reshape(batch, m), _owners=(points, tangents))
+
+
+class PathwayGraph:
+    """The database side of the connect cycle (Carr, Trygubenko & Wales 2005), on the host: minima and saddles by index and
+    energy, edges ``(minimum, saddle, minimum)``, a cache of pair distances and a count of the bands tried per pair.  Holds no
+    coordinates and needs no device.  ``max_attempts``: after that many bands between one pair of minima the pair is not
+    proposed again."""
+
+    def __init__(self, max_attempts=2):
+        self.max_attempts = int(max_attempts)
+        self.minimum_energies, self.saddle_energies, self.edges = [], [], []
+        # (n_minima, n_minima) tables, grown by doubling: the cached distances (inf: none), the bands tried, "a saddle joins them"
+        self._d, self._tries, self._joined = np.full((0, 0), np.inf), np.zeros((0, 0), np.int64), np.zeros((0, 0), bool)
+        self._weights = None                                 # the table next_attempts searches, until the next change
+
+    n_minima = property(lambda self: len(self.minimum_energies))
+    n_saddles = property(lambda self: len(self.saddle_energies))
+
+    @staticmethod
+    def _key(i, j):
+        return (int(i), int(j)) if i <= j else (int(j), int(i))
+
+    def add_minimum(self, energy):
+        """Returns the index of the new minimum."""
+        self.minimum_energies.append(float(energy))
+        k, room = len(self.minimum_energies), len(self._d)
+        if k > room:
+            grown = max(2 * room, 16)
+            for name, fill in (("_d", np.inf), ("_tries", 0), ("_joined", False)):
+                old = getattr(self, name)
+                new = np.full((grown, grown), fill, dtype=old.dtype)
+                new[:room, :room] = old
+                setattr(self, name, new)
+        self._d[k - 1, k - 1] = 0.0
+        self._weights = None
+        return k - 1
+
+    def add_saddle(self, energy, i, j):
+        """A saddle of ``energy`` that joins minima i and j (i != j).  Returns its index."""
+        assert 0 <= i < self.n_minima and 0 <= j < self.n_minima and i != j, (i, j)
+        self.saddle_energies.append(float(energy))
+        self.edges.append((int(i), len(self.saddle_energies) - 1, int(j)))
+        self._joined[i, j] = self._joined[j, i] = True
+        self._weights = None
+        return len(self.saddle_energies) - 1
+
+    def set_distance(self, i, j, d):
+        """Caches the distance of minima i and j; arrays set many pairs at once."""
+        self._d[i, j] = self._d[j, i] = d
+        self._weights = None
+
+    def distance(self, i, j):
+        """The cached distance of minima i and j; inf where none was set."""
+        return float(self._d[i, j])
+
+    def note_attempt(self, i, j):
+        self._tries[i, j] += 1
+        if i != j:
+            self._tries[j, i] += 1
+        self._weights = None
+
+    def attempts(self, i, j):
+        return int(self._tries[i, j])
+
+    def _neighbours(self):
+        out = [[] for _ in range(self.n_minima)]
+        for i, s, j in self.edges:
+            out[i].append((j, s))
+            out[j].append((i, s))
+        return out
+
+    def connected(self, i, j):
+        """Whether a chain of saddles joins minima i and j."""
+        component = self.components()
+        return bool(component[i] == component[j])
+
+    def components(self):
+        """The label of every minimum's connected component (the lowest index in it), as an int array."""
+        n = self.n_minima
+        label = np.arange(n)
+        for i, _, j in self.edges:                           # union by the lower root, paths halved on the way
+            while label[i] != i:
+                label[i] = label[label[i]]
+                i = label[i]
+            while label[j] != j:
+                label[j] = label[label[j]]
+                j = label[j]
+            label[max(i, j)] = min(i, j)
+        for k in range(n):
+            label[k] = label[label[k]]                       # roots have lower indices: one ascending pass flattens
+        return label
+
+    def best_path(self, i, j):
+        """The path from i to j whose highest saddle is lowest, among those the one with the fewest steps:
+        ``[i, saddle, minimum, ..., saddle, j]`` (``[i]`` for i == j), or None when nothing joins them."""
+        import heapq
+        i, j = int(i), int(j)
+        nb = self._neighbours()
+        # the minimax value: the lowest "highest saddle" of any way from i to j
+        best, heap = {i: -float("inf")}, [(-float("inf"), i)]
+        while heap:
+            top, u = heapq.heappop(heap)
+            if top != best[u]:
+                continue
+            if u == j:
+                break
+            for v, s in nb[u]:
+                cand = max(top, self.saddle_energies[s])
+                if v not in best or cand < best[v]:
+                    best[v] = cand
+                    heapq.heappush(heap, (cand, v))
+        if j not in best:
+            return None
+        # ... and the fewest steps over the saddles at or below it, breadth first; of several saddles between two minima the lowest
+        limit, back, front = best[j], {i: None}, [i]
+        while front and j not in back:
+            reached = []
+            for u in front:
+                for v, s in sorted(nb[u], key=lambda e: (self.saddle_energies[e[1]], e[1])):
+                    if v not in back and self.saddle_energies[s] <= limit:
+                        back[v] = (u, s)
+                        reached.append(v)
+            front = reached
+        path, u = [j], j
+        while u != i:
+            u, s = back[u]
+            path += [s, u]
+        return path[::-1]
+
+    def next_attempts(self, i, j):
+        """The bands to try next for the pair (i, j): Dijkstra from i to j over ALL minima with the weight 0 for a pair a
+        saddle joins, the squared cached distance otherwise, and infinity for a pair without a cached distance or tried
+        ``max_attempts`` times; returns the pairs ``(p, q)`` of non-zero weight on that path, in path order.  Empty when i and
+        j are connected already, and when every way across is used up."""
+        n, i, j = self.n_minima, int(i), int(j)
+        joined = self._joined[:n, :n]
+        if self._weights is None:
+            d = self._d[:n, :n]
+            self._weights = np.where(joined, 0.0, np.where(self._tries[:n, :n] >= self.max_attempts, np.inf, d * d))
+        w = self._weights
+        dist, back, done = np.full(n, np.inf), np.full(n, -1), np.zeros(n, bool)
+        dist[i] = 0.0
+        for _ in range(n):                                   # dense Dijkstra: the graph is complete
+            u = int(np.argmin(np.where(done, np.inf, dist)))
+            if done[u] or dist[u] == np.inf or u == j:
+                break
+            done[u] = True
+            through = dist[u] + w[u]
+            better = (through < dist) & ~done
+            dist[better], back[better] = through[better], u
+        if dist[j] == np.inf:
+            return []
+        hops, u = [], j
+        while u != i:
+            hops.append((int(back[u]), u))
+            u = int(back[u])
+        return [(p, q) for p, q in hops[::-1] if not joined[p, q]]
+
+
+class PathwayConnections:
+    """What ``connect_pathways`` returns.  ``graph`` (the ``PathwayGraph``); ``minima`` and ``saddles`` (DeviceArrays
+    ``(n_minima, 3N)`` and ``(n_saddles, 3N)``, rows by graph index), ``saddle_modes`` (DeviceArray like ``saddles``: the
+    downhill direction at every saddle), ``minimum_energies`` and ``saddle_energies`` (host); ``pairs`` (host int ``(P, 2)``:
+    the graph indices of the ends of every pair; identical ends share a node); per pair ``connected`` (bool), ``paths``
+    (``PathwayGraph.best_path`` or None), ``barriers`` (the highest saddle on the path minus the energy of the pair's first
+    end; NaN where not connected, 0 for a pair of identical ends), ``cycles_used`` (the cycle after which the pair was first
+    connected; the cycles run otherwise) and ``attempts_used`` (the bands proposed for the pair over all cycles, a band it shares with another pair counted for both); ``cycles`` (one dict per cycle:
+    ``bands``, ``candidates``, ``refined``, ``new_saddles``, ``new_minima``, ``duplicates``, ``degenerate``, ``unresolved``,
+    ``connected`` (pairs, after the cycle), ``minima`` and ``saddles`` (the database's size after it) and ``seconds``, the
+    cycle's time by phase: distances, search (the graph), align, band, candidates, refine, connect)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _rows(host, index, dtype):
+    """The rows ``index`` of the host array as a DeviceArray."""
+    return DeviceArray.from_host(np.ascontiguousarray(host[np.asarray(index, dtype=np.int64)], dtype=dtype))
+
+
+def connect_pathways(a, b, n_particles, n_images, *, tol, displacement, band_iterations=600, max_cycles=10, max_attempts=2,
+                     grad_tol=1e-10, zero_tol=1e-4, refine_steps=300, verify_index=True, steps_per_call=100, align=None,
+                     band_options=None, refine_options=None, quench_options=None, radial=RADIAL_LENNARD_JONES):
+    """The connect cycle (Carr, Trygubenko & Wales 2005): which transition states and intermediate minima join minimum ``a[k]``
+    to minimum ``b[k]``, for pairs that may be several elementary steps apart.  ``a`` and ``b`` are DeviceArrays of
+    ``3 * n_particles * P`` elements, in any frames and labellings; neither is changed.  All ends enter one database by
+    ``classify_structures`` with ``tol``, so identical ends share a node.  A cycle: (1) ``PathwayGraph.next_attempts`` of every
+    pair that is not connected yet, duplicates removed; before that (2) the aligned distances of every new database member to
+    all members by ONE ``align_pairs`` call (``align``: its options; ``seed`` is the cycle's number less one unless given;
+    with K members of which k are new that is about k K pairs, gathered on the host and uploaded, ``2 * 3N`` elements each, and the search
+    of (1) is a dense Dijkstra of K^2 operations per pair: both grow quadratically with the database, and from the second cycle on
+    they are most of a cycle's time on the 38-atom workload of the ``pathways-readme`` block of README.md); (3) the attempts are aligned and interpolated
+    (``n_images`` images); (4) one ``ElasticBand`` (``band_options``; ``force_tol`` 0 unless given there) runs
+    ``band_iterations`` iterations, whatever its status; (5) ``band_candidates`` of the bands as they stand, FAILED ones
+    included; (6) ``HybridModeFollowing(directions=tangents)`` (``grad_tol``, ``zero_tol``, ``refine_options``) for at most
+    ``refine_steps`` steps; (7) the CONVERGED instances with ``eigenvalues < -zero_tol`` are kept, and for
+    ``n_particles <= 128`` only those with exactly one eigenvalue of ``hessian_spectrum`` below ``-zero_tol`` unless
+    ``verify_index=False`` (above 128 particles the index is NOT checked: a kept point may be a saddle of higher index);
+    (8) ``connect_saddles(..., known_minima=database)`` (``displacement``, ``tol``, ``quench_options``; ``descent_steps`` is 2000 unless
+    given there, so that an end is taken down its gradient before L-BFGS finishes it); (9) new minima and
+    saddles are appended, a saddle that matches an earlier one in fingerprint and edge is dropped as a duplicate, a saddle
+    with the same minimum on both sides or an end that did not come to rest is dropped and counted.  The cycle ends when every
+    pair is connected, after ``max_cycles`` cycles, or when no pair has an attempt left.  ``tol`` and ``displacement`` have no
+    default: see ``connect_saddles``.  Returns a ``PathwayConnections``."""
+    import time
+    n, pairs_n = _pair_of(a, b, n_particles)
+    m, n3, dtype = int(n_images), 3 * n, a.dtype
+    band_opts = dict(force_tol=0.0)
+    band_opts.update(band_options or {})
+    quench_opts = dict(descent_steps=2000)                   # the ends go down the gradient first: see connect_saddles
+    quench_opts.update(quench_options or {})
+    ends_host = np.concatenate([a.to_host().reshape(pairs_n, n3), b.to_host().reshape(pairs_n, n3)])
+    fp, end_energies = structure_fingerprints(DeviceArray.from_host(ends_host), n, radial)
+    labels, reps = classify_structures(fp, tol)
+    assert np.all(labels >= 0), "an end has a non-finite fingerprint"
+    node = {int(r): k for k, r in enumerate(reps)}
+    graph = PathwayGraph(max_attempts)
+    for r in reps:
+        graph.add_minimum(end_energies[r])
+    minima_host = ends_host[reps].copy()
+    pairs = np.array([[node[int(labels[k])], node[int(labels[pairs_n + k])]] for k in range(pairs_n)], dtype=np.int64).reshape(pairs_n, 2)
+    saddles_host, modes_host = np.empty((0, n3), dtype), np.empty((0, n3), dtype)
+    have_distances = 0                                       # members whose distances to all earlier members are cached
+    cycles_used, attempts_used = np.zeros(pairs_n, np.int64), np.zeros(pairs_n, np.int64)
+
+    def is_connected():
+        component = graph.components()
+        return component[pairs[:, 0]] == component[pairs[:, 1]]
+
+    connected, cycles = is_connected(), []
+    for cycle in range(1, int(max_cycles) + 1):
+        if connected.all():
+            break
+        clock, seconds = time.perf_counter(), {}
+
+        def lap(name):
+            nonlocal clock
+            synchronize()
+            now = time.perf_counter()
+            seconds[name] = seconds.get(name, 0.0) + now - clock
+            clock = now
+
+        # the random starts of this cycle's alignments: a second attempt at a pair is not a copy of the first
+        align_opts = dict(seed=cycle - 1)
+        align_opts.update(align or {})
+        # 2. distances of the new members to all members
+        k_all = graph.n_minima
+        q_new = np.repeat(np.arange(have_distances, k_all), np.arange(have_distances, k_all))
+        p_all = np.concatenate([np.arange(q) for q in range(have_distances, k_all)] + [np.empty(0, np.int64)]).astype(np.int64)
+        if len(q_new):
+            graph.set_distance(p_all, q_new, align_pairs(_rows(minima_host, p_all, dtype), _rows(minima_host, q_new, dtype), n, **align_opts).distances)
+        have_distances = k_all
+        lap("distances")
+        # 1. this cycle's bands
+        attempts, seen = [], set()
+        for k in np.flatnonzero(~connected):
+            for p, q in graph.next_attempts(*pairs[k]):
+                attempts_used[k] += 1
+                if graph._key(p, q) not in seen:
+                    seen.add(graph._key(p, q))
+                    attempts.append((p, q))
+        lap("search")
+        if not attempts:
+            break
+        for p, q in attempts:
+            graph.note_attempt(p, q)
+        cycles_used[~connected] = cycle
+        # 3, 4. align, interpolate, relax
+        ends_a = _rows(minima_host, [p for p, _ in attempts], dtype)
+        aligned = align_pairs(ends_a, _rows(minima_host, [q for _, q in attempts], dtype), n, **align_opts).aligned
+        band = interpolate_band(ends_a, aligned, n, m)
+        lap("align")
+        neb = ElasticBand(band, n, m, radial=radial, **band_opts)
+        try:
+            neb.run(int(band_iterations), steps_per_call)
+        finally:
+            neb.close()
+        lap("band")
+        # 5 .. 7. candidates, refinement, the saddles among them
+        cand = band_candidates(band, n, m, radial=radial)
+        lap("candidates")
+        stats = dict(bands=len(attempts), candidates=cand.count, refined=0, new_saddles=0, new_minima=0, duplicates=0, degenerate=0, unresolved=0)
+        kept_points = kept_modes = None
+        if cand.count:
+            search = HybridModeFollowing(cand.points, n, cand.tangents, zero_tol=zero_tol, grad_tol=grad_tol, radial=radial, **(refine_options or {}))
+            try:
+                search.run(int(refine_steps))
+                keep = np.flatnonzero((search.status == HYBRIDEF_CONVERGED) & (search.eigenvalues < -float(zero_tol)))
+                kept_points, kept_modes = search.current_points[keep], search.modes[keep]
+            finally:
+                search.close()
+            if len(keep) and 3 * n <= SYMEIG_MAX_N and verify_index:
+                negatives, _ = morse_index(hessian_spectrum(DeviceArray.from_host(kept_points), n, radial=radial), zero_tol)
+                kept_points, kept_modes = kept_points[negatives == 1], kept_modes[negatives == 1]
+            stats["refined"] = len(kept_points)
+        lap("refine")
+        # 8, 9. the minima on both sides of every saddle, and the database
+        if kept_points is not None and len(kept_points):
+            known = DeviceArray.from_host(minima_host)
+            pw = connect_saddles(DeviceArray.from_host(kept_points), DeviceArray.from_host(kept_modes), n, displacement, tol, known_minima=known,
+                                 radial=radial, **quench_opts)
+            # position in pw.minima -> graph index: a database member keeps its own, every other distinct end is new
+            found, gid, fresh = pw.minima.to_host().reshape(-1, n3), [], []
+            for pos, r in enumerate(np.flatnonzero(pw.labels == np.arange(len(pw.labels)))):
+                if r < k_all:
+                    gid.append(int(r))
+                else:
+                    gid.append(graph.add_minimum(pw.minimum_energies[pos]))
+                    fresh.append(pos)
+            minima_host = np.concatenate([minima_host, found[fresh]])
+            stats["new_minima"] = len(fresh)
+            # duplicates: the fingerprints of [saddles so far | this cycle's], an earlier row of the same label and the same edge
+            both = np.concatenate([saddles_host, kept_points])
+            sfp, _ = structure_fingerprints(DeviceArray.from_host(both), n, radial)
+            slabels, _ = classify_structures(sfp, tol)
+            s0 = len(saddles_host)
+            have = {}                                        # (fingerprint label, edge) of every saddle of the graph
+            for i, s, j in graph.edges:
+                have[(int(slabels[s]), graph._key(i, j))] = s
+            taken = []
+            for r, (i, j) in enumerate(pw.edges):
+                if i < 0 or j < 0:
+                    stats["unresolved"] += 1
+                    continue
+                i, j = gid[i], gid[j]
+                key = (int(slabels[s0 + r]), graph._key(i, j))
+                if i == j:
+                    stats["degenerate"] += 1
+                elif key[0] >= 0 and key in have:
+                    stats["duplicates"] += 1
+                else:
+                    have[key] = graph.add_saddle(pw.saddle_energies[r], i, j)
+                    taken.append(r)
+            saddles_host = np.concatenate([saddles_host, kept_points[taken]])
+            modes_host = np.concatenate([modes_host, kept_modes[taken]])
+            stats["new_saddles"] = len(taken)
+        lap("connect")
+        connected = is_connected()
+        stats.update(connected=int(connected.sum()), minima=graph.n_minima, saddles=graph.n_saddles, seconds=seconds)
+        cycles.append(stats)
+    paths = [graph.best_path(i, j) for i, j in pairs]
+    e_min, e_sad = np.array(graph.minimum_energies, dtype=np.float64), np.array(graph.saddle_energies, dtype=np.float64)
+    barriers = np.array([np.nan if p is None else 0.0 if len(p) == 1 else e_sad[p[1::2]].max() - e_min[p[0]] for p in paths], dtype=np.float64)
+    return PathwayConnections(graph=graph, minima=DeviceArray.from_host(minima_host), saddles=DeviceArray.from_host(saddles_host) if len(saddles_host) else None,
+                              saddle_modes=DeviceArray.from_host(modes_host) if len(modes_host) else None, minimum_energies=e_min,
+                              saddle_energies=e_sad, pairs=pairs, connected=connected, paths=paths, barriers=barriers,
+                              cycles_used=cycles_used, attempts_used=attempts_used, cycles=cycles)
 
 
 # ------------------------------------------------------------------------------ profiling
@@ -2439,7 +2849,8 @@ __all__ = [
     "symmetric_batch_eigen", "hessian_spectrum", "LowestModes", "lowest_modes", "modefollow_apply", "ModeFollowing",
     "polish_minima", "find_saddles", "hybridef_apply", "HybridModeFollowing", "find_saddles_hybrid", "structure_fingerprints",
     "classify_structures", "unique_structures", "Pathways", "quench_to_rest", "connect_saddles", "neb_plan", "interpolate_band",
-    "neb_apply", "ElasticBand", "BandConnections", "connect_minima", "assign_particles", "Alignment", "align_pairs", "profile_enable",
+    "neb_apply", "ElasticBand", "BandConnections", "connect_minima", "assign_particles", "Alignment", "align_pairs", "BandCandidates",
+    "band_candidates", "PathwayGraph", "PathwayConnections", "connect_pathways", "profile_enable",
     "profile_reset", "unsealed_first_reads", "profile_table", "Problem", "NativeCallbacks", "LineSearchEvaluator",
     "LBFGSOptimizer", "AdGDOptimizer", "BFGSOptimizer", "GradientDescentOptimizer", "update_inverse_hessian_",
     "update_inverse_hessian_mfma_", "symv_", "BatchedBFGS", "Comm", "batches_all_done", "step_",

@@ -39,6 +39,7 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        structure_fingerprints, classify_structures, connect_saddles,
        ElasticBand, interpolate_band!, neb_apply!, neb_plan, connect_minima, NEB_ACTIVE, NEB_CONVERGED, NEB_FAILED,
        assign_particles, align_pairs, ALIGN_TRIAL_IDENTITY, ALIGN_TRIAL_PRINCIPAL, ALIGN_CONVERGED, ALIGN_CYCLE_LIMIT, ALIGN_FAILED,
+       band_candidates, PATHWAY_MAX_BATCH, PATHWAY_OVERFLOW,
        BasinHopping, hop!, set_record!, set_array!
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
@@ -1248,6 +1249,39 @@ function connect_minima(f::typeof(lj_energy), a::HipVector{T}, b::HipVector{T}, 
     end
     return (band=band, energies=energies, status=status, climbing_images=climbing, converged=converged, saddles=saddles,
             saddle_energies=saddle_energies, saddle_status=saddle_status, barriers=barriers, alignment=alignment)
+end
+
+################################################################################ transition-state candidates of many bands
+# (not exercised in the build container either; the Python function of the same name binds the same entry point and IS tested.
+# The connect cycle built on it, connect_pathways with its PathwayGraph, is Python only.)
+const PATHWAY_MAX_PARTICLES, PATHWAY_MAX_IMAGES, PATHWAY_MAX_BATCH = 1024, 32, 1048576
+const PATHWAY_OVERFLOW = 7
+
+"""`band_candidates(band, energies, n_particles, n_images)`: the transition-state candidates of every band of `band` (3N n_images
+elements per band, the layout of `ElasticBand`; not changed) from its energy profile `energies` (n_images per band, for instance
+`array_pointer(eb, NEB_ENERGIES)` wrapped, or `pairwise_batch_energy_gradient!` of the band taken as points):
+`dzo_pathway_batch_candidates`, include/dzo.h states the rule.  Interior image m is a candidate iff `E[m] > E[m-1]` and
+`E[m] >= E[m+1]`.  Returns a named tuple, compacted band-major: `count`, `points` and `tangents` (HipVectors with room for the
+most the bands can hold; the first `3N count` elements are the candidates), `energies`, `band_index` and `image_index` (0-based,
+`count` each) and `offsets` (batch + 1).  Blocks."""
+function band_candidates(band::HipVector{T}, energies::HipVector{T}, n_particles::Integer, n_images::Integer) where {T}
+    n3 = 3 * n_particles
+    batch = div(length(band), n3 * n_images)
+    @assert length(band) == n3 * n_images * batch && length(energies) == n_images * batch && batch >= 1
+    capacity = batch * div(n_images - 1, 2)
+    points, tangents = HipVector{T}(undef, n3 * capacity), HipVector{T}(undef, n3 * capacity)
+    cand_energies = HipVector{T}(undef, capacity)
+    band_index, image_index = HipVector{Float32}(undef, capacity), HipVector{Float32}(undef, capacity)
+    offsets = HipVector{Float32}(undef, batch + 1)
+    count = Ref{Int64}(0)
+    check(ccall((:dzo_pathway_batch_candidates, libdzo), Cint,
+                (Int64, Cint, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                 Ptr{Int64}),
+                n_particles, n_images, batch, dtype_code(T), band.ptr, energies.ptr, capacity, points.ptr, tangents.ptr, cand_energies.ptr,
+                band_index.ptr, image_index.ptr, offsets.ptr, count))
+    k = Int(count[])
+    return (count=k, points=points, tangents=tangents, energies=Array(cand_energies)[1:k], band_index=int32_array(band_index)[1:k],
+            image_index=int32_array(image_index)[1:k], offsets=int32_array(offsets))
 end
 
 ################################################################################ batched AdGD over Lennard-Jones clusters

@@ -1237,6 +1237,66 @@ int32_t dzo_align_batch_pairs(int64_t n_particles, int64_t batch, int32_t dtype,
                               double *trial_distances_dev /* fp64, (n_starts, batch); may be NULL */);
 
 /* ---------------------------------------------------------------------------------------
+ * Transition-state candidates of many bands (the candidate step of the connect cycle of Carr, Trygubenko & Wales 2005, the
+ * method of Wales' OPTIM): a band between two minima that are several elementary steps apart does not converge, and does not
+ * have to.  Every local maximum of its energy profile is a candidate for a transition state, with the band's tangent there as
+ * the first mode of a refinement (dzo_hybridef_batch_*).  dzo_pathway_batch_candidates takes the candidates of `batch` bands
+ * and compacts them.  Nothing in the reference does this: this block is the specification.  No potential is evaluated (the
+ * caller supplies the energies), so there is no `radial`.
+ *
+ * band_dev is (3N, M batch), the layout of dzo_neb_batch_*: image m of band b sits at element 3N (M b + m), [x | y | z].
+ * energies_dev is (M, batch) in T, for instance DZO_NEB_ENERGIES of a handle or dzo_pairwise_batch_energy_gradient of the band
+ * taken as M batch points.  Neither is changed.  1 <= n_particles <= DZO_PATHWAY_MAX_PARTICLES = 1024,
+ * 3 <= n_images <= DZO_PATHWAY_MAX_IMAGES = 32, 1 <= batch <= DZO_PATHWAY_MAX_BATCH = 1048576.
+ *
+ * Candidate rule.  Interior image m, 1 <= m <= M-2, of band b is a candidate iff E_m > E_{m-1} and E_m >= E_{m+1}, plain
+ * comparisons in T.  So a plateau E_m == E_{m+1} yields its first image only, E_m == E_{m-1} is no candidate, a NaN on either
+ * side of a comparison yields nothing, and the ends are never candidates.  A band holds at most (M - 1) / 2 candidates.
+ * Order.  Candidates are numbered band-major, the image index ascending inside a band: offsets_dev[b] is the number of
+ * candidates of the bands before b, offsets_dev[batch] the count; candidate offsets_dev[b] + k is the k-th of band b.
+ * Per candidate c (band b, image m): points_dev row c = x_m, copied; candidate_energies_dev[c] = E_m, copied;
+ * band_index_dev[c] = b, image_index_dev[c] = m; tangents_dev row c = tau, the improved tangent of the band rule of
+ * dzo_neb_batch_* (its item 2), restated: d+ = x_{m+1} - x_m and d- = x_m - x_{m-1}, element by element in T.
+ * If E_{m+1} > E_m > E_{m-1}: t = d+.  If E_{m+1} < E_m < E_{m-1}: t = d-.  Otherwise, with (in T)
+ * a = max(|E_{m+1} - E_m|, |E_{m-1} - E_m|) and b = min of the same two: t_e = fma(a, d+_e, b d-_e) if E_{m+1} > E_{m-1}, else
+ * t_e = fma(b, d+_e, a d-_e).  (A candidate always takes the third case.)  tau_e = T(t_e / sqrt(t.t)), the root and the quotient
+ * in fp64.  t.t is in fp64 in the order of the sums of dzo_neb_batch_* for the same N: three terms per particle (a product and
+ * two fused multiply-adds), a thread's particles in order, the wave tree, and for N > 64 the four waves in wave order.  So a
+ * candidate's tangent is bit for bit the tangent dzo_neb_batch_apply records for image m of the same band, and t.t == 0 (two
+ * neighbours on top of the image) gives the same NaN row.
+ *
+ * Capacity.  The five candidate arrays hold `capacity` rows.  If the count exceeds it, candidates capacity, capacity + 1, ...
+ * are not written, offsets_dev and *count are complete all the same, and the call returns DZO_PATHWAY_OVERFLOW = 7 (not a
+ * failure of the device: call again with room for *count).  With capacity == 0 the five arrays may be NULL: the call counts.
+ *
+ * Launches: three on one stream and one host wait at the end, for the count.  (1) One thread per band counts its candidates from
+ * its energies.  (2) ONE 256-thread block turns the counts into exclusive offsets in place: thread t adds the counts of bands
+ * t per .. (t + 1) per - 1, per = ceil(batch / 256), the 256 run sums are scanned in LDS, and the thread writes its run's
+ * offsets; integers, so no order matters, and any batch up to the bound is one pass.  (3) One 256-thread block per band reads
+ * the band's energies into LDS, finds the candidates again and writes its slice: for N <= 64 candidate k goes to wave k mod 4
+ * and lane i holds particle i, for 65 <= N <= 1024 the block takes the candidates in turn and thread t owns particles
+ * t, t + 256, ...  No read-modify-write on memory, one writer per element, every loop is bounded by an argument; a band computes
+ * the same bits alone or anywhere in any batch.  The call blocks.
+ * Out of scope: evaluating the band (dzo_pairwise_batch_energy_gradient does), the refinement, and the cycle that owns the
+ * database of minima and saddles (the host modules' connect_pathways).
+ *
+ * Errors follow the neighbours: unknown dtype, sizes < 1, n_images outside 3 .. 32, a negative capacity, null pointers
+ * DZO_ERR_INVALID; n_particles > 1024 or batch > DZO_PATHWAY_MAX_BATCH DZO_ERR_UNSUPPORTED; a host pointer where a device
+ * pointer is required DZO_ERR_ASSERT.
+ * ------------------------------------------------------------------------------------- */
+#define DZO_PATHWAY_MAX_PARTICLES 1024
+#define DZO_PATHWAY_MAX_IMAGES 32
+#define DZO_PATHWAY_MAX_BATCH 1048576
+/* returned when the count exceeds the capacity */
+#define DZO_PATHWAY_OVERFLOW 7
+int32_t dzo_pathway_batch_candidates(int64_t n_particles, int32_t n_images, int64_t batch, int32_t dtype,
+                                     const void *band_dev /* T, (3N, M batch) */, const void *energies_dev /* T, (M, batch) */,
+                                     int64_t capacity, void *points_dev, void *tangents_dev /* T, (3N, capacity) each */,
+                                     void *candidate_energies_dev /* T, capacity */, int32_t *band_index_dev,
+                                     int32_t *image_index_dev /* int32, capacity each */, int32_t *offsets_dev /* int32, batch + 1 */,
+                                     int64_t *count /* host */);
+
+/* ---------------------------------------------------------------------------------------
  * LBFGSOptimizer  (src/DZOptimization.jl:321-509)
  * ------------------------------------------------------------------------------------- */
 /* Full constructor (:347-397).  ALIASES x_dev and g_dev as current_point / current_gradient
