@@ -66,6 +66,8 @@ template <typename T> __global__ __launch_bounds__(kBlock) void adgd_batch_init_
     }
 }
 
+// (a step kernel is its body as a __device__ function and the entry point that calls it: written into the __global__ function
+// itself, the same statements compile to other code -- DESIGN.md, "One table, one entry point per kernel")
 template <typename T, typename F> __device__ __forceinline__ void adgd_batch_wave_step_body(AdgdBatchArgs<T> a) {
     const int64_t b = blockIdx.x;
     if (a.stuck[b]) return;                                  // :276, the whole wave
@@ -129,8 +131,6 @@ template <typename T, typename F> __device__ __forceinline__ void adgd_batch_wav
     }
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void adgd_batch_wave_step_kernel(AdgdBatchArgs<T> a) { adgd_batch_wave_step_body<T, F>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_adgdb_wave_step(AdgdBatchArgs<T> a) { adgd_batch_wave_step_body<T, F>(a); }
 
 extern __shared__ __attribute__((aligned(16))) double adgd_batch_smem[];
 
@@ -218,8 +218,6 @@ template <typename T, typename F> __device__ __forceinline__ void adgd_batch_blo
     }
 }
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void adgd_batch_block_step_kernel(AdgdBatchArgs<T> a) { adgd_batch_block_step_body<T, F>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_adgdb_block_step(AdgdBatchArgs<T> a) { adgd_batch_block_step_body<T, F>(a); }
 
 }  // namespace dzo
 
@@ -249,11 +247,9 @@ template <typename T> static AdgdBatchArgs<T> ab_args(const dzo_adgd_batch_s *h,
 template <typename T, typename F> static void ab_launch_step(hipStream_t s, const dzo_adgd_batch_s *h, int steps) {
     const AdgdBatchArgs<T> a = ab_args<T>(h, steps, 0.0);
     const dim3 grid((unsigned)h->core.B);
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(adgd_batch_wave_step_kernel, rad_adgdb_wave_step, (T, F), grid, dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL(adgd_batch_block_step_kernel, rad_adgdb_block_step, (T, F), grid, dim3(kBlock), h->core.lds_bytes, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((adgd_batch_wave_step_kernel<T, F>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((adgd_batch_block_step_kernel<T, F>), grid, dim3(kBlock), h->core.lds_bytes, s, a);
 }
-
-template <typename T, typename F> static const void *ab_block_kernel() { return DZO_RADIAL_KERNEL(adgd_batch_block_step_kernel, rad_adgdb_block_step, (T, F)); }
 
 // `what` -> device address, bytes
 static int32_t ab_array(dzo_adgd_batch_s *h, int32_t what, void **p, size_t *bytes) {
@@ -300,10 +296,8 @@ int32_t dzo_adgd_batch_create(int32_t radial, int64_t n_particles, int64_t batch
                            {&h->prev, es * B}, {(void **)&c.stuck, 4 * B}, {(void **)&c.halv, 4 * B}, {(void **)&c.iters, 8 * B},
                            {(void **)&c.active_dev, 8}},
                           "the batched AdGD state");
-    const void *k = dtype == DZO_F64 ? (const void *)adgd_batch_block_step_kernel<double, LJRadial<double>>
-                                     : (const void *)adgd_batch_block_step_kernel<float, LJRadial<float>>;
-    if (rc == DZO_OK && radial != DZO_RADIAL_LENNARD_JONES)
-        rc = [&]() -> int32_t { DZO_DISPATCH_RADIAL(radial, dtype, k = (ab_block_kernel<T, F>())); return DZO_OK; }();
+    const void *k = nullptr;                                  // the block step kernel of the handle's radial and element type
+    if (rc == DZO_OK) rc = [&]() -> int32_t { DZO_DISPATCH_RADIAL(radial, dtype, k = (const void *)adgd_batch_block_step_kernel<T, F>); return DZO_OK; }();
     if (rc == DZO_OK)
         rc = cl_finish_create(&c, k, "batched AdGD state", "batched AdGD constructor", [&](hipStream_t s) -> int32_t {
             DZO_TIMED("adgd_batch_init", s);

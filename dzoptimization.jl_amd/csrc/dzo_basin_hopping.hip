@@ -144,6 +144,8 @@ __device__ __forceinline__ PcgMap bh_map(uint64_t k) {
 extern __shared__ __attribute__((aligned(16))) double basin_smem[];
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
+// (each kernel of this file is its body as a __device__ function and the entry point that calls it: written into the
+// __global__ function itself, the same statements compile to other code -- DESIGN.md, "One table, one entry point per kernel")
 template <typename T, typename F> __device__ __forceinline__ void basin_hop_wave_body(BasinArgs<T> a) {
     const int lane = threadIdx.x, N = a.N, m = a.m;
     const int64_t b = blockIdx.x, base = (int64_t)3 * N * b;
@@ -212,8 +214,6 @@ template <typename T, typename F> __device__ __forceinline__ void basin_hop_wave
     }
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void basin_hop_wave_kernel(BasinArgs<T> a) { basin_hop_wave_body<T, F>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_bhop_wave(BasinArgs<T> a) { basin_hop_wave_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
 // HL: the history ring is in LDS (else in a.slab)
@@ -305,8 +305,6 @@ template <typename T, typename F, bool HL> __device__ __forceinline__ void basin
     }
 }
 template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void basin_hop_block_kernel(BasinArgs<T> a) { basin_hop_block_body<T, F, HL>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void rad_bhop_block(BasinArgs<T> a) { basin_hop_block_body<T, F, HL>(a); }
 
 }  // namespace dzo
 
@@ -348,8 +346,8 @@ static void bh_free(dzo_basin_hopping_s *h) {
 }
 
 template <typename T, typename F> static const void *bh_kernel(const dzo_basin_hopping_s *h) {
-    if (h->N <= 64) return DZO_RADIAL_KERNEL(basin_hop_wave_kernel, rad_bhop_wave, (T, F));
-    return h->hist_lds ? DZO_RADIAL_KERNEL(basin_hop_block_kernel, rad_bhop_block, (T, F, true)) : DZO_RADIAL_KERNEL(basin_hop_block_kernel, rad_bhop_block, (T, F, false));
+    if (h->N <= 64) return (const void *)basin_hop_wave_kernel<T, F>;
+    return h->hist_lds ? (const void *)basin_hop_block_kernel<T, F, true> : (const void *)basin_hop_block_kernel<T, F, false>;
 }
 
 template <typename T, typename F> static void bh_launch(hipStream_t s, const dzo_basin_hopping_s *h, int64_t num_hops, int create, int adapt) {
@@ -366,9 +364,9 @@ template <typename T, typename F> static void bh_launch(hipStream_t s, const dzo
     a.rec_normals = (T *)h->rec_normals; a.rec_uniform = (T *)h->rec_uniform; a.rec_trial = (T *)h->rec_trial;
     a.rec_iters = h->rec_iters; a.rec_code = h->rec_code;
     const dim3 grid((unsigned)h->B);
-    if (h->N <= 64) DZO_LAUNCH_RADIAL(basin_hop_wave_kernel, rad_bhop_wave, (T, F), grid, dim3(64), h->lds_bytes, s, a);
-    else if (h->hist_lds) DZO_LAUNCH_RADIAL(basin_hop_block_kernel, rad_bhop_block, (T, F, true), grid, dim3(kBlock), h->lds_bytes, s, a);
-    else DZO_LAUNCH_RADIAL(basin_hop_block_kernel, rad_bhop_block, (T, F, false), grid, dim3(kBlock), h->lds_bytes, s, a);
+    if (h->N <= 64) hipLaunchKernelGGL((basin_hop_wave_kernel<T, F>), grid, dim3(64), h->lds_bytes, s, a);
+    else if (h->hist_lds) hipLaunchKernelGGL((basin_hop_block_kernel<T, F, true>), grid, dim3(kBlock), h->lds_bytes, s, a);
+    else hipLaunchKernelGGL((basin_hop_block_kernel<T, F, false>), grid, dim3(kBlock), h->lds_bytes, s, a);
 }
 
 // `what` -> device address, bytes

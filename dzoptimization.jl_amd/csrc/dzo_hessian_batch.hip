@@ -46,6 +46,8 @@ template <typename T> struct HessBatchArgs {
     double *curv;              // hvp: (2, batch) u.Hu and u.u, or null
 };
 
+// (each kernel of this file is its body as a __device__ function and the entry point that calls it: written into the
+// __global__ function itself, the same statements compile to other code -- DESIGN.md, "One table, one entry point per kernel")
 // ------------------------------------------------------------------------------ products, WAVE shape: grid batch, block 64
 template <typename T, typename F> __device__ __forceinline__ void hess_batch_wave_hvp_body(HessBatchArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
@@ -72,8 +74,6 @@ template <typename T, typename F> __device__ __forceinline__ void hess_batch_wav
     if (lane == 0) { a.curv[2 * b] = uhu; a.curv[2 * b + 1] = uu; }
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hvp_kernel(HessBatchArgs<T> a) { hess_batch_wave_hvp_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_hessb_wave_hvp(HessBatchArgs<T> a) { hess_batch_wave_hvp_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ products, BLOCK shape: grid batch, block 256
 template <typename T, typename F> __device__ __forceinline__ void hess_batch_block_hvp_body(HessBatchArgs<T> a) {
@@ -110,8 +110,6 @@ template <typename T, typename F> __device__ __forceinline__ void hess_batch_blo
     if (tid == 0) { a.curv[2 * b] = uhu; a.curv[2 * b + 1] = uu; }
 }
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess_batch_block_hvp_kernel(HessBatchArgs<T> a) { hess_batch_block_hvp_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_hessb_block_hvp(HessBatchArgs<T> a) { hess_batch_block_hvp_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ dense Hessians
 // The pair (i, j) seen from particle i at (x, y, z): t[b][a] = the term of row component a for the direction +e_b of particle i
@@ -183,8 +181,6 @@ template <typename T, typename F> __device__ __forceinline__ void hess_batch_wav
     if (live) hb_store_diagonal<T>(col0, n3, N, lane, acc);
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void hess_batch_wave_hessian_kernel(HessBatchArgs<T> a) { hess_batch_wave_hessian_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_hessb_wave_hessian(HessBatchArgs<T> a) { hess_batch_wave_hessian_body<T, F>(a); }
 
 // BLOCK shape: grid batch, block 256
 template <typename T, typename F> __device__ __forceinline__ void hess_batch_block_hessian_body(HessBatchArgs<T> a) {
@@ -221,18 +217,16 @@ template <typename T, typename F> __device__ __forceinline__ void hess_batch_blo
     }
 }
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void hess_batch_block_hessian_kernel(HessBatchArgs<T> a) { hess_batch_block_hessian_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_hessb_block_hessian(HessBatchArgs<T> a) { hess_batch_block_hessian_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ host side
 template <typename T, typename F> static void hb_launch_hvp(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(hess_batch_wave_hvp_kernel, rad_hessb_wave_hvp, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL(hess_batch_block_hvp_kernel, rad_hessb_block_hvp, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((hess_batch_wave_hvp_kernel<T, F>), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hess_batch_block_hvp_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 template <typename T, typename F> static void hb_launch_hessian(hipStream_t s, int64_t batch, const HessBatchArgs<T> &a) {
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(hess_batch_wave_hessian_kernel, rad_hessb_wave_hessian, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL(hess_batch_block_hessian_kernel, rad_hessb_block_hessian, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((hess_batch_wave_hessian_kernel<T, F>), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hess_batch_block_hessian_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 // dzo_chain.h: the launch of dzo_pairwise_batch_hessian on `s`, checked arguments, no wait

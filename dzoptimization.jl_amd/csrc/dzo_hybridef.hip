@@ -197,30 +197,18 @@ template <typename T, typename RF, bool BLOCK> __device__ __forceinline__ void h
 }
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
-template <typename T> __global__ __launch_bounds__(64) void hybridef_wave_step_kernel(HybridefArgs<T> a) { he_run<T, LJRadial<T>, false>(a, nullptr, nullptr); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename RF> __global__ __launch_bounds__(64) void rad_hybef_wave_step(HybridefArgs<T> a) { he_run<T, RF, false>(a, nullptr, nullptr); }
+template <typename T, typename RF> __global__ __launch_bounds__(64) void hybridef_wave_step_kernel(HybridefArgs<T> a) { he_run<T, RF, false>(a, nullptr, nullptr); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
-template <typename T> __global__ __launch_bounds__(kBlock) void hybridef_block_step_kernel(HybridefArgs<T> a) {
-    __shared__ T X[3 * kClMaxN];
-    __shared__ double red[2 * kWaves];
-    he_run<T, LJRadial<T>, true>(a, X, red);
-}
-template <typename T, typename RF> __global__ __launch_bounds__(kBlock) void rad_hybef_block_step(HybridefArgs<T> a) {
+template <typename T, typename RF> __global__ __launch_bounds__(kBlock) void hybridef_block_step_kernel(HybridefArgs<T> a) {
     __shared__ T X[3 * kClMaxN];
     __shared__ double red[2 * kWaves];
     he_run<T, RF, true>(a, X, red);
 }
 
-template <typename T, typename RF> static void he_launch_radial(hipStream_t s, int64_t batch, const HybridefArgs<T> &a) {
-    using F = RF;
-    if (a.N <= 64) DZO_LAUNCH_RADIAL2(hybridef_wave_step_kernel, (T), rad_hybef_wave_step, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL2(hybridef_block_step_kernel, (T), rad_hybef_block_step, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
-}
-template <typename T> static int32_t he_launch(hipStream_t s, int32_t radial, int64_t batch, const HybridefArgs<T> &a) {
-    DZO_RADIAL_CASES_(radial, (he_launch_radial<T, F>(s, batch, a)))
-    return DZO_OK;
+template <typename T, typename RF> static void he_launch(hipStream_t s, int64_t batch, const HybridefArgs<T> &a) {
+    if (a.N <= 64) hipLaunchKernelGGL((hybridef_wave_step_kernel<T, RF>), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hybridef_block_step_kernel<T, RF>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 // the argument checks of apply and create
@@ -319,13 +307,13 @@ int32_t dzo_hybridef_batch_apply(int32_t radial, int64_t n_particles, int64_t ba
     {
         DZO_TIMED("hybridef_step", c.stream);
         DZO_HIP(hipMemsetAsync(status_dev, 0, 4 * (size_t)batch, c.stream));   // every instance ACTIVE
-        DZO_DISPATCH(dtype, HybridefArgs<T> a{};
+        DZO_DISPATCH_RADIAL(radial, dtype, HybridefArgs<T> a{};
                      a.N = (int)n_particles; a.tangent_steps = tangent_steps; a.tangent_steps_convex = tangent_steps_convex;
                      a.zero_tol = (T)zero_tol; a.max_step = max_step; a.tangent_cap = tangent_cap; a.tangent_first = tangent_first; a.grad_tol = grad_tol;
                      a.x = (T *)points_dev; a.lam_in = (const T *)eigenvalues_dev; a.u_in = (const T *)modes_dev;
                      a.E = (T *)energies_dev; a.g = (T *)gradients_dev; a.F = (T *)projections_dev; a.h = (T *)uphill_steps_dev;
                      a.grms = grms_dev; a.status = status_dev; a.tangent = tangent_counts_dev;
-                     DZO_TRY(he_launch<T>(c.stream, radial, batch, a)));
+                     (he_launch<T, F>(c.stream, batch, a)));
         DZO_HIP(hipGetLastError());
     }
     DZO_HIP(hipStreamSynchronize(c.stream));
@@ -405,7 +393,7 @@ int32_t dzo_hybridef_batch_step(dzo_hybridef_batch_t h, int32_t steps, int32_t *
             }
             h->have_modes = true;
             DZO_TIMED("hybridef_step", s);
-            DZO_DISPATCH(c.dtype, DZO_TRY(he_launch<T>(s, c.radial, c.B, he_args<T>(h))));
+            DZO_DISPATCH_RADIAL(c.radial, c.dtype, (he_launch<T, F>(s, c.B, he_args<T>(h))));
             DZO_HIP(hipGetLastError());
         }
         return DZO_OK;

@@ -46,6 +46,8 @@ template <typename T> struct QuenchArgs {
 };
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
+// (each kernel of this file is its body as a __device__ function and the entry point that calls it: written into the
+// __global__ function itself, the same statements compile to other code -- DESIGN.md, "One table, one entry point per kernel")
 template <typename T, typename F> __device__ __forceinline__ void quench_wave_eval_body(QuenchArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
     const int64_t b = blockIdx.x, base = (int64_t)3 * N * b;
@@ -62,8 +64,6 @@ template <typename T, typename F> __device__ __forceinline__ void quench_wave_ev
     if (lane == 0) a.stuck[b] = stuck ? 1 : 0;
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void quench_wave_eval_kernel(QuenchArgs<T> a) { quench_wave_eval_body<T, F>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_quench_wave_eval(QuenchArgs<T> a) { quench_wave_eval_body<T, F>(a); }
 
 extern __shared__ __attribute__((aligned(16))) double quench_smem[];
 
@@ -121,8 +121,6 @@ template <typename T, typename F> __device__ __forceinline__ void quench_wave_st
     }
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void quench_wave_step_kernel(QuenchArgs<T> a) { quench_wave_step_body<T, F>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_quench_wave_step(QuenchArgs<T> a) { quench_wave_step_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
 template <typename T, typename F> __device__ __forceinline__ void quench_block_eval_body(QuenchArgs<T> a) {
@@ -148,8 +146,6 @@ template <typename T, typename F> __device__ __forceinline__ void quench_block_e
     if (tid == 0) a.stuck[b] = stuck ? 1 : 0;
 }
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void quench_block_eval_kernel(QuenchArgs<T> a) { quench_block_eval_body<T, F>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_quench_block_eval(QuenchArgs<T> a) { quench_block_eval_body<T, F>(a); }
 
 // HL: the history ring is in LDS (else in a.slab)
 template <typename T, typename F, bool HL> __device__ __forceinline__ void quench_block_step_body(QuenchArgs<T> a) {
@@ -200,8 +196,6 @@ template <typename T, typename F, bool HL> __device__ __forceinline__ void quenc
     }
 }
 template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void quench_block_step_kernel(QuenchArgs<T> a) { quench_block_step_body<T, F, HL>(a); }
-// LJRadial<T> keeps the entry point above; the other radials run the same body under a name of its own (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F, bool HL> __global__ __launch_bounds__(kBlock) void rad_quench_block_step(QuenchArgs<T> a) { quench_block_step_body<T, F, HL>(a); }
 
 // instances that are not stuck: one block, integer sums
 __global__ __launch_bounds__(kBlock) void quench_count_active_kernel(int64_t batch, const int32_t *__restrict__ stuck, int64_t *__restrict__ out) {
@@ -246,8 +240,8 @@ template <typename T> static QuenchArgs<T> qb_args(const dzo_lbfgs_batch_s *h, i
 }
 
 template <typename T, typename F> static void qb_launch_eval(hipStream_t s, int64_t batch, const QuenchArgs<T> &a) {
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(quench_wave_eval_kernel, rad_quench_wave_eval, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL(quench_block_eval_kernel, rad_quench_block_eval, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((quench_wave_eval_kernel<T, F>), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((quench_block_eval_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 template <typename T> int32_t cl_launch_eval(hipStream_t s, int32_t radial, int N, int64_t batch, const T *x, T *f, T *g) {
@@ -260,17 +254,17 @@ template int32_t cl_launch_eval<double>(hipStream_t, int32_t, int, int64_t, cons
 template int32_t cl_launch_eval<float>(hipStream_t, int32_t, int, int64_t, const float *, float *, float *);
 
 template <typename T, typename F> static const void *qb_step_kernel(const dzo_lbfgs_batch_s *h) {
-    if (h->core.N <= 64) return DZO_RADIAL_KERNEL(quench_wave_step_kernel, rad_quench_wave_step, (T, F));
-    return h->hist_lds ? DZO_RADIAL_KERNEL(quench_block_step_kernel, rad_quench_block_step, (T, F, true)) : DZO_RADIAL_KERNEL(quench_block_step_kernel, rad_quench_block_step, (T, F, false));
+    if (h->core.N <= 64) return (const void *)quench_wave_step_kernel<T, F>;
+    return h->hist_lds ? (const void *)quench_block_step_kernel<T, F, true> : (const void *)quench_block_step_kernel<T, F, false>;
 }
 
 template <typename T, typename F> static void qb_launch_step(hipStream_t s, const dzo_lbfgs_batch_s *h, int steps) {
     const QuenchArgs<T> a = qb_args<T>(h, steps, 0, 0.0);
     const dim3 grid((unsigned)h->core.B);
     const size_t lds = h->core.lds_bytes;
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(quench_wave_step_kernel, rad_quench_wave_step, (T, F), grid, dim3(64), lds, s, a);
-    else if (h->hist_lds) DZO_LAUNCH_RADIAL(quench_block_step_kernel, rad_quench_block_step, (T, F, true), grid, dim3(kBlock), lds, s, a);
-    else DZO_LAUNCH_RADIAL(quench_block_step_kernel, rad_quench_block_step, (T, F, false), grid, dim3(kBlock), lds, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((quench_wave_step_kernel<T, F>), grid, dim3(64), lds, s, a);
+    else if (h->hist_lds) hipLaunchKernelGGL((quench_block_step_kernel<T, F, true>), grid, dim3(kBlock), lds, s, a);
+    else hipLaunchKernelGGL((quench_block_step_kernel<T, F, false>), grid, dim3(kBlock), lds, s, a);
 }
 
 int32_t cl_count_active(ClCore *c, hipStream_t s, int64_t *active) {

@@ -473,16 +473,13 @@ template <typename T, typename F, bool BLOCK> __device__ __forceinline__ void lm
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
 template <typename T, typename F> __global__ __launch_bounds__(64) void lowmode_wave_kernel(LowmodeArgs<T> a) { lm_run<T, F, false>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_lowm_wave(LowmodeArgs<T> a) { lm_run<T, F, false>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid batch, block 256
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void lowmode_block_kernel(LowmodeArgs<T> a) { lm_run<T, F, true>(a); }
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_lowm_block(LowmodeArgs<T> a) { lm_run<T, F, true>(a); }
 
 // ------------------------------------------------------------------------------ host side
 template <typename T, typename F> static const void *lm_kernel(bool block) {
-    return block ? DZO_RADIAL_KERNEL(lowmode_block_kernel, rad_lowm_block, (T, F)) : DZO_RADIAL_KERNEL(lowmode_wave_kernel, rad_lowm_wave, (T, F));
+    return block ? (const void *)lowmode_block_kernel<T, F> : (const void *)lowmode_wave_kernel<T, F>;
 }
 
 static size_t lm_lds_bytes(int N, int K, int32_t dtype) {
@@ -491,8 +488,8 @@ static size_t lm_lds_bytes(int N, int K, int32_t dtype) {
 }
 
 template <typename T, typename F> static void lm_launch(hipStream_t s, int64_t batch, size_t lds, const LowmodeArgs<T> &a) {
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(lowmode_wave_kernel, rad_lowm_wave, (T, F), dim3((unsigned)batch), dim3(64), lds, s, a);
-    else DZO_LAUNCH_RADIAL(lowmode_block_kernel, rad_lowm_block, (T, F), dim3((unsigned)batch), dim3(kBlock), lds, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((lowmode_wave_kernel<T, F>), dim3((unsigned)batch), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL((lowmode_block_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), lds, s, a);
 }
 
 // ------------------------------------------------------------------------------ the asynchronous path (dzo_chain.h)

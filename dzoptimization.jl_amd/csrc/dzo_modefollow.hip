@@ -67,7 +67,9 @@ template <typename T> __device__ __forceinline__ void mf_record(const Modefollow
     a.status[b] = r.status;
 }
 
-// grid batch, block 256; RF is the radial functor (F is the projections' name here)
+// grid batch, block 256; RF is the radial functor (F is the projections' name here).  The body is a __device__ function and the
+// kernel the entry point that calls it: written into the __global__ function itself, the same statements compile to other code
+// ("One table, one entry point per kernel").
 template <typename T, typename RF> __device__ __forceinline__ void modefollow_step_body(ModefollowArgs<T> a) {
     __shared__ T S[6 * kMfMaxDim];                           // X | G | L | F | H | W, n elements each
     __shared__ double ov[kMfMaxDim];                         // |V[:,c].w|
@@ -235,13 +237,10 @@ template <typename T, typename RF> __device__ __forceinline__ void modefollow_st
     rec.steplen = capped ? a.max_step : hn;
     if (tid == 0) mf_record(a, b, rec);
 }
-template <typename T> __global__ __launch_bounds__(kBlock) void modefollow_step_kernel(ModefollowArgs<T> a) { modefollow_step_body<T, LJRadial<T>>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename RF> __global__ __launch_bounds__(kBlock) void rad_mfollow_step(ModefollowArgs<T> a) { modefollow_step_body<T, RF>(a); }
+template <typename T, typename RF> __global__ __launch_bounds__(kBlock) void modefollow_step_kernel(ModefollowArgs<T> a) { modefollow_step_body<T, RF>(a); }
 
 template <typename T, typename RF> static void mf_launch(hipStream_t s, int64_t batch, const ModefollowArgs<T> &a) {
-    using F = RF;
-    DZO_LAUNCH_RADIAL2(modefollow_step_kernel, (T), rad_mfollow_step, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL((modefollow_step_kernel<T, RF>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 // the argument checks of apply and create

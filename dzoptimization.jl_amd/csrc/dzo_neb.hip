@@ -294,11 +294,8 @@ template <typename T, typename F, bool BLOCK> __device__ __forceinline__ void ne
 }
 
 // ------------------------------------------------------------------------------ the two shapes: grid batch, block 256
-template <typename T> __global__ __launch_bounds__(kBlock) void neb_wave_kernel(NebArgs<T> a) { neb_run<T, LJRadial<T>, false>(a); }
-template <typename T> __global__ __launch_bounds__(kBlock) void neb_block_kernel(NebArgs<T> a) { neb_run<T, LJRadial<T>, true>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_band_wave(NebArgs<T> a) { neb_run<T, F, false>(a); }
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_band_block(NebArgs<T> a) { neb_run<T, F, true>(a); }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void neb_wave_kernel(NebArgs<T> a) { neb_run<T, F, false>(a); }
+template <typename T, typename F> __global__ __launch_bounds__(kBlock) void neb_block_kernel(NebArgs<T> a) { neb_run<T, F, true>(a); }
 
 // x_m = fma(T(m / (M - 1)), b - a, a) for the interior images, copies of a and b at the ends: one thread per element
 template <typename T> __global__ __launch_bounds__(kBlock) void neb_interp_kernel(int n, int M, int64_t total, const T *a, const T *b, T *band) {
@@ -313,7 +310,7 @@ template <typename T> __global__ __launch_bounds__(kBlock) void neb_interp_kerne
 }
 
 template <typename T, typename F> static const void *neb_kernel(const NebPlan &plan) {
-    return plan.shape == DZO_NEB_SHAPE_WAVE ? DZO_RADIAL_KERNEL2(neb_wave_kernel, (T), rad_band_wave, (T, F)) : DZO_RADIAL_KERNEL2(neb_block_kernel, (T), rad_band_block, (T, F));
+    return plan.shape == DZO_NEB_SHAPE_WAVE ? (const void *)neb_wave_kernel<T, F> : (const void *)neb_block_kernel<T, F>;
 }
 
 // the LDS attribute of the kernel that serves (radial, N, M, dtype), once per call that launches it: it belongs to the kernel and is
@@ -324,13 +321,9 @@ static int32_t neb_prepare(int32_t radial, int32_t dtype, const NebPlan &plan) {
     return DZO_OK;
 }
 
-template <typename T, typename F> static void neb_launch_radial(hipStream_t s, int64_t batch, const NebPlan &plan, const NebArgs<T> &a) {
-    if (plan.shape == DZO_NEB_SHAPE_WAVE) DZO_LAUNCH_RADIAL2(neb_wave_kernel, (T), rad_band_wave, (T, F), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
-    else DZO_LAUNCH_RADIAL2(neb_block_kernel, (T), rad_band_block, (T, F), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
-}
-template <typename T> static int32_t neb_launch(hipStream_t s, int32_t radial, int64_t batch, const NebPlan &plan, const NebArgs<T> &a) {
-    DZO_RADIAL_CASES_(radial, (neb_launch_radial<T, F>(s, batch, plan, a)))
-    return DZO_OK;
+template <typename T, typename F> static void neb_launch(hipStream_t s, int64_t batch, const NebPlan &plan, const NebArgs<T> &a) {
+    if (plan.shape == DZO_NEB_SHAPE_WAVE) hipLaunchKernelGGL((neb_wave_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
+    else hipLaunchKernelGGL((neb_block_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), (size_t)plan.lds_bytes, s, a);
 }
 
 // the argument checks of every entry point (the ones without a radial pass Lennard-Jones)
@@ -460,13 +453,13 @@ int32_t dzo_neb_batch_apply(int32_t radial, int64_t n_particles, int32_t n_image
         {
             DZO_TIMED("neb_step", c.stream);
             DZO_HIP(hipMemsetAsync(status_dev, 0, 4 * (size_t)batch, c.stream));   // every band ACTIVE
-            DZO_DISPATCH(dtype, NebArgs<T> a{};
+            DZO_DISPATCH_RADIAL(radial, dtype, NebArgs<T> a{};
                          a.N = (int)n_particles; a.M = n_images; a.steps = 1; a.climb = climb; a.ends = 1; a.in_lds = plan.storage == DZO_NEB_STORAGE_LDS;
                          a.climb_after = 0; a.spring = spring; a.dt = dt; a.max_move = max_move; a.force_tol = force_tol;
                          a.band = (T *)band_dev; a.vel = (T *)velocities_dev; a.force = (T *)(forces_dev ? forces_dev : work);
                          a.tan = (T *)tangents_dev; a.grad = (T *)gradients_dev; a.E = (T *)energies_dev; a.frms = force_rms_dev; a.res = residuals_dev;
                          a.climbing = climbing_dev; a.highest = highest_dev; a.status = status_dev; a.iters = nullptr;
-                         DZO_TRY(neb_launch<T>(c.stream, radial, batch, plan, a)));
+                         (neb_launch<T, F>(c.stream, batch, plan, a)));
             DZO_HIP(hipGetLastError());
         }
         DZO_HIP(hipStreamSynchronize(c.stream));
@@ -502,7 +495,7 @@ int32_t dzo_neb_batch_create(int32_t radial, int64_t n_particles, int32_t n_imag
             DZO_TIMED("neb_init", s);
             DZO_HIP(hipMemsetAsync(h->climbing, 0xff, 4 * B, s));   // -1: no image climbs yet
             // the energies of the fixed ends; every other record is zero until the first iteration
-            DZO_DISPATCH(dtype, DZO_TRY(neb_launch<T>(s, radial, batch, h->plan, neb_args<T>(h, 0, 1))));
+            DZO_DISPATCH_RADIAL(radial, dtype, (neb_launch<T, F>(s, batch, h->plan, neb_args<T>(h, 0, 1))));
             return DZO_OK;
         });
     if (rc != DZO_OK) { neb_free(h); return rc; }
@@ -523,7 +516,7 @@ int32_t dzo_neb_batch_step(dzo_neb_batch_t h, int32_t steps, int32_t *all_done) 
     return cl_step(h, steps, all_done, [&](hipStream_t s) -> int32_t {
         const ClCore &c = h->core;
         DZO_TIMED("neb_step", s);
-        DZO_DISPATCH(c.dtype, DZO_TRY(neb_launch<T>(s, c.radial, c.B, h->plan, neb_args<T>(h, steps, 0))));
+        DZO_DISPATCH_RADIAL(c.radial, c.dtype, (neb_launch<T, F>(s, c.B, h->plan, neb_args<T>(h, steps, 0))));
         DZO_HIP(hipGetLastError());
         return DZO_OK;
     });

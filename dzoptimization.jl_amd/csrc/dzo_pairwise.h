@@ -103,27 +103,6 @@ template <typename T, int RHO> struct MorseRadial {
     else if ((radial) == DZO_RADIAL_MORSE_RHO6) { using F = ::dzo::MorseRadial<T, 6>; __VA_ARGS__; }      \
     else if ((radial) == DZO_RADIAL_MORSE_RHO14) { using F = ::dzo::MorseRadial<T, 14>; __VA_ARGS__; }    \
     else { ::dzo::set_error("unknown radial function %d", (int)(radial)); return DZO_ERR_INVALID; }
-// Which kernel serves (T, F).  The Lennard-Jones instantiation of every cluster kernel keeps the entry point it always had; the
-// other radials run the SAME body (a __device__ function, or the unit's run function) through a second entry point with a name
-// of its own, rad_*.  So the set of Lennard-Jones kernels, their names and their code do not depend on how many radials
-// there are.  LJK and RADK are the two templates, TARGS their parenthesised template arguments.
-template <typename T, typename F> struct PwIsLJ { static constexpr bool value = false; };
-template <typename T> struct PwIsLJ<T, LJRadial<T>> { static constexpr bool value = true; };
-#define DZO_UNPAREN(...) __VA_ARGS__
-#define DZO_RADIAL_KERNEL2(LJK, LJARGS, RADK, RADARGS)                                                    \
-    ([]() -> const void * {                                                                               \
-        if constexpr (::dzo::PwIsLJ<T, F>::value) return (const void *)LJK<DZO_UNPAREN LJARGS>;           \
-        else return (const void *)RADK<DZO_UNPAREN RADARGS>;                                              \
-    }())
-#define DZO_LAUNCH_RADIAL2(LJK, LJARGS, RADK, RADARGS, grid, block, lds, s, ...)                          \
-    do {                                                                                                  \
-        if constexpr (::dzo::PwIsLJ<T, F>::value) hipLaunchKernelGGL((LJK<DZO_UNPAREN LJARGS>), grid, block, lds, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((RADK<DZO_UNPAREN RADARGS>), grid, block, lds, s, __VA_ARGS__);           \
-    } while (0)
-// (the units whose Lennard-Jones kernels are templates of T alone pass (T) and (T, F))
-#define DZO_RADIAL_KERNEL(LJK, RADK, TARGS) DZO_RADIAL_KERNEL2(LJK, TARGS, RADK, TARGS)
-#define DZO_LAUNCH_RADIAL(LJK, RADK, TARGS, ...) DZO_LAUNCH_RADIAL2(LJK, TARGS, RADK, TARGS, __VA_ARGS__)
-
 #define DZO_DISPATCH_RADIAL(radial, dtype, ...)                                                           \
     do {                                                                                                  \
         if ((dtype) == DZO_F64) { using T = double; DZO_RADIAL_CASES_(radial, __VA_ARGS__) }              \

@@ -103,6 +103,8 @@ __host__ __device__ __forceinline__ int sk_pow2(int n) {
 }
 
 // ------------------------------------------------------------------------------ fingerprints, WAVE shape: grid batch, block 64
+// (a fingerprint kernel is its body as a __device__ function and the entry point that calls it: written into the __global__
+// function itself, the same statements compile to other code -- DESIGN.md, "One table, one entry point per kernel")
 template <typename T, typename F> __device__ __forceinline__ void structfp_wave_body(StructFpArgs<T> a) {
     using Key = typename StructKey<T>::type;
     const int lane = threadIdx.x, N = a.N;
@@ -131,8 +133,6 @@ template <typename T, typename F> __device__ __forceinline__ void structfp_wave_
     if (a.energy && lane == 0) a.energy[b] = E;
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void structfp_wave_kernel(StructFpArgs<T> a) { structfp_wave_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_sfp_wave(StructFpArgs<T> a) { structfp_wave_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ fingerprints, BLOCK shape: grid batch, block 256
 template <typename T, typename F> __device__ __forceinline__ void structfp_block_body(StructFpArgs<T> a) {
@@ -196,8 +196,6 @@ template <typename T, typename F> __device__ __forceinline__ void structfp_block
     if (a.energy && tid == 0) a.energy[b] = E;
 }
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void structfp_block_kernel(StructFpArgs<T> a) { structfp_block_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_sfp_block(StructFpArgs<T> a) { structfp_block_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ the match matrix: grid (words / 4, batch), block 256
 // wave (k, w) forms word w of row k: bit l is the pair (k, j = 64 w + l)
@@ -261,8 +259,8 @@ __global__ __launch_bounds__(64) void structlabel_kernel(int batch, int words, c
 
 // ------------------------------------------------------------------------------ host side
 template <typename T, typename F> static void sf_launch(hipStream_t s, int64_t batch, const StructFpArgs<T> &a) {
-    if (a.N <= 64) DZO_LAUNCH_RADIAL(structfp_wave_kernel, rad_sfp_wave, (T, F), dim3((unsigned)batch), dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL(structfp_block_kernel, rad_sfp_block, (T, F), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
+    if (a.N <= 64) hipLaunchKernelGGL((structfp_wave_kernel<T, F>), dim3((unsigned)batch), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((structfp_block_kernel<T, F>), dim3((unsigned)batch), dim3(kBlock), 0, s, a);
 }
 
 template <typename T> static void sf_launch_cmp(hipStream_t s, int64_t length, int batch, int words, double tol, const void *fp, unsigned long long *bits) {

@@ -104,6 +104,8 @@ template <typename T> struct McEnd {
 };
 
 // ------------------------------------------------------------------------------ WAVE shape: grid R, block 64
+// (each kernel of this file that evaluates pairs is its body as a __device__ function and the entry point that calls it: written
+// into the __global__ function itself, the same statements compile to other code -- DESIGN.md, "One table, one entry point per kernel")
 template <typename T, typename F> __device__ __forceinline__ void temper_wave_body(TemperArgs<T> a) {
     const int lane = threadIdx.x, N = a.N;
     const int64_t k = blockIdx.x;
@@ -149,8 +151,6 @@ template <typename T, typename F> __device__ __forceinline__ void temper_wave_bo
     if (lane == 0) end.store(radius, acc, rej, s);
 }
 template <typename T, typename F> __global__ __launch_bounds__(64) void temper_wave_kernel(TemperArgs<T> a) { temper_wave_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(64) void rad_temper_wave(TemperArgs<T> a) { temper_wave_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ BLOCK shape: grid R, block 256
 template <typename T, typename F> __device__ __forceinline__ void temper_block_body(TemperArgs<T> a) {
@@ -219,8 +219,6 @@ template <typename T, typename F> __device__ __forceinline__ void temper_block_b
     if (tid == 0) end.store(radius, acc, rej, s);
 }
 template <typename T, typename F> __global__ __launch_bounds__(kBlock) void temper_block_kernel(TemperArgs<T> a) { temper_block_body<T, F>(a); }
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F> __global__ __launch_bounds__(kBlock) void rad_temper_block(TemperArgs<T> a) { temper_block_body<T, F>(a); }
 
 // ------------------------------------------------------------------------------ swap (:89-136): grid ceil(R / 2), block 256
 // Block b owns the pair (a, a + 1), a = 2 b + odd, when a + 1 < R, and the record slots a and a + 1 (block 0 also slot 0 when
@@ -276,12 +274,6 @@ __device__ __forceinline__ void swap_body(int N, int64_t R, int odd, T *__restri
 template <typename T, typename F>
 __global__ __launch_bounds__(kBlock) void swap_kernel(int N, int64_t R, int odd, T *__restrict__ replicas, const T *__restrict__ inv_temps,
                                                       uint64_t *__restrict__ rng, int8_t *__restrict__ rec_swap, T *__restrict__ rec_logp) {
-    swap_body<T, F>(N, R, odd, replicas, inv_temps, rng, rec_swap, rec_logp);
-}
-// the same body under a name of its own for the radials other than Lennard-Jones (dzo_pairwise.h, DZO_LAUNCH_RADIAL)
-template <typename T, typename F>
-__global__ __launch_bounds__(kBlock) void rad_swap(int N, int64_t R, int odd, T *__restrict__ replicas, const T *__restrict__ inv_temps,
-                                                   uint64_t *__restrict__ rng, int8_t *__restrict__ rec_swap, T *__restrict__ rec_logp) {
     swap_body<T, F>(N, R, odd, replicas, inv_temps, rng, rec_swap, rec_logp);
 }
 
@@ -376,8 +368,8 @@ template <typename T, typename F> static int32_t tp_temper_t(dzo_tempering_s *h,
     a.rec_normals = (T *)h->rec_normals;
     a.rec_uniform = (T *)h->rec_uniform;
     a.rec_code = h->rec_code;
-    if (h->N <= 64) DZO_LAUNCH_RADIAL(temper_wave_kernel, rad_temper_wave, (T, F), dim3((unsigned)h->R), dim3(64), 0, s, a);
-    else DZO_LAUNCH_RADIAL(temper_block_kernel, rad_temper_block, (T, F), dim3((unsigned)h->R), dim3(kBlock), 0, s, a);
+    if (h->N <= 64) hipLaunchKernelGGL((temper_wave_kernel<T, F>), dim3((unsigned)h->R), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((temper_block_kernel<T, F>), dim3((unsigned)h->R), dim3(kBlock), 0, s, a);
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
@@ -388,16 +380,13 @@ static int32_t tp_temper(dzo_tempering_s *h, hipStream_t s, int64_t num_steps, v
     return DZO_OK;
 }
 
-template <typename T, typename F> static void tp_launch_swap(dzo_tempering_s *h, hipStream_t s, unsigned grid, size_t lds, int32_t odd) {
-    DZO_LAUNCH_RADIAL(swap_kernel, rad_swap, (T, F), dim3(grid), dim3(kBlock), lds, s, h->N, h->R, odd ? 1 : 0, (T *)h->replicas, (const T *)h->inv_temps,
-                      h->rng, h->rec_swap, (T *)h->rec_logp);
-}
-
 static int32_t tp_swap(dzo_tempering_s *h, hipStream_t s, int32_t odd) {
     DZO_TIMED("tempering_swap", s);
     const unsigned grid = (unsigned)((h->R + 1) / 2);
     const size_t lds = (size_t)6 * h->N * dtype_size(h->dtype);
-    DZO_DISPATCH_RADIAL(h->radial, h->dtype, (tp_launch_swap<T, F>(h, s, grid, lds, odd)));
+    DZO_DISPATCH_RADIAL(h->radial, h->dtype,
+                        hipLaunchKernelGGL((swap_kernel<T, F>), dim3(grid), dim3(kBlock), lds, s, h->N, h->R, odd ? 1 : 0, (T *)h->replicas,
+                                           (const T *)h->inv_temps, h->rng, h->rec_swap, (T *)h->rec_logp));
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }

@@ -6,7 +6,8 @@ import ctypes
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,17 +56,7 @@ def test_header_states_the_arithmetic_with_the_reference_lines():
 def test_adgd_batch_kernels_exist_for_gfx950_without_scratch():
     """Both launch shapes of the step kernel and the constructor's kernel, two element types each: no private segment, no VGPR
     or SGPR spill."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "adgd_batch_" in n)
-    for shape in ("adgd_batch_wave_step_kernel", "adgd_batch_block_step_kernel", "adgd_batch_init_kernel"):
-        for t in ("If", "Id"):
-            assert any(shape + t in n for n in kernels), (shape, t, kernels)
-    assert len(kernels) == 6, kernels
-    for n in kernels:
-        print(n, meta[n])
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+    check_unit("adgd_batch", lj_count=6)
 
 
 def _csrc():
@@ -96,9 +87,9 @@ def test_the_evaluation_has_one_definition():
     assert "pw_pair" not in section and "F::" not in section
     assert 'DZO_TIMED("adgd_batch_init"' in section and 'DZO_TIMED("adgd_batch_step"' in section
     assert header.count("hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClLdsMax") == 1
-    # ... which dzo_adgd_batch_create raises for its block step kernel of either element type
-    assert re.search(r"\(const void \*\)adgd_batch_block_step_kernel<double, LJRadial<double>>\s*:\s*\(const void \*\)adgd_batch_block_step_kernel<float,", section)
-    assert "cl_finish_create(" in section
+    # ... which dzo_adgd_batch_create raises for the block step kernel of the handle's radial and element type
+    assert "DZO_DISPATCH_RADIAL(radial, dtype, k = (const void *)adgd_batch_block_step_kernel<T, F>)" in section
+    assert "cl_finish_create(&c, k, " in section
     assert "csrc/dzo_adgd_batch.hip" in open(os.path.join(PKG, "Makefile")).read()
 
 

@@ -1,15 +1,15 @@
 """CPU-side checks of the alignment unit (the method of tests/test_structure_build.py): the library exports the two entry
 points, the Python table and the Julia module bind them with the header's arity, the constants match the header, the header
 block sits behind the nudged-elastic-band block and states its rule, the kernels exist for gfx950 in the three column-per-lane
-instantiations and both element types without scratch memory or spills and with names the kernel counts of the other units do
-not pick up (those counts are what they were), and the plain-C example compiles and links against the library alone.  No
+instantiations and both element types without scratch memory or spills, and the plain-C example compiles and links against the library alone.  No
 compute here."""
 import ctypes
 import inspect
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,12 +17,6 @@ PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = {"dzo_align_batch_assign": 7, "dzo_align_batch_pairs": 18}
 CONSTANTS = dict(ALIGN_MAX_PARTICLES=1024, ALIGN_MAX_RANDOM_TRIALS=64, ALIGN_MAX_CYCLES=64, ALIGN_TRIAL_IDENTITY=1, ALIGN_TRIAL_PRINCIPAL=2,
                  ALIGN_CONVERGED=0, ALIGN_CYCLE_LIMIT=1, ALIGN_FAILED=2)
-# substrings by which the other units count their kernels
-COUNTED = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "lowmode_", "hybridef_", "basin_hop_", "temper_", "swap_kernel",
-           "analyze_kernel", "pairwise", "batch_step_kernel", "lbfgs_single_pass_kernel", "lbfgs_point_pass_kernel", "gram_pass_lanes_kernel",
-           "combine_kernel", "struct", "neb_")
-# ... and the counts that must stay
-UNCHANGED = {"hybridef_": 4, "lowmode_": 4, "modefollow_": 2, "symeig_": 4, "hess_batch_": 8, "basin_hop_": 6, "adgd_batch_": 6, "neb_": 6}
 BANNED_TITLES = ("Batched LBFGSOptimizer", "Batched AdGDOptimizer", "Batched basin hopping", "Batched Hessian-vector products and dense Hessians",
                  "Batched symmetric eigensolver", "Batched eigenvector following", "Batched lowest Hessian mode",
                  "Batched hybrid eigenvector following", "Structure fingerprints and their classification", "Batched nudged elastic band")
@@ -128,25 +122,8 @@ def test_header_block_is_in_place_and_states_the_rule():
 
 def test_align_kernels_exist_for_gfx950_without_scratch():
     """Three column-per-lane instantiations and the finish kernel in both element types, one finish kernel of the assignment:
-    no private segment, no VGPR or SGPR spill, no name another unit counts by, and the other units' counts unchanged."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "align_" in n and "_kernel" in n)
-    for t in ("Id", "If"):
-        for q in (1, 4, 16):
-            assert any("align_wave_kernel%sLi%dE" % (t, q) in n for n in kernels), (t, q, kernels)
-        assert any("align_finish_kernel%sE" % t in n for n in kernels), (t, kernels)
-    assert len([n for n in kernels if "align_assign_finish_kernel" in n]) == 1
-    assert len(kernels) == 9, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in COUNTED:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_count", 0) <= 512, (n, meta[n])
-    for word, count in UNCHANGED.items():
-        assert len([n for n in meta if word in n]) == count, word
+    no private segment, no VGPR or SGPR spill, no more than 512 vector registers."""
+    check_unit("align", lj_count=9, vgpr_limit=512)
 
 
 def test_the_source_keeps_to_its_rules():

@@ -1,7 +1,6 @@
 """CPU-side checks of the batched basin-hopping unit (the method of tests/test_modefollow_build.py): the library exports its
 entry points, the Python table and the Julia module bind them, the constants match the header, the header states the rule of a
-hop, the kernels exist for gfx950 in both element types and both launch shapes without scratch memory or spills, their names
-contain none of the substrings the other units are counted by and those counts are what they were, the quench loop is defined
+hop, the kernels exist for gfx950 in both element types and both launch shapes without scratch memory or spills, the quench loop is defined
 once (csrc/dzo_quench_core.h) and called by both units, and the plain-C example compiles and links against the library alone.
 No compute here."""
 import ctypes
@@ -9,7 +8,8 @@ import inspect
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,10 +17,6 @@ PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = ["dzo_basin_hopping_" + s for s in ("create", "destroy", "set_max_halvings", "hop", "set_record", "get_ptr", "read", "set")]
 WHATS = ["POINTS", "ENERGIES", "BEST_POINTS", "BEST_ENERGIES", "RADII", "INV_TEMPS", "NUM_ACCEPT", "NUM_REJECT", "RNG_STATES", "HOP_COUNTS",
          "QUENCH_ITERATIONS", "QUENCH_UNFINISHED", "REC_NORMALS", "REC_UNIFORM", "REC_TRIAL_ENERGY", "REC_QUENCH_ITERATIONS", "REC_CODE"]
-# substring of a kernel's name -> kernels of the library that carry it, as counted by the other units' build tests
-COUNTED = {"hess_batch_": 8, "symeig_": 4, "modefollow_": 2}
-OTHERS = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "temper_", "swap_kernel", "analyze_kernel", "pairwise",
-          "batch_step_kernel")
 
 
 def _csrc(name):
@@ -88,26 +84,8 @@ def test_header_states_the_rule_of_a_hop():
 
 def test_basin_hopping_kernels_exist_for_gfx950_without_scratch():
     """One wave kernel and two block kernels (ring in LDS / in the slab) per element type: no private segment, no VGPR or SGPR
-    spill.  The kernels of the other units are counted by substrings of their names: none of them may occur in the new names,
-    and the counts stay."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "basin_hop_" in n)
-    for t in ("Id", "If"):
-        assert any("basin_hop_wave_kernel" + t in n for n in kernels), (t, kernels)
-        for hist in ("Lb1E", "Lb0E"):
-            assert any("basin_hop_block_kernel" + t in n and hist in n for n in kernels), (t, hist, kernels)
-    assert len(kernels) == 6, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in OTHERS:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-    for word, count in COUNTED.items():
-        assert len([n for n in meta if word in n]) == count, word
-    assert len([n for n in meta if re.search(r"quench_(wave|block)_(step|eval)_kernel|quench_count_active_kernel", n)]) == 11
-    assert len([n for n in meta if re.search(r"temper_wave_kernel|temper_block_kernel|swap_kernel|analyze_kernel", n)]) == 8
+    spill.  (tests/test_kernel_inventory.py: no kernel belongs to two units, and every unit's count is what it was.)"""
+    check_unit("basin_hopping", lj_count=6)
 
 
 def test_the_quench_loop_has_one_definition():
@@ -128,7 +106,8 @@ def test_the_quench_loop_has_one_definition():
         assert landmark in core and landmark not in quench and landmark not in basin, landmark
     assert '#include "dzo_quench_core.h"' in quench and '#include "dzo_quench_core.h"' in basin
     assert "atomic" not in basin.split("namespace dzo {", 1)[1]
-    assert "cl_wave_eval<T, F>(" in basin and "cl_block_eval<T, F>(" in basin and "pw_pin_ptr(" in basin and "LJRadial<T>" in basin
+    assert "cl_wave_eval<T, F>(" in basin and "cl_block_eval<T, F>(" in basin and "pw_pin_ptr(" in basin
+    assert "F::energy(" not in basin and "F::first(" not in basin
     for text in (basin, temper):
         assert '#include "dzo_pcg.h"' in text and "pcg_normals<T>(" in text and "0x5851F42D4C957F2D" not in text
     assert "mc_adapted_radius<T>(" in basin and "mc_adapted_radius<T>(" in temper and "mc_exp<T>(" in basin and "mc_exp<T>(" in temper

@@ -8,7 +8,8 @@ import inspect
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,20 +58,7 @@ def test_header_states_the_arithmetic_with_the_reference_lines():
 
 def test_hessian_batch_kernels_exist_for_gfx950_without_scratch():
     """Both launch shapes of both entries, two element types each: no private segment, no VGPR or SGPR spill."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "hess_batch_" in n)
-    for shape in ("wave", "block"):
-        for entry in ("hvp", "hessian"):
-            for t in ("If", "Id"):
-                assert any("hess_batch_%s_%s_kernel%s" % (shape, entry, t) in n for n in kernels), (shape, entry, t, kernels)
-    assert len(kernels) == 8, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in ("adgd_batch_", "pairwise", "quench", "tempering"):
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+    check_unit("hessian_batch", lj_count=8)
 
 
 def test_the_pair_term_has_one_definition():

@@ -1,8 +1,7 @@
 """CPU-side checks of the batched hybrid eigenvector-following unit (the method of tests/test_lowmode_build.py): the library
 exports its entry points, the Python table and the Julia module bind them with the header's arity, the constants match the
 header, the header block sits where its neighbours are and states the rule, the kernels exist for gfx950 in both launch shapes
-and both element types without scratch memory or spills and with names the kernel counts of the other units do not pick up
-(those counts are what they were), the source takes its energies, gradients and sums from dzo_cluster.h and its modes from the
+and both element types without scratch memory or spills, the source takes its energies, gradients and sums from dzo_cluster.h and its modes from the
 asynchronous path of the lowest-mode unit, and the plain-C example compiles and links against the library alone.  No compute
 here."""
 import ctypes
@@ -10,7 +9,8 @@ import inspect
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,11 +18,6 @@ PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = ["dzo_hybridef_batch_" + s for s in ("apply", "create", "destroy", "set_directions", "step", "count_active", "get_ptr", "read")]
 WHATS = ["POINTS", "GRADIENTS", "ENERGIES", "GRMS", "STATUS", "EIGENVALUES", "MODES", "MODE_RESIDUALS", "PROJECTIONS", "UPHILL_STEPS",
          "TANGENT_STEPS", "ITERATION_COUNTS", "PRODUCTS", "EVALUATIONS"]
-# substrings by which the other units count their kernels
-COUNTED = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "lowmode_", "basin_hop_", "temper_", "swap_kernel", "analyze_kernel",
-           "pairwise", "batch_step_kernel", "lbfgs_single_pass_kernel", "lbfgs_point_pass_kernel", "gram_pass_lanes_kernel", "combine_kernel")
-# ... and the counts that must stay
-UNCHANGED = {"lowmode_": 4, "modefollow_": 2, "symeig_": 4, "hess_batch_": 8, "basin_hop_": 6, "adgd_batch_": 6}
 BANNED_TITLES = ("Batched LBFGSOptimizer", "Batched AdGDOptimizer", "Batched basin hopping", "Batched Hessian-vector products and dense Hessians",
                  "Batched symmetric eigensolver", "Batched eigenvector following", "Batched lowest Hessian mode")
 
@@ -118,23 +113,8 @@ def test_header_block_is_in_place_and_states_the_rule():
 
 
 def test_hybridef_kernels_exist_for_gfx950_without_scratch():
-    """Two launch shapes, two element types: no private segment, no VGPR or SGPR spill, no name another unit counts by, and the
-    other units' counts unchanged."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "hybridef_" in n)
-    for shape in ("wave", "block"):
-        for t in ("If", "Id"):
-            assert any("hybridef_%s_step_kernel%sE" % (shape, t) in n for n in kernels), (shape, t, kernels)
-    assert len(kernels) == 4, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in COUNTED:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-    for word, count in UNCHANGED.items():
-        assert len([n for n in meta if word in n]) == count, word
+    """Two launch shapes, two element types: no private segment, no VGPR or SGPR spill."""
+    check_unit("hybridef", lj_count=4)
 
 
 def test_the_source_takes_its_pieces_from_the_shared_headers():
@@ -148,7 +128,8 @@ def test_the_source_takes_its_pieces_from_the_shared_headers():
         assert word not in src, word
     # nothing waits between the two launches of a step or between steps
     step = src[src.index("int32_t dzo_hybridef_batch_step("):src.index("int32_t dzo_hybridef_batch_count_active(")]
-    assert "Synchronize" not in step and "cl_step(" in step and step.index("lm_enqueue(") < step.index("he_launch<T>(")
+    assert "Synchronize" not in step and "cl_step(" in step and step.index("lm_enqueue(") < step.index("he_launch<T, F>(")
+    assert step.count("he_launch<") == 1
     chain = open(os.path.join(PKG, "csrc", "dzo_chain.h")).read()
     assert "int32_t lm_prepare(" in chain and "int32_t lm_enqueue(hipStream_t s" in chain
     lowmode = open(os.path.join(PKG, "csrc", "dzo_lowmode.hip")).read()

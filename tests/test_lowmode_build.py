@@ -1,7 +1,7 @@
 """CPU-side checks of the batched lowest Hessian mode (the method of tests/test_hessian_batch_build.py): the library exports the
 entry point, the Python table and the Julia module bind it, the constants match the header, the header block sits where its
 neighbours are and states what a caller relies on, the kernels exist for gfx950 in both launch shapes and both element types
-without scratch memory or spills and with names the kernel counts of the other units do not pick up, the source takes its pair
+without scratch memory or spills, the source takes its pair
 term from dzo_pairwise.h and its dots from dzo_cluster.h, and the plain-C example compiles and links against the library alone.
 No compute here."""
 import ctypes
@@ -11,15 +11,13 @@ import re
 
 import numpy as np
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOL = "dzo_pairwise_batch_lowest_mode"
-# substrings by which the other units count their kernels
-COUNTED = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "basin_hop_", "temper_", "swap_kernel", "analyze_kernel",
-           "pairwise", "batch_step_kernel", "lbfgs_single_pass_kernel", "lbfgs_point_pass_kernel", "gram_pass_lanes_kernel", "combine_kernel")
 
 
 def test_library_exports_the_entry_point_and_both_hosts_bind_it():
@@ -64,20 +62,8 @@ def test_header_block_is_in_place_and_states_the_contract():
 
 
 def test_lowmode_kernels_exist_for_gfx950_without_scratch():
-    """Two launch shapes, two element types: no private segment, no VGPR or SGPR spill, and no name another unit counts."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "lowmode_" in n)
-    for shape in ("wave", "block"):
-        for t in ("If", "Id"):
-            assert any("lowmode_%s_kernel%s" % (shape, t) in n for n in kernels), (shape, t, kernels)
-    assert len(kernels) == 4, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in COUNTED:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+    """Two launch shapes, two element types: no private segment, no VGPR or SGPR spill."""
+    check_unit("lowmode", lj_count=4)
 
 
 def test_the_product_and_the_dots_have_one_definition():

@@ -1,14 +1,14 @@
 """CPU-side checks of the batched eigenvector-following unit (the method of tests/test_symeig_build.py): the library exports its
 entry points, the Python table and the Julia module bind them, the constants match the header, the header states the
-arithmetic of the step, the kernels exist for gfx950 in both element types without scratch memory or spills, their names
-contain none of the substrings the other units are counted by and those counts are what they were, and the plain-C example
+arithmetic of the step, the kernels exist for gfx950 in both element types without scratch memory or spills, and the plain-C example
 compiles and links against the library alone.  No compute here."""
 import ctypes
 import inspect
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,9 +17,6 @@ SYMBOLS = ["dzo_modefollow_batch_" + s for s in ("apply", "create", "destroy", "
                                                  "get_ptr", "read")]
 WHATS = ["POINTS", "GRADIENTS", "ENERGIES", "GRMS", "STATUS", "INDEX", "ZEROS", "FOLLOWED_MODE", "STEP_LENGTHS", "ITERATION_COUNTS",
          "EIGENVALUES", "EIGENVECTORS", "SWEEPS", "FOLLOW"]
-# substring of a kernel's name -> kernels of the library that carry it, as counted by the other units' build tests
-COUNTED = {"hess_batch_": 8, "symeig_": 4}
-OTHERS = ("hess_batch_", "adgd_batch_", "pairwise", "quench_", "swap_kernel", "analyze_kernel", "temper_", "symeig_")
 
 
 def test_library_exports_the_mode_following_entry_points():
@@ -72,23 +69,8 @@ def test_header_states_the_arithmetic_of_the_step():
 
 
 def test_modefollow_kernels_exist_for_gfx950_without_scratch():
-    """One step kernel per element type: no private segment, no VGPR or SGPR spill.  The kernels of the other units are counted
-    by substrings of their names: none of them may occur in the new names, and the counts stay."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "modefollow_" in n)
-    for t in ("Id", "If"):
-        assert any("modefollow_step_kernel%sE" % t in n for n in kernels), (t, kernels)
-    assert len(kernels) == 2, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in OTHERS:
-            assert word not in n, (word, n)
-        assert not re.search(r"batch_step_kernelI[df]Li[124]", n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-    for word, count in COUNTED.items():
-        assert len([n for n in meta if word in n]) == count, word
+    """One step kernel per element type: no private segment, no VGPR or SGPR spill."""
+    check_unit("modefollow", lj_count=2)
     src = open(os.path.join(PKG, "csrc", "dzo_modefollow.hip")).read()
     body = src.split("namespace dzo {", 1)[1]
     assert "atomic" not in body and "cl_wave_eval<" in body and "cl_block_eval<" in body and "cl_block_sum(" in body

@@ -4,26 +4,13 @@ them with scratch memory), and the plain-C example compiles and links against th
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+import kernel_inventory as inv
+from build_checks import link_example
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SELECTORS = {"LENNARD_JONES": 0, "MORSE_RHO6": 2, "MORSE_RHO14": 3}
-# Per unit (csrc/dzo_<unit>.hip): the Lennard-Jones entry points and the entry points of the same bodies for the other radials.
-UNITS = {"pairwise": {"pairwise_tile_kernel": "pairwise_tile_kernel", "pairwise_wave_kernel": "pairwise_wave_kernel",
-                      "pairwise_energy_delta_kernel": "pairwise_energy_delta_kernel"},
-         "tempering": {"temper_wave_kernel": "rad_temper_wave", "temper_block_kernel": "rad_temper_block", "swap_kernel": "rad_swap"},
-         "lbfgs_batch": {"quench_wave_eval_kernel": "rad_quench_wave_eval", "quench_block_eval_kernel": "rad_quench_block_eval",
-                         "quench_wave_step_kernel": "rad_quench_wave_step", "quench_block_step_kernel": "rad_quench_block_step"},
-         "adgd_batch": {"adgd_batch_wave_step_kernel": "rad_adgdb_wave_step", "adgd_batch_block_step_kernel": "rad_adgdb_block_step"},
-         "hessian_batch": {"hess_batch_wave_hvp_kernel": "rad_hessb_wave_hvp", "hess_batch_block_hvp_kernel": "rad_hessb_block_hvp",
-                           "hess_batch_wave_hessian_kernel": "rad_hessb_wave_hessian", "hess_batch_block_hessian_kernel": "rad_hessb_block_hessian"},
-         "lowmode": {"lowmode_wave_kernel": "rad_lowm_wave", "lowmode_block_kernel": "rad_lowm_block"},
-         "structure": {"structfp_wave_kernel": "rad_sfp_wave", "structfp_block_kernel": "rad_sfp_block"},
-         "basin_hopping": {"basin_hop_wave_kernel": "rad_bhop_wave", "basin_hop_block_kernel": "rad_bhop_block"},
-         "modefollow": {"modefollow_step_kernel": "rad_mfollow_step"},
-         "hybridef": {"hybridef_wave_step_kernel": "rad_hybef_wave_step", "hybridef_block_step_kernel": "rad_hybef_block_step"},
-         "neb": {"neb_wave_kernel": "rad_band_wave", "neb_block_kernel": "rad_band_block"}}
+UNITS = inv.RADIAL_UNITS                                     # every unit (csrc/dzo_<unit>.hip) with a kernel that takes a radial
 
 
 def test_header_python_and_julia_agree_on_the_selectors():
@@ -52,25 +39,19 @@ def test_julia_passes_no_radial_literal():
 
 def test_every_radial_unit_has_morse_kernels_without_scratch():
     """Every kernel that takes a radial exists for both Morse ranges and both element types, as many of them as there are
-    Lennard-Jones twins, with no private segment (scratch) and no VGPR spill.  The Lennard-Jones entry points are instantiated
-    for Lennard-Jones only.  (The fp64 Morse kernels keep the constants of exp in scalar registers and move some of those to
-    VGPR lanes; that costs no memory traffic and is reported, not refused.)"""
-    meta = kernel_metadata()
-    moved = {}
-    for unit, kernels in UNITS.items():
-        for lj, rad in kernels.items():
-            for t in ("f", "d"):
-                # (the Lennard-Jones kernels of three units are templates of the element type alone)
-                twins = [n for n in meta if lj in n and ("8LJRadialI%sE" % t in n or "%sI%sE" % (lj, t) in n)]
-                assert len(twins) >= 1, (unit, lj, t)
+    Lennard-Jones twins, with no private segment (scratch) and no VGPR spill.  (The fp64 Morse kernels keep the constants of
+    exp in scalar registers and move some of those to VGPR lanes; that costs no memory traffic and is reported, not refused.)"""
+    meta, moved = inv.code_object()[0], {}
+    for unit in UNITS:
+        found = inv.present(unit)
+        for kernel, axes in inv.UNITS[unit].items():
+            for t in inv.ELEMENT_TYPES if axes and inv.R in axes else ():
+                twins = [i for i in found if i[:3] == (kernel, t, "LJ")]
+                assert len(twins) >= 1, (unit, kernel, t)
                 for rho in (6, 14):
-                    tag = "11MorseRadialI%sLi%dEE" % (t, rho)
-                    hits = [n for n in meta if rad in n and tag in n]
-                    assert len(hits) == len(twins), (unit, rad, t, rho, hits, twins)
-                    if rad != lj:
-                        assert [n for n in meta if lj in n and tag in n] == [], (unit, lj)
-                        assert [n for n in meta if rad in n and "LJRadial" in n] == [], (unit, rad)
-                    for n in hits:
+                    hits = [i for i in found if i[:3] == (kernel, t, "Morse%d" % rho)]
+                    assert sorted(i[3] for i in hits) == sorted(i[3] for i in twins), (unit, kernel, t, rho, hits, twins)
+                    for n in (found[i] for i in hits):
                         assert meta[n].get("private_segment_fixed_size", 0) == 0 and meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
                         if meta[n].get("sgpr_spill_count", 0):
                             moved[n] = meta[n]["sgpr_spill_count"]

@@ -1,8 +1,7 @@
 """CPU-side checks of the batched nudged elastic band (the method of tests/test_hybridef_build.py): the library exports its
 entry points, the Python table and the Julia module bind them with the header's arity, the constants match the header, the
 header block sits where its neighbours are and states the rule, the kernels exist for gfx950 in both launch shapes and both
-element types without scratch memory or spills and with names the kernel counts of the other units do not pick up (those counts
-are what they were), the source takes its energies, gradients and sums from dzo_cluster.h, the residency plan is pinned at its
+element types without scratch memory or spills, the source takes its energies, gradients and sums from dzo_cluster.h, the residency plan is pinned at its
 edges, and the plain-C example compiles and links against the library alone.  No compute here."""
 import ctypes
 import inspect
@@ -11,7 +10,8 @@ import re
 
 import numpy as np
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,12 +19,6 @@ PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = ["dzo_neb_plan"] + ["dzo_neb_batch_" + s for s in ("interpolate", "apply", "create", "destroy", "step", "count_active", "get_ptr", "read")]
 WHATS = ["BAND", "VELOCITIES", "FORCES", "TANGENTS", "ENERGIES", "FORCE_RMS", "RESIDUALS", "CLIMBING_IMAGES", "HIGHEST_IMAGES", "STATUS",
          "ITERATION_COUNTS"]
-# substrings by which the other units count their kernels
-COUNTED = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "lowmode_", "hybridef_", "basin_hop_", "temper_", "swap_kernel",
-           "analyze_kernel", "pairwise", "batch_step_kernel", "lbfgs_single_pass_kernel", "lbfgs_point_pass_kernel", "gram_pass_lanes_kernel",
-           "combine_kernel", "struct")
-# ... and the counts that must stay
-UNCHANGED = {"lowmode_": 4, "modefollow_": 2, "symeig_": 4, "hess_batch_": 8, "basin_hop_": 6, "adgd_batch_": 6, "hybridef_": 4}
 BANNED_TITLES = ("Batched LBFGSOptimizer", "Batched AdGDOptimizer", "Batched basin hopping", "Batched Hessian-vector products and dense Hessians",
                  "Batched symmetric eigensolver", "Batched eigenvector following", "Batched lowest Hessian mode",
                  "Batched hybrid eigenvector following", "Structure fingerprints and their classification")
@@ -133,23 +127,8 @@ def test_header_block_is_in_place_and_states_the_rule():
 
 
 def test_neb_kernels_exist_for_gfx950_without_scratch():
-    """Two launch shapes and the interpolation, two element types: no private segment, no VGPR or SGPR spill, no name another unit
-    counts by, and the other units' counts unchanged."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "neb_" in n)
-    for kind in ("wave", "block", "interp"):
-        for t in ("If", "Id"):
-            assert any("neb_%s_kernel%sE" % (kind, t) in n for n in kernels), (kind, t, kernels)
-    assert len(kernels) == 6, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in COUNTED:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-    for word, count in UNCHANGED.items():
-        assert len([n for n in meta if word in n]) == count, word
+    """Two launch shapes and the interpolation, two element types: no private segment, no VGPR or SGPR spill."""
+    check_unit("neb", lj_count=6)
 
 
 def test_the_source_takes_its_pieces_from_the_shared_headers():
@@ -163,7 +142,7 @@ def test_the_source_takes_its_pieces_from_the_shared_headers():
         assert word not in src, word
     # one launch per step call, nothing waits inside it or after it
     step = src[src.index("int32_t dzo_neb_batch_step("):src.index("int32_t dzo_neb_batch_count_active(")]
-    assert "Synchronize" not in step and "cl_step(" in step and step.count("neb_launch<T>(") == 1 and "for (" not in step
+    assert "Synchronize" not in step and "cl_step(" in step and step.count("neb_launch<T, F>(") == 1 and step.count("neb_launch<") == 1 and "for (" not in step
     cluster = open(os.path.join(PKG, "csrc", "dzo_cluster.h")).read()
     assert "__global__" not in cluster
     plan = open(os.path.join(PKG, "csrc", "dzo_neb_plan.h")).read()

@@ -5,7 +5,8 @@ import ctypes
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,18 +32,9 @@ def test_python_constants_and_functions():
 
 
 def test_pairwise_kernels_exist_for_gfx950_without_scratch():
-    """Four entries x two element types is the fewest there can be; every one of them keeps its accumulators in registers:
-    no private segment, no VGPR or SGPR spill."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "pairwise" in n)
-    assert len(kernels) >= 8, kernels
-    for shape in ("pairwise_tile_kernel", "pairwise_wave_kernel", "pairwise_energy_delta_kernel"):
-        for t in ("If", "Id"):
-            assert any(shape + t in n for n in kernels), (shape, t, kernels)
-    for n in kernels:
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+    """The tile and wave kernels in their three modes, the energy difference and the two finishing kernels, two element types:
+    every one of them, under every radial, keeps its accumulators in registers: no private segment, no VGPR or SGPR spill."""
+    check_unit("pairwise", lj_count=17, morse_sgpr_clean=True)
 
 
 def test_lj_cluster_example_compiles_and_links(tmp_path):

@@ -1,26 +1,20 @@
 """CPU-side checks of the candidate unit (the method of tests/test_align_build.py): the library exports the entry point, the
 Python table and the Julia module bind it with the header's arity, the constants match the header, the header block sits behind
 the alignment block and states its rule, the kernels exist for gfx950 in both launch shapes and both element types without
-scratch memory or spills and with names the kernel counts of the other units do not pick up (those counts are what they were),
-the source takes its sums from the shared headers, and the plain-C example compiles and links against the library alone.  No
+scratch memory or spills, the source takes its sums from the shared headers, and the plain-C example compiles and links against the library alone.  No
 compute here."""
 import ctypes
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = {"dzo_pathway_batch_candidates": 14}
 CONSTANTS = dict(PATHWAY_MAX_PARTICLES=1024, PATHWAY_MAX_IMAGES=32, PATHWAY_MAX_BATCH=1048576, PATHWAY_OVERFLOW=7)
-# substrings by which the other units count their kernels
-COUNTED = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "lowmode_", "hybridef_", "basin_hop_", "temper_", "swap_kernel",
-           "analyze_kernel", "pairwise", "batch_step_kernel", "lbfgs_single_pass_kernel", "lbfgs_point_pass_kernel", "gram_pass_lanes_kernel",
-           "combine_kernel", "struct", "neb_", "align_")
-# ... and the counts that must stay
-UNCHANGED = {"hybridef_": 4, "lowmode_": 4, "modefollow_": 2, "symeig_": 4, "hess_batch_": 8, "basin_hop_": 6, "adgd_batch_": 6, "neb_": 6}
 BANNED_TITLES = ("Batched LBFGSOptimizer", "Batched AdGDOptimizer", "Batched basin hopping", "Batched Hessian-vector products and dense Hessians",
                  "Batched symmetric eigensolver", "Batched eigenvector following", "Batched lowest Hessian mode",
                  "Batched hybrid eigenvector following", "Structure fingerprints and their classification", "Batched nudged elastic band",
@@ -116,25 +110,8 @@ def test_header_block_is_in_place_and_states_the_rule():
 
 def test_candidate_kernels_exist_for_gfx950_without_scratch():
     """The count, the two shapes of the writing kernel in both element types and the one scan: no private segment, no VGPR or
-    SGPR spill, no name another unit counts by, and the other units' counts unchanged."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "pathcand_" in n and "_kernel" in n)
-    for kind in ("count", "wave", "block"):
-        for t in ("If", "Id"):
-            assert any("pathcand_%s_kernel%sE" % (kind, t) in n for n in kernels), (kind, t, kernels)
-    assert len([n for n in kernels if "pathcand_scan_kernel" in n]) == 1
-    assert len(kernels) == 7, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in COUNTED:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_count", 0) <= 512, (n, meta[n])
-    for word, count in UNCHANGED.items():
-        assert len([n for n in meta if word in n]) == count, word
-    assert len([n for n in meta if "align_" in n and "_kernel" in n]) == 9
+    SGPR spill, no more than 512 vector registers."""
+    check_unit("pathway", lj_count=7, vgpr_limit=512)
 
 
 def test_the_source_keeps_to_its_rules():

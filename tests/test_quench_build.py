@@ -5,7 +5,8 @@ import ctypes
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,27 +51,16 @@ def test_header_cites_the_reference_for_every_entry():
 def test_quench_kernels_exist_for_gfx950_without_scratch():
     """Both launch shapes of the step kernel (the BLOCK shape with the history in LDS and in device memory) and of the
     evaluation kernel, two element types each: no private segment, no VGPR or SGPR spill."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if re.search(r"quench_(wave|block)_(step|eval)_kernel|quench_count_active_kernel", n))
-    assert len(kernels) >= 11, kernels
-    for shape in ("quench_wave_step_kernel", "quench_block_step_kernel", "quench_wave_eval_kernel", "quench_block_eval_kernel"):
-        for t in ("If", "Id"):
-            assert any(shape + t in n for n in kernels), (shape, t, kernels)
-    for t in ("If", "Id"):
-        for hist in ("Lb1E", "Lb0E"):
-            assert any("quench_block_step_kernel" + t in n and hist in n for n in kernels), (t, hist, kernels)
-    for n in kernels:
-        print(n, meta[n])
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+    check_unit("lbfgs_batch", lj_count=11)                    # ... and the one count kernel
 
 
 def test_source_uses_the_shared_pair_arithmetic():
     """The quench, the batched AdGD and the header both are built on (dzo_cluster.h, which holds their pair loops)."""
     src, adgd, header = (open(os.path.join(PKG, "csrc", f)).read() for f in ("dzo_lbfgs_batch.hip", "dzo_adgd_batch.hip", "dzo_cluster.h"))
     assert '#include "dzo_cluster.h"' in src and '#include "dzo_cluster.h"' in adgd and '#include "dzo_pairwise.h"' in header
-    assert "LJRadial<T>" in src and "LJRadial<T>" in adgd and "pw_pair<" in header
+    for text in (src, adgd):
+        assert "cl_wave_eval<T, F>(" in text and "cl_block_eval<T, F>(" in text
+    assert "qc_wave_run<T, F>(" in src and "qc_block_run<T, F>(" in src and "pw_pair<" in header
     for text in (src, adgd, header):
         assert "F::energy(" not in text and "F::first(" not in text
     # the one integer count; no floating-point atomic

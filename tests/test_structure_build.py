@@ -1,26 +1,20 @@
 """CPU-side checks of the structure unit (the method of tests/test_lowmode_build.py): the library exports the two entry points,
 the Python table and the Julia module bind them with the header's arity, the constants match the header, the header block sits
 behind the hybrid eigenvector-following block and states its contract, the kernels exist for gfx950 in both launch shapes and
-both element types without scratch memory or spills and with names the kernel counts of the other units do not pick up (those
-counts are what they were), the source takes its pair term from dzo_pairwise.h and its sums from dzo_cluster.h, and the plain-C
+both element types without scratch memory or spills, the source takes its pair term from dzo_pairwise.h and its sums from dzo_cluster.h, and the plain-C
 example compiles and links against the library alone.  No compute here."""
 import ctypes
 import inspect
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "dzoptimization.jl_amd")
 SYMBOLS = ["dzo_structure_batch_fingerprint", "dzo_structure_batch_classify"]
-# substrings by which the other units count their kernels
-COUNTED = ("quench_", "hess_batch_", "adgd_batch_", "symeig_", "modefollow_", "lowmode_", "hybridef_", "basin_hop_", "temper_", "swap_kernel",
-           "analyze_kernel", "pairwise", "batch_step_kernel", "lbfgs_single_pass_kernel", "lbfgs_point_pass_kernel", "gram_pass_lanes_kernel",
-           "combine_kernel")
-# ... and the counts that must stay
-UNCHANGED = {"hybridef_": 4, "lowmode_": 4, "modefollow_": 2, "symeig_": 4, "hess_batch_": 8, "basin_hop_": 6, "adgd_batch_": 6}
 
 
 def _header_arity(header, name):
@@ -99,25 +93,8 @@ def test_header_block_is_in_place_and_states_the_contract():
 
 def test_structure_kernels_exist_for_gfx950_without_scratch():
     """Two launch shapes and two element types of the fingerprint, the comparison in both element types, one label kernel: no
-    private segment, no VGPR or SGPR spill, no name another unit counts by, and the other units' counts unchanged."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "struct" in n and "_kernel" in n)
-    for shape in ("wave", "block"):
-        for t in ("If", "Id"):
-            assert any("structfp_%s_kernel%s" % (shape, t) in n for n in kernels), (shape, t, kernels)
-    for t in ("If", "Id"):
-        assert any("structcmp_kernel%s" % t in n for n in kernels), (t, kernels)
-    assert len([n for n in kernels if "structlabel_kernel" in n]) == 1
-    assert len(kernels) == 7, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in COUNTED:
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-    for word, count in UNCHANGED.items():
-        assert len([n for n in meta if word in n]) == count, word
+    private segment, no VGPR or SGPR spill."""
+    check_unit("structure", lj_count=7)
 
 
 def test_the_source_takes_its_pieces_from_the_shared_headers():

@@ -1,7 +1,7 @@
 """CPU-side checks of the batched symmetric eigensolver (the method of tests/test_hessian_batch_build.py): the library exports
 its entry points, the Python table and the Julia module bind them, the constant matches the header, the header states the
 arithmetic, the kernels exist for gfx950 in both storages and both element types without scratch memory or spills, the kernel
-counts of the other units are what they were, the storage plan is a sound pure function, and the plain-C example compiles and
+storage plan is a sound pure function, and the plain-C example compiles and
 links against the library alone.  No compute here."""
 import ctypes
 import inspect
@@ -11,7 +11,8 @@ import re
 import numpy as np
 
 import symeig_twin as st
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import UNITS, check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,22 +73,9 @@ def test_header_states_the_arithmetic():
 
 
 def test_symeig_kernels_exist_for_gfx950_without_scratch():
-    """One kernel body, two storages, two element types: no private segment, no VGPR or SGPR spill.  The kernels of the other
-    units are counted by substrings of their names: none of them may occur in the new names, and the counts stay."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if "symeig_" in n)
-    for t in ("Id", "If"):
-        for storage in (dzo.SYMEIG_STORAGE_LDS, dzo.SYMEIG_STORAGE_MEMORY):
-            assert any("symeig_jacobi_kernel%sLi%dE" % (t, storage) in n for n in kernels), (t, storage, kernels)
-    assert len(kernels) == 4, kernels
-    for n in kernels:
-        print(n, meta[n])
-        for word in ("hess_batch_", "adgd_batch_", "pairwise", "quench_", "swap_kernel", "analyze_kernel", "temper_"):
-            assert word not in n, (word, n)
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
-    assert len([n for n in meta if "hess_batch_" in n]) == 8
+    """One kernel body, two storages, two element types: no private segment, no VGPR or SGPR spill."""
+    assert UNITS["symeig"] == {"symeig_jacobi_kernel": ((dzo.SYMEIG_STORAGE_LDS, dzo.SYMEIG_STORAGE_MEMORY),)}
+    check_unit("symeig", lj_count=4)
     src = open(os.path.join(PKG, "csrc", "dzo_symeig.hip")).read()
     assert 'DZO_TIMED("symeig"' in src and "atomic" not in src.split("namespace dzo {", 1)[1]
     assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src and '#include "dzo_symeig_plan.h"' in src

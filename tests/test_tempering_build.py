@@ -5,7 +5,8 @@ import ctypes
 import os
 import re
 
-from build_checks import kernel_metadata, link_example
+from build_checks import link_example
+from kernel_inventory import check_unit
 from dzo_loader import dzo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,16 +45,7 @@ def test_header_states_the_random_number_rule():
 def test_tempering_kernels_exist_for_gfx950_without_scratch():
     """Both launch shapes of the temper kernel, the swap and the analyze kernel, two element types each; every one keeps its
     state in registers: no private segment, no VGPR or SGPR spill."""
-    meta = kernel_metadata()
-    kernels = sorted(n for n in meta if re.search(r"temper_wave_kernel|temper_block_kernel|swap_kernel|analyze_kernel", n))
-    assert len(kernels) >= 8, kernels
-    for shape in ("temper_wave_kernel", "temper_block_kernel", "swap_kernel", "analyze_kernel"):
-        for t in ("If", "Id"):
-            assert any(shape + t in n for n in kernels), (shape, t, kernels)
-    for n in kernels:
-        assert meta[n].get("private_segment_fixed_size", 0) == 0, (n, meta[n])
-        assert meta[n].get("vgpr_spill_count", 0) == 0, (n, meta[n])
-        assert meta[n].get("sgpr_spill_count", 0) == 0, (n, meta[n])
+    check_unit("tempering", lj_count=8)
 
 
 def test_source_uses_the_shared_pair_arithmetic():
