@@ -20,12 +20,14 @@
 // run on one wave (see Inst below).
 //
 // The objective is the chained Rosenbrock function (n = 2 is exactly the README's 2-D
-// Rosenbrock); the search logic mirrors oracle/dzo_oracle_impl.h line for line.
+// Rosenbrock, elementwise by dzo_rosen.h).  The line search is this kernel's own statement, in T arithmetic, of the search
+// that dzo_phi_search.h states for every other caller (see Inst::bracket for why).
 #include <cmath>
 #include <cstdlib>
 
 #include "dzo_common.h"
 #include "dzo_problems.h"
+#include "dzo_rosen.h"
 
 namespace dzo {
 
@@ -78,29 +80,6 @@ template <typename T> __device__ __forceinline__ T t_sqrt(T v);
 template <> __device__ __forceinline__ double t_sqrt<double>(double v) { return sqrt(v); }
 template <> __device__ __forceinline__ float t_sqrt<float>(float v) { return sqrtf(v); }
 template <typename T> __device__ __forceinline__ bool t_finite(T v) { return isfinite(v); }
-template <typename T> __device__ __forceinline__ T t_max();
-template <> __device__ __forceinline__ double t_max<double>() { return 1.7976931348623157e308; }
-template <> __device__ __forceinline__ float t_max<float>() { return 3.4028234663852886e38f; }
-
-// same elementwise expressions as dzo_problems.hip / the oracle
-template <typename T> __device__ __forceinline__ double b_rosen_term(T xi, T xn) {
-    T t1 = (T)1 - xi;
-    T t2 = dfma(-xi, xi, xn);
-    return (double)dfma((T)100 * t2, t2, t1 * t1);
-}
-template <typename T> __device__ __forceinline__ T b_rosen_grad(int i, int n, T xp, T xi, T xn) {
-    T gi = (T)0;
-    if (i + 1 < n) {
-        T t2 = dfma(-xi, xi, xn);
-        T t1 = (T)1 - xi;
-        gi = dfma((T)-400 * xi, t2, (T)-2 * t1);
-    }
-    if (i > 0) {
-        T t2p = dfma(-xp, xp, xi);
-        gi = dfma((T)200, t2p, gi);
-    }
-    return gi;
-}
 
 // The line searches of an instance run on ONE wave (lane-strided loops over the LDS vectors, sums and
 // votes across the wave by DPP / ballot): at n = 256 a thread of the workgroup would own a single
@@ -144,7 +123,7 @@ template <typename T> struct Inst {
             for (int i = lane; i < n; i += 64) acc = __builtin_fma(b_quad_row<T>((const T *)ob.A, n, i, p), (double)p[i], acc);
             f = (T)(0.5 * wave_sum_all_dpp(acc));
         } else {
-            for (int i = lane; i + 1 < n; i += 64) acc += b_rosen_term<T>(p[i], p[i + 1]);
+            for (int i = lane; i + 1 < n; i += 64) acc += rosen_term<T>(p[i], p[i + 1]);
             f = (T)wave_sum_all_dpp(acc);
         }
         if (ob.l2 != 0.0) {                                      // L2RegularizationWrapper (:231-232)
@@ -189,7 +168,11 @@ template <typename T> struct Inst {
         wave_lds_fence();
     }
 
-    // find_three_point_bracket (legacy :49-172) started at t0; see oracle bfgs_bracket
+    // find_three_point_bracket (legacy :49-172) started at t0.  The same decisions as phi_sequential_search of dzo_phi_search.h
+    // (the loop that the dense optimizer runs, tested on the CPU against the oracle), kept as a copy here: with Inst as that
+    // loop's evaluator the eight instantiations keep their registers, scratch and LDS, but config 5 runs 2.5 % slower, beyond
+    // the run-to-run spread (profiles/phi_sequential_ab.json).  A change to one of the two belongs in both;
+    // tests/test_gpu_bfgs_search_paths.py replays this one's rare paths against the oracle.
     __device__ void bracket(const T *dir, T f0, T t0, T &x1, T &f1, T &x2, T &f2) {
         x1 = 0; f1 = f0; x2 = 0; f2 = f0;
         if (!t_finite(f0)) return;                               // :64-66
@@ -257,7 +240,7 @@ template <typename T> __device__ __forceinline__ void block_gradient(const Batch
     for (int i = threadIdx.x; i < n; i += kBlock) {
         T gi;
         if (ob.kind == DZO_PROBLEM_QUADRATIC) gi = (T)b_quad_row<T>((const T *)ob.A, n, i, p);
-        else gi = b_rosen_grad<T>(i, n, i > 0 ? p[i - 1] : (T)0, p[i], i + 1 < n ? p[i + 1] : (T)0);
+        else gi = rosen_grad_elem<T>(i, n, i > 0 ? p[i - 1] : (T)0, p[i], i + 1 < n ? p[i + 1] : (T)0);
         out[i] = b_decorate_grad<T>(ob, gi, p[i]);
     }
     __syncthreads();
@@ -568,7 +551,7 @@ __global__ __launch_bounds__(kBlock) void batch_init_kernel(BatchState st, doubl
     if (ob.kind == DZO_PROBLEM_QUADRATIC) {
         for (int i = threadIdx.x; i < n; i += kBlock) acc = __builtin_fma(b_quad_row<T>((const T *)ob.A, n, i, xs), (double)xs[i], acc);
     } else {
-        for (int i = threadIdx.x; i + 1 < n; i += kBlock) acc += b_rosen_term<T>(xs[i], xs[i + 1]);
+        for (int i = threadIdx.x; i + 1 < n; i += kBlock) acc += rosen_term<T>(xs[i], xs[i + 1]);
     }
     for (int i = threadIdx.x; i < n; i += kBlock) ss = __builtin_fma((double)xs[i], (double)xs[i], ss);
     T fT = ob.kind == DZO_PROBLEM_QUADRATIC ? (T)(0.5 * bsum(acc, red)) : (T)bsum(acc, red);
@@ -578,7 +561,7 @@ __global__ __launch_bounds__(kBlock) void batch_init_kernel(BatchState st, doubl
     for (int i = threadIdx.x; i < n; i += kBlock) {
         T gi;
         if (ob.kind == DZO_PROBLEM_QUADRATIC) gi = (T)b_quad_row<T>((const T *)ob.A, n, i, xs);
-        else gi = b_rosen_grad<T>(i, n, i > 0 ? xs[i - 1] : (T)0, xs[i], i + 1 < n ? xs[i + 1] : (T)0);
+        else gi = rosen_grad_elem<T>(i, n, i > 0 ? xs[i - 1] : (T)0, xs[i], i + 1 < n ? xs[i + 1] : (T)0);
         gi = b_decorate_grad<T>(ob, gi, xs[i]);
         g[i] = gi; d[i] = gi; dx[i] = (T)0; dg[i] = (T)0;
     }

@@ -802,15 +802,6 @@ static int32_t bfgs_phi_fused(dzo_bfgs_s *o, const void *dir, double t, const vo
     return DZO_OK;
 }
 
-static int32_t bfgs_phi(dzo_bfgs_s *o, const void *dir, double t, double *f) {
-    bool fused_ok = false;
-    DZO_TRY(bfgs_phi_fused(o, dir, t, nullptr, f, nullptr, nullptr, nullptr, &fused_ok));
-    if (fused_ok) { o->evals += 1; return DZO_OK; }
-    bool feasible;
-    DZO_TRY(bfgs_point(o, dir, t, nullptr, nullptr));
-    return bfgs_phi_at_scratch(o, f, &feasible);
-}
-
 static int32_t bfgs_scratch_equals(dzo_bfgs_s *o, const void *other, bool *equal) {
     hipStream_t s = o->stream;
     DZO_HIP(hipMemsetAsync(o->flags(), 0, sizeof(int32_t), s));
@@ -822,102 +813,61 @@ static int32_t bfgs_scratch_equals(dzo_bfgs_s *o, const void *other, bool *equal
     return DZO_OK;
 }
 
-static inline bool finite_t(double v) { return std::isfinite(v); }
-
-// find_three_point_bracket (legacy/DZOptimization.jl:49-172), started at step size t0.
-// Mirrors oracle/dzo_oracle_impl.h bfgs_bracket line for line.
-static int32_t bfgs_bracket(dzo_bfgs_s *o, const void *dir, double f0, double t0, double *x1, double *f1, double *x2,
-                            double *f2) {
-    const int32_t dt = o->dtype;
-    const size_t bytes = (size_t)o->n * dtype_size(dt);
-    *x1 = 0; *f1 = f0; *x2 = 0; *f2 = f0;
-    if (!finite_t(f0)) return DZO_OK;                            // :64-66
-    if (!(t0 > 0) || !finite_t(t0)) return DZO_OK;
-    bool changed = false, nonzero = false;
-    double fa = 0;
-    bool feasible = true, have_fa = false;
-    DZO_TRY(bfgs_phi_fused(o, dir, t0, nullptr, &fa, &changed, &nonzero, nullptr, &have_fa));   // :71-80 (+ :104 speculatively)
-    if (!have_fa) DZO_TRY(bfgs_point(o, dir, t0, &changed, &nonzero));
-    if (!nonzero) return DZO_OK;                                 // :83-85
-    double step = t0;
-    bool small = false;
-    while (!changed) {                                           // :91-101
-        step = round_to_dtype(dt, step + step);
-        small = true;
-        have_fa = false;                                         // (the speculative value belonged to a point that did not move)
-        if (!finite_t(step)) return DZO_OK;
-        DZO_TRY(bfgs_point(o, dir, step, &changed, nullptr));
-    }
-    if (have_fa) o->evals += 1;
-    else DZO_TRY(bfgs_phi_at_scratch(o, &fa, &feasible));        // :104,:126
-    if (small) {                                                 // :107-123
-        if (!feasible) return DZO_OK;
-        bool eq;
-        DZO_TRY(bfgs_scratch_equals(o, o->x, &eq));
-        if (eq) return DZO_OK;
-    }
-    if (fa <= f0) {                                              // :130
-        int32_t increases = 0;
-        DZO_HIP(hipMemcpyAsync(o->ref_point, o->scratch, bytes, hipMemcpyDeviceToDevice, o->stream));   // :136
-        for (;;) {                                               // :143-156
-            const double dbl = round_to_dtype(dt, step + step);
-            increases += 1;
-            double fb;
-            bool eq = false, fused_ok = false;
-            DZO_TRY(bfgs_phi_fused(o, dir, dbl, o->ref_point, &fb, nullptr, nullptr, &eq, &fused_ok));   // value and the :150 test together
-            if (fused_ok) o->evals += 1;
-            else DZO_TRY(bfgs_phi(o, dir, dbl, &fb));
-            bool stop = (o->max_increases > 0 && increases >= o->max_increases) || !finite_t(fb) || fb > fa;
-            if (!stop) {
-                if (!fused_ok) DZO_TRY(bfgs_scratch_equals(o, o->ref_point, &eq));  // :150
-                stop = eq;
-            }
-            if (stop) { *x1 = step; *f1 = fa; *x2 = dbl; *f2 = fb; return DZO_OK; }   // :151
-            step = dbl;
-            fa = fb;
-            DZO_HIP(hipMemcpyAsync(o->ref_point, o->scratch, bytes, hipMemcpyDeviceToDevice, o->stream));   // :155
-        }
-    } else {                                                     // :157-171
-        for (;;) {
-            const double hs = round_to_dtype(dt, 0.5 * step);
-            double fb;
-            DZO_TRY(bfgs_phi(o, dir, hs, &fb));
-            if (fb <= f0) { *x1 = hs; *f1 = fb; *x2 = step; *f2 = fa; return DZO_OK; }   // :166
-            if (hs == 0.0) return DZO_OK;
-            step = hs;
-            fa = fb;
-        }
-    }
+static int32_t bfgs_keep_reference(dzo_bfgs_s *o) {
+    DZO_HIP(hipMemcpyAsync(o->ref_point, o->scratch, (size_t)o->n * dtype_size(o->dtype), hipMemcpyDeviceToDevice, o->stream));
+    return DZO_OK;
 }
 
-// QuadraticLineSearch (legacy/DZOptimization.jl:191-216)
-static int32_t bfgs_quadratic_search(dzo_bfgs_s *o, const void *dir, double f0, double t0, double *t_best,
-                                     double *f_best) {
-    const int32_t dt = o->dtype;
-    double x1, f1, x2, f2;
-    DZO_TRY(bfgs_bracket(o, dir, f0, t0, &x1, &f1, &x2, &f2));   // :195
-    double xb = 0, fb = f0;                                      // :196
-    if (f1 < fb) { xb = x1; fb = f1; }                           // :197-199
-    if (f2 < fb) { xb = x2; fb = f2; }                           // :200-202
-    double xq;
-    if (phi_quadratic_request(dt, f0, x1, f1, x2, f2, &xq)) {    // :203-209
-        double fq;
-        DZO_TRY(bfgs_phi(o, dir, xq, &fq));                      // :210
-        if (fq < fb) { xb = xq; fb = fq; }                       // :211-213
+// The evaluator of the sequential search (phi_sequential_search, dzo_phi_search.h) over the pieces above: the trial point
+// lies in o->scratch, the reference point in o->ref_point.  Where the objective has the fused form, point() brings the
+// value and the :150 flag along; the loop then asks for them or drops them.  A failing call stays in rc and ends the loop.
+struct BfgsEvaluator {
+    dzo_bfgs_s *o;
+    const void *dir;
+    int32_t rc = DZO_OK;
+    double f = 0;
+    bool have_f = false, have_eq = false, eq = false;
+    bool failed() const { return rc != DZO_OK; }
+    void point(double t, int at, bool &changed, bool &nonzero) {
+        bool *ch = at <= kPhiAtTinyDouble ? &changed : nullptr, *nz = at == kPhiAtT0 ? &nonzero : nullptr;   // (flags nobody reads cost a sync)
+        const bool vs_ref = at == kPhiAtDoubling;
+        have_f = false;
+        if (at != kPhiAtTinyDouble) rc = bfgs_phi_fused(o, dir, t, vs_ref ? o->ref_point : nullptr, &f, ch, nz, &eq, &have_f);
+        have_eq = have_f && vs_ref;
+        if (!failed() && !have_f) rc = bfgs_point(o, dir, t, ch, nz);
     }
-    *t_best = xb; *f_best = fb;
-    return DZO_OK;
+    double objective(bool *feasible) {
+        if (have_f) o->evals += 1;
+        else if (!failed()) rc = bfgs_phi_at_scratch(o, &f, feasible);
+        return f;
+    }
+    bool same_as(const void *other) {
+        bool equal = false;
+        if (!failed()) rc = bfgs_scratch_equals(o, other, &equal);
+        return equal;
+    }
+    bool same_as_x() { return same_as(o->x); }
+    bool same_as_reference() { return have_eq ? eq : same_as(o->ref_point); }
+    void keep_reference() { if (!failed()) rc = bfgs_keep_reference(o); }
+};
+
+// QuadraticLineSearch (legacy/DZOptimization.jl:191-216) along x + sign*t*dir, started at step size t0
+static int32_t bfgs_sequential_search(dzo_bfgs_s *o, const void *dir, double f0, double t0, double *t_best, double *f_best) {
+    BfgsEvaluator ev{o, dir};
+    phi_sequential_search(o->dtype, o->max_increases, ev, f0, t0, t_best, f_best);
+    return ev.rc;
 }
 
 // ---------------------------------------------------------------------------------------------
 // The two line searches of a dense BFGS step (gradient direction :922-925, quasi-Newton direction
 // :929-932) are independent, so they are advanced side by side: each round evaluates the next
 // points of BOTH in one pass over A (quadratic_phi6_kernel).  Each search is a PhiMachine
-// (dzo_phi_search.h: bfgs_bracket + bfgs_quadratic_search as a resumable state machine whose trial
-// points and gradients are indices); two drivers run the same machines:
-//   bfgs_dual_search   the machines on the HOST: one launch and one wait per round
-//   bfgs_dev_search    the machines on the DEVICE, advanced by each round's finish kernel: one wait per step
-// Both turn indices into buffers by the same tables (PhiBuffers) and end by the same rule (bfgs_search_result).
+// (dzo_phi_search.h: the search as a resumable state machine); three drivers run the same machine:
+//   bfgs_sequential_search   one evaluation at a time (above): every objective, and the tiny-step path of the other two
+//   bfgs_dual_search         two machines on the HOST, speculative requests: one launch and one wait per round
+//   bfgs_dev_search          two machines on the DEVICE, advanced by each round's finish kernel: one wait per step
+// The two speculative ones know trial points and gradients as indices, turn them into buffers by the same tables
+// (PhiBuffers) and end by the same rule (bfgs_search_result).
 // ---------------------------------------------------------------------------------------------
 static_assert(kPhiF32 == DZO_F32, "dzo_phi_search.h restates the dtype code");
 
@@ -941,11 +891,11 @@ static void phi_round_outputs(const dzo_bfgs_s *o, const PhiBuffers &B, int roun
 }
 
 // a search that stopped asking, after `round` rounds: its step size and value, and into o->best_grad[side] the gradient at
-// the best point if phi_result still vouches for its pool entry.  The rare tiny-step path (:91-101) is finished with the
-// sequential code.
+// the best point if phi_result still vouches for its pool entry.  The rare tiny-step path (:91-101) is the sequential
+// driver's: the search runs again from q.t0.
 static int32_t bfgs_search_result(dzo_bfgs_s *o, const PhiBuffers &B, const PhiMachine &q, int round, int side, const void *dir,
                                   double *t, double *f) {
-    if (q.state == kPhiSequential) return bfgs_quadratic_search(o, dir, o->f, q.t0, t, f);
+    if (q.state == kPhiSequential) return bfgs_sequential_search(o, dir, o->f, q.t0, t, f);
     int grad_index;
     phi_result(q, round, t, f, &grad_index);
     if (grad_index >= 0) o->best_grad[side] = (char *)o->grad_pool + (size_t)grad_index * B.vbytes;
@@ -1312,8 +1262,8 @@ static int32_t bfgs_step(dzo_bfgs_s *o) {
                              &t_g, &f_g, &t_b, &f_b, &dual));    // :922-925 and :929-932 side by side
     if (!dual) {
         o->best_grad[0] = o->best_grad[1] = nullptr;
-        DZO_TRY(bfgs_quadratic_search(o, o->g, o->f, round_to_dtype(dt, step_length / grad_norm), &t_g, &f_g));   // :922-925
-        DZO_TRY(bfgs_quadratic_search(o, o->d, o->f, round_to_dtype(dt, step_length / bfgs_norm_v), &t_b, &f_b)); // :929-932
+        DZO_TRY(bfgs_sequential_search(o, o->g, o->f, round_to_dtype(dt, step_length / grad_norm), &t_g, &f_g));   // :922-925
+        DZO_TRY(bfgs_sequential_search(o, o->d, o->f, round_to_dtype(dt, step_length / bfgs_norm_v), &t_b, &f_b)); // :929-932
     }
     if (f_b < o->f && !(f_b > f_g)) {                            // :934
         o->f = f_b;                                              // :937
@@ -1520,7 +1470,7 @@ static int32_t gd_step(dzo_bfgs_s *o) {
     const size_t bytes = (size_t)o->n * dtype_size(dt);
     hipStream_t s = o->stream;
     double t, fv;
-    DZO_TRY(bfgs_quadratic_search(o, o->d, o->f, 1.0, &t, &fv)); // :405-407 (bracket starts at step size 1, :89)
+    DZO_TRY(bfgs_sequential_search(o, o->d, o->f, 1.0, &t, &fv)); // :405-407 (bracket starts at step size 1, :89)
     if (t == 0.0 || !(fv < o->f)) { o->has_terminated = true; return DZO_OK; }   // :410-414
     o->iteration_count += 1;                                     // :415
     DZO_HIP(hipMemcpyAsync(o->dx, o->x, bytes, hipMemcpyDeviceToDevice, s));      // :418
@@ -1717,7 +1667,7 @@ int32_t dzo_symv(int64_t n, int32_t dtype, const void *H_dev, const void *v_dev,
 int32_t dzo_bfgs_line_search(dzo_bfgs_t o, int32_t use_gradient_direction, double t0, double *t_best, double *f_best) {
     DZO_REQUIRE(o && t_best && f_best, DZO_ERR_INVALID, "null argument");
     problem_view_sync(o->problem);
-    return bfgs_quadratic_search(o, use_gradient_direction ? o->g : o->d, o->f, t0, t_best, f_best);
+    return bfgs_sequential_search(o, use_gradient_direction ? o->g : o->d, o->f, t0, t_best, f_best);
 }
 
 int32_t dzo_bfgs_reset(dzo_bfgs_t o) {

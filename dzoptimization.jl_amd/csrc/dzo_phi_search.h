@@ -1,13 +1,20 @@
 // dzo_phi_search.h -- the quadratic line search of the dense BFGS step (find_three_point_bracket + QuadraticLineSearch,
-// legacy/DZOptimization.jl:49-216) as ONE resumable state machine: bfgs_bracket + bfgs_quadratic_search of dzo_bfgs.hip
-// turned inside out.  The machine asks for evaluations (phi_post: the one it needs now plus the one or two it will most
-// likely need next), is fed their values (phi_consume: the primary, then the speculative ones that match what it asks for
-// next) and ends with t_best / f_best (phi_result).  Same decisions, same values, same evaluation counts as the sequential
-// form -- only the order in which evaluations reach the device changes.
+// legacy/DZOptimization.jl:49-216) as ONE resumable state machine, the only statement of the search in the library.  The
+// machine asks for an evaluation (phi_begin, then phi_feed after every value) and ends with t_best / f_best (phi_result).
+// Three drivers run it:
+//   phi_sequential_search      one evaluation at a time over an evaluator: the dense search of dzo_bfgs.hip for callbacks,
+//                              constraints and every objective without a two-direction kernel.  It alone knows the
+//                              tiny-step path (:91-101, :107-123).  (The batched step kernel of dzo_batch.hip keeps a copy
+//                              of this search in T arithmetic: as this loop's evaluator it measured 2.5 % slower.)
+//   bfgs_dual_search,          speculative: every launch evaluates the point the machine needs now plus the one or two it
+//   finish_phi6_advance_kernel will most likely need next (phi_post), and phi_consume feeds the primary, then the speculative
+//                              values that match what the machine asks for next.  Same decisions, values and evaluation
+//                              counts -- only the order in which evaluations reach the device changes.  A first point
+//                              that does not move parks the machine (kPhiSequential) for the sequential driver.
 //
-// Trial points and gradients are INDICES: a trial point is its request slot (0: the search's scratch vector, 1, 2: its two
-// speculative buffers), a gradient its entry of the gradient pool (phi_pool_index).  The host-driven search
-// (bfgs_dual_search) turns them into buffers, the device-driven one (finish_phi6_advance_kernel) works on them as they are.
+// For the speculative drivers trial points and gradients are INDICES: a trial point is its request slot (0: the search's
+// scratch vector, 1, 2: its two speculative buffers), a gradient its entry of the gradient pool (phi_pool_index).  The
+// host-driven search (bfgs_dual_search) turns them into buffers, the device-driven one works on them as they are.
 //
 // No HIP here: every function is __host__ __device__ under hipcc and plain inline under a C++17 compiler, so every path of
 // the search runs on the CPU against the oracle (tools/phi_search_table.cpp, tests/test_phi_search.py).  Arithmetic is in
@@ -66,7 +73,7 @@ DZO_PHI_FN bool phi_quadratic_request(int32_t dt, double f0, double x1, double f
     return true;
 }
 
-DZO_PHI_FN void phi_to_quadratic(int32_t dt, PhiMachine &q) {    // bfgs_quadratic_search after :195
+DZO_PHI_FN void phi_to_quadratic(int32_t dt, PhiMachine &q) {    // QuadraticLineSearch after :195
     q.xb = 0; q.fb = q.f0; q.best_grad = -1; q.best_round = 0;   // :196
     if (q.f1 < q.fb) { q.xb = q.x1; q.fb = q.f1; q.best_grad = q.g1; q.best_round = q.r1; }   // :197-199
     if (q.f2 < q.fb) { q.xb = q.x2; q.fb = q.f2; q.best_grad = q.g2; q.best_round = q.r2; }   // :200-202
@@ -103,8 +110,10 @@ DZO_PHI_FN void phi_begin(int32_t dt, PhiMachine &q, double f0, double t0) {
     q.req_t = t0; q.want = 1; q.req_ref = 0;
 }
 
-// the value of the pending request.  slot: where the evaluation's trial point lies; cur_grad / cur_round: its gradient
-DZO_PHI_FN void phi_feed(int32_t dt, int32_t max_increases, PhiMachine &q, double f, bool changed, bool nonzero, bool equal_ref,
+// the value of the pending request.  slot: where the evaluation's trial point lies; cur_grad / cur_round: its gradient;
+// equal_ref(): whether the trial point is the reference point, called only if :150 is reached
+template <typename EqualRef>
+DZO_PHI_FN void phi_feed(int32_t dt, int32_t max_increases, PhiMachine &q, double f, bool changed, bool nonzero, EqualRef &&equal_ref,
                          int slot, int cur_grad, int cur_round, int64_t &evals) {
     q.want = 0;
     switch (q.state) {
@@ -130,7 +139,7 @@ DZO_PHI_FN void phi_feed(int32_t dt, int32_t max_increases, PhiMachine &q, doubl
         evals += 1;
         const double dbl = q.req_t, fb = f;
         bool stop = (max_increases > 0 && q.increases >= max_increases) || !__builtin_isfinite(fb) || fb > q.fa;
-        if (!stop) stop = equal_ref;                             // :150
+        if (!stop) stop = equal_ref();                           // :150, asked for last: it costs a pass over the point
         if (stop) { phi_bracket_done(dt, q, q.step, q.fa, dbl, fb, q.step_grad, q.step_round, cur_grad, cur_round); return; }   // :151
         q.step = dbl; q.fa = fb; q.step_grad = cur_grad; q.step_round = cur_round;
         q.ref_buf = slot;                                        // :155
@@ -201,8 +210,8 @@ DZO_PHI_FN int phi_consume(int32_t dt, int32_t max_increases, PhiMachine &q, dou
         const int changed = phi_sel3(slot, hf[0], hf[3], hf[6]);
         const int nonzero = phi_sel3(slot, hf[1], hf[4], hf[7]);
         const int differs = phi_sel3(slot, hf[2], hf[5], hf[8]);
-        phi_feed(dt, max_increases, q, phi_sel3(slot, f_0, f_1, f_2), changed != 0, nonzero != 0, differs == 0, slot, pool_base + slot,
-                 round, evals);
+        phi_feed(dt, max_increases, q, phi_sel3(slot, f_0, f_1, f_2), changed != 0, nonzero != 0, [equal = differs == 0] { return equal; }, slot,
+                 pool_base + slot, round, evals);
         if (!q.want) break;
         int next = -1;
         for (int e = 1; e < 3; ++e)
@@ -219,6 +228,53 @@ DZO_PHI_FN int phi_consume(int32_t dt, int32_t max_increases, PhiMachine &q, dou
 DZO_PHI_FN void phi_result(const PhiMachine &q, int round, double *t, double *f, int *grad_index) {
     *t = q.t_best; *f = q.f_best;
     *grad_index = (q.state == kPhiDone && q.t_best != 0.0 && q.best_grad >= 0 && round - q.best_round < 4) ? q.best_grad : -1;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The sequential search: one evaluation at a time, the tiny-step path included.
+
+DZO_PHI_FN double phi_typemax(int32_t dt) { return dt == kPhiF32 ? 3.4028234663852886e38 : 1.7976931348623157e308; }   // typemax(T), :41
+
+// :91-101: the first trial point is x itself -- ask again at twice the step; a step that overflows ends the search at x
+DZO_PHI_FN void phi_tiny_double(int32_t dt, PhiMachine &q) {
+    q.step = q.req_t = phi_rt(dt, q.step + q.step);
+    if (!__builtin_isfinite(q.step)) phi_bracket_done(dt, q, 0, q.f0, 0, q.f0);
+}
+
+enum { kPhiAtT0 = 0, kPhiAtTinyDouble, kPhiAtDoubling, kPhiAtOther };
+
+// The whole search over an evaluator E, which holds x, the direction, the trial point and the reference point:
+//   void   point(double t, int at, bool &changed, bool &nonzero)
+//                                       trial point <- x + sign t dir.  at (kPhiAt...) says which point of the search this is, and
+//                                       so what is wanted: at t0 both flags of :71-80, after a tiny doubling `changed` alone (and
+//                                       objective() will likely not follow), else no flag (while doubling same_as_reference() may follow)
+//   double objective(bool *feasible)    P(trial point) and, if feasible, the objective there -- E counts this evaluation
+//   bool   same_as_x(), same_as_reference()                             the trial point against x (:119), the reference point (:150)
+//   void   keep_reference()             reference point <- trial point (:136 / :155)
+//   bool   failed()                     stops the loop; what was found so far is returned
+// The objective is asked for only where the oracle asks: not at a point that did not move (:91-101), not at an infeasible one
+// (its value is typemax(T), uncounted), and :150 only when the cheaper tests of :147-149 have not ended the doubling.
+template <typename E> DZO_PHI_FN void phi_sequential_run(int32_t dt, int32_t max_increases, E &ev, double f0, double t0, PhiMachine &q) {
+    phi_begin(dt, q, f0, t0);
+    bool small = false;
+    int64_t fed = 0;                                             // (E counts: an infeasible point is fed, not evaluated)
+    while (q.want && !ev.failed()) {
+        const bool first = q.state == kPhiFirst;
+        bool changed = true, nonzero = true, feasible = true;
+        ev.point(q.req_t, first ? (small ? kPhiAtTinyDouble : kPhiAtT0) : (q.req_ref ? kPhiAtDoubling : kPhiAtOther), changed, nonzero);
+        if (nonzero && !changed) { small = true; phi_tiny_double(dt, q); continue; }
+        const double f = nonzero ? ev.objective(&feasible) : 0.0;
+        if (small && first && (!feasible || ev.same_as_x())) { phi_bracket_done(dt, q, 0, f0, 0, f0); continue; }   // :107-123
+        phi_feed(dt, max_increases, q, feasible ? f : phi_typemax(dt), true, nonzero, [&] { return ev.same_as_reference(); }, 0, -1, 0, fed);
+        if (q.state == kPhiDoubling) ev.keep_reference();
+    }
+}
+template <typename E>
+DZO_PHI_FN void phi_sequential_search(int32_t dt, int32_t max_increases, E &ev, double f0, double t0, double *t_best, double *f_best) {
+    PhiMachine q;
+    phi_sequential_run(dt, max_increases, ev, f0, t0, q);
+    int grad_index;
+    phi_result(q, 0, t_best, f_best, &grad_index);
 }
 
 }  // namespace dzo
