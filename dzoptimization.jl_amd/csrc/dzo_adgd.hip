@@ -74,11 +74,9 @@ struct dzo_adgd_s {
     // the same recurrence and checks the value the device used (spec_corrected counts disagreements: none, both
     // sides evaluate the same IEEE expressions).
     bool pipeline = true;            // DZO_TUNE_ADGD_PIPELINE=0: one host round trip per pass
-    bool nt_stores = true;           // DZO_TUNE_ADGD_NT_STORES=0: plain stores of the trial point / gradient (measured: no difference)
     bool prologue = true;            // DZO_TUNE_ADGD_PROLOGUE=0: a decision kernel behind every pass
     dzo::AdgdDev *dev = nullptr;     // [2] states (pass s uses dev[s & 1]) + 4 int32 changed-flags behind them (pass s raises flag s % 3)
     double *pass_partials = nullptr; // [2][3][kMaxPartialBlocks] partial sums of the fused pass (pass s writes set s & 1)
-    int pass_bpc = 4;                // DZO_TUNE_ADGD_BPC: blocks of the fused pass per CU (measured: 4 / 6 / 8 -> 22.0 / 21.4 / 20.4 k step!()/s at n = 1e7)
     double *slots = nullptr, *slots_dev = nullptr;   // pinned: 2 x 8 doubles, outcome of the last two decisions (6 words + their seal)
     bool spec_pending = false;       // a pass is enqueued whose outcome the host has not consumed
     int spec_slot = 0;
@@ -105,6 +103,7 @@ namespace dzo {
 // lane 1 takes only the LAST element of lane 0's trial point and lane 62 the FIRST of lane 63's, and the stencils of
 // those inner elements lie inside the row.  (Round 2's pass read and wrote the gradients: 4 n T.)
 constexpr int kAdgdOwn = 62;
+constexpr int kAdgdPassBpc = 4;     // blocks of the fused pass per CU (measured: 4 / 6 / 8 -> 22.0 / 21.4 / 20.4 k step!()/s at n = 1e7)
 
 template <typename T> struct AdgdFusedParams {
     int64_t n;
@@ -116,7 +115,6 @@ template <typename T> struct AdgdFusedParams {
     AdgdRule rule;
     int32_t seq;                               // the number of this pass
     int32_t mode;                              // 0: decide pass seq - 1 first (prologue); 1: st[seq & 1] is ready
-    int nt_stores;                             // DZO_TUNE_ADGD_NT_STORES
 };
 
 constexpr int64_t kAdgdPartialSet = 3 * (int64_t)kMaxPartialBlocks;
@@ -295,8 +293,7 @@ __global__ __launch_bounds__(kBlock) void adgd_fused_rosen_kernel(AdgdFusedParam
             }
         }
         if (owner) {
-            if (p.nt_stores) store16_nt(xout + v * N, xn);
-            else store16(xout + v * N, xn);
+            store16_nt(xout + v * N, xn);                   // (against plain stores: measured, no difference)
         }
     }
     block_raise_flag(diff, p.flags + p.seq % 3, &lds_flag);
@@ -483,12 +480,11 @@ template <typename T> static int32_t adgd_fused_step(dzo_adgd_s *o, double step,
     fp.rule.to_f32 = c.dtype == DZO_F32 ? 1 : 0;
     fp.rule.inv_sqrt_two = c.dtype == DZO_F32 ? (double)sqrtf(0.5f) : sqrt(0.5);
     fp.rule.max_halvings = (int64_t)c.max_halvings;
-    fp.nt_stores = o->nt_stores ? 1 : 0;
     // grid: four blocks per CU.  (The pass holds 46 registers, so eight would be resident, and a wave has only one row in
     // flight at a time -- but more blocks do not make the pass faster, 33.2-33.7 us by HIP events at 4 / 6 / 8 per CU, and
     // the decision kernel behind it sums three partials per block: 22.0 / 21.4 / 20.4 k step!()/s at n = 1e7, round 3.)
     int64_t blocks = (rows + kWaves - 1) / kWaves;
-    const int64_t cap = (int64_t)ctx().cus * (o->pass_bpc < 1 ? 1 : (o->pass_bpc > 8 ? 8 : o->pass_bpc));
+    const int64_t cap = (int64_t)ctx().cus * kAdgdPassBpc;
     if (blocks > cap) blocks = cap;
     if (blocks > kMaxPartialBlocks) blocks = kMaxPartialBlocks;
     const int grid = (int)(blocks < 1 ? 1 : blocks);
@@ -716,11 +712,9 @@ int32_t dzo_adgd_create(int64_t n, int32_t dtype, void *x_dev, void *g_dev, doub
     c.is_stuck = (gnorm == 0.0);                                   // :231
     const double s0 = c.is_stuck ? 0.0 : round_to_dtype(dtype, initial_step_length / gnorm);  // :232-233
     o->current_step_size = s0; o->previous_step_size = s0;         // :241
-    o->fused = getenv("DZO_TUNE_ADGD_FUSED") ? atoi(getenv("DZO_TUNE_ADGD_FUSED")) != 0 : true;
-    o->pipeline = getenv("DZO_TUNE_ADGD_PIPELINE") ? atoi(getenv("DZO_TUNE_ADGD_PIPELINE")) != 0 : true;
-    o->nt_stores = getenv("DZO_TUNE_ADGD_NT_STORES") ? atoi(getenv("DZO_TUNE_ADGD_NT_STORES")) != 0 : true;
-    o->prologue = getenv("DZO_TUNE_ADGD_PROLOGUE") ? atoi(getenv("DZO_TUNE_ADGD_PROLOGUE")) != 0 : true;
-    o->pass_bpc = getenv("DZO_TUNE_ADGD_BPC") ? atoi(getenv("DZO_TUNE_ADGD_BPC")) : 4;
+    o->fused = tune_int("DZO_TUNE_ADGD_FUSED", 1) != 0;
+    o->pipeline = tune_int("DZO_TUNE_ADGD_PIPELINE", 1) != 0;
+    o->prologue = tune_int("DZO_TUNE_ADGD_PROLOGUE", 1) != 0;
     *out = o;
     return DZO_OK;
 }

@@ -595,7 +595,6 @@ __global__ __launch_bounds__(kBlock) void batch_count_active_kernel(const int32_
 
 }  // namespace dzo
 
-static inline int tune_env(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
 typedef void (*batch_kernel_fn)(dzo::BatchState, int, int);
 static batch_kernel_fn batch_kernel_of(int32_t dtype, int rp, int wide) {
     using namespace dzo;
@@ -676,7 +675,7 @@ static int32_t batch_create_impl(const BatchObjective &ob, int64_t batch, int64_
     if (b->st.ob.kind == DZO_PROBLEM_ROSENBROCK2D) b->st.ob.kind = DZO_PROBLEM_ROSENBROCK_CHAIN;   // n = 2: the same function
     b->st.batch = batch; b->st.n = n;
     b->rp = n <= 256 ? 1 : (n <= 512 ? 2 : 4);
-    b->wide = (b->rp == 2 && n > tune_env("DZO_TUNE_BATCH_RP2_WIDE_ABOVE", 448)) ? 1 : 0;
+    b->wide = (b->rp == 2 && n > tune_int("DZO_TUNE_BATCH_RP2_WIDE_ABOVE", 448)) ? 1 : 0;
     const size_t es = dtype_size(dtype);
     const size_t np = (size_t)((n + 1) & ~(int64_t)1);
     b->lds_bytes = 9 * np * es + (5 * np + 16) * sizeof(double) + 16;
@@ -816,7 +815,7 @@ int32_t dzo_bfgs_batch_step(dzo_bfgs_batch_t b, int32_t steps, int32_t *all_done
         DZO_TIMED("bfgs_batch_step", b->stream);
         const dim3 grid((unsigned)b->st.batch), block(kBlock);
         hipLaunchKernelGGL(batch_kernel_of(b->dtype, b->rp, b->wide), grid, block, b->lds_bytes, b->stream, b->st, (int)steps,
-                           getenv("DZO_TUNE_BATCH_DEBUG") ? atoi(getenv("DZO_TUNE_BATCH_DEBUG")) : 0);
+                           tune_int("DZO_TUNE_BATCH_DEBUG", 0));
     }
     DZO_HIP(hipGetLastError());
     if (all_done) {

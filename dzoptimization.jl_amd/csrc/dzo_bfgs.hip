@@ -32,7 +32,7 @@ constexpr int kColsPerBlock = 4;     // default column group per block (symv / u
 
 static int bfgs_cols_knob() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("DZO_TUNE_BFGS_COLS"); v = e ? atoi(e) : kColsPerBlock; if (v != 8 && v != 16) v = 4; }
+    if (v < 0) { v = tune_int("DZO_TUNE_BFGS_COLS", kColsPerBlock); if (v != 8 && v != 16) v = 4; }
     return v;
 }
 
@@ -787,7 +787,7 @@ static int32_t bfgs_phi_at_scratch(dzo_bfgs_s *o, double *f, bool *feasible) {
 // `fused_ok` false: this objective / these options have no such path and nothing was done.
 static int32_t bfgs_phi_fused(dzo_bfgs_s *o, const void *dir, double t, const void *ref, double *f, bool *changed,
                               bool *nonzero, bool *equal_ref, bool *fused_ok) {
-    const bool fast = getenv("DZO_TUNE_BFGS_PHI_FUSED") ? atoi(getenv("DZO_TUNE_BFGS_PHI_FUSED")) != 0 : true;
+    const bool fast = tune_int("DZO_TUNE_BFGS_PHI_FUSED", 1) != 0;
     *fused_ok = fast && !o->objective && !o->constraint && o->problem &&
                 problem_phi_async(o->problem, o->stream, o->x, dir, round_to_dtype(o->dtype, o->sign * t), o->scratch,
                                   o->phi_flags(), o->host_dev, ref);
@@ -906,7 +906,7 @@ static int32_t bfgs_search_result(dzo_bfgs_s *o, const PhiBuffers &B, const PhiM
 // was evaluated)
 static int32_t bfgs_dual_search(dzo_bfgs_s *o, const void *dir_a, double t0_a, const void *dir_b, double t0_b,
                                 double *t_a, double *f_a, double *t_b, double *f_b, bool *done) {
-    const bool enabled = getenv("DZO_TUNE_BFGS_DUAL_SEARCH") ? atoi(getenv("DZO_TUNE_BFGS_DUAL_SEARCH")) != 0 : true;
+    const bool enabled = tune_int("DZO_TUNE_BFGS_DUAL_SEARCH", 1) != 0;
     *done = false;
     if (!enabled || o->objective || o->constraint || !o->problem || o->problem->kind != DZO_PROBLEM_QUADRATIC ||
         o->problem->l2 != 0.0 || o->problem->cons_on)
@@ -1126,15 +1126,15 @@ __global__ __launch_bounds__(kBlock) void finish_phi6_advance_kernel(const doubl
 }
 
 static int dev_search_rounds() {
-    const int r = getenv("DZO_TUNE_BFGS_DEV_ROUNDS") ? atoi(getenv("DZO_TUNE_BFGS_DEV_ROUNDS")) : 2;
+    const int r = tune_int("DZO_TUNE_BFGS_DEV_ROUNDS", 2);
     return r < 1 ? 1 : (r > 8 ? 8 : r);
 }
 
 // norms + both searches, one host wait.  *done = false: not applicable (nothing was enqueued).
 static int32_t bfgs_dev_search(dzo_bfgs_s *o, double step_length, double *grad_norm, double *bfgs_norm_v, double *t_a, double *f_a,
                                double *t_b, double *f_b, bool *done) {
-    const bool enabled = getenv("DZO_TUNE_BFGS_DEV_SEARCH") ? atoi(getenv("DZO_TUNE_BFGS_DEV_SEARCH")) != 0 : true;      // (read per call: tests switch it)
-    const bool dual = getenv("DZO_TUNE_BFGS_DUAL_SEARCH") ? atoi(getenv("DZO_TUNE_BFGS_DUAL_SEARCH")) != 0 : true;
+    const bool enabled = tune_int("DZO_TUNE_BFGS_DEV_SEARCH", 1) != 0;      // (read per call: tests switch it)
+    const bool dual = tune_int("DZO_TUNE_BFGS_DUAL_SEARCH", 1) != 0;
     *done = false;
     if (!enabled || !dual || !o->dsearch || o->objective || o->constraint || !o->problem || o->problem->kind != DZO_PROBLEM_QUADRATIC ||
         o->problem->l2 != 0.0 || o->problem->cons_on || o->n > 65536 || o->problem->scratch_doubles < 6 * o->n)
@@ -1325,8 +1325,8 @@ static int32_t bfgs_alloc(dzo_bfgs_s *o) {
         // Infinity Cache) update + direction 68 us against 78 us for the full-storage kernels, the step rate
         // the same; n = 8192 (512 MiB, HBM) 196 us against 332 us, step! 1446 against 1218 per second.
         // Below that size the two extra launches cost more than the halved traffic saves.
-        const char *e = getenv("DZO_TUNE_BFGS_TRI_MIN_N");
-        const bool big = e ? o->n >= atoll(e) : (size_t)o->n * (size_t)o->n * es >= (128u << 20);
+        const int min_n = tune_int("DZO_TUNE_BFGS_TRI_MIN_N", INT_MIN);
+        const bool big = min_n != INT_MIN ? o->n >= min_n : (size_t)o->n * (size_t)o->n * es >= (128u << 20);
         o->tri = !o->no_hessian && o->n % 2 == 0 && big && o->n < 65535LL * kTriCW;
         if (o->tri) {
             const size_t nw = (size_t)((o->n + kTriCW - 1) / kTriCW), npn = (size_t)((o->n + kTriPH - 1) / kTriPH);

@@ -11,8 +11,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -50,6 +52,12 @@ int32_t hip_fail(hipError_t e, const char *what, const char *file, int line);
             return (code);                   \
         }                                    \
     } while (0)
+
+// The one reader of the DZO_TUNE_* variables (dev only; the defaults are the product; DESIGN.md lists them).
+static inline int tune_int(const char *name, int dflt) {
+    const char *v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 
 // ------------------------------------------------------------------------------ context
 struct Context {

@@ -51,7 +51,7 @@ DeviceScope::~DeviceScope() {
 }
 
 int32_t wait_ticket(hipStream_t s, const double *word, double ticket) {
-    static const bool poll = getenv("DZO_TUNE_POLL") ? atoi(getenv("DZO_TUNE_POLL")) != 0 : true;
+    static const bool poll = tune_int("DZO_TUNE_POLL", 1) != 0;
     if (!poll) { DZO_HIP(hipStreamSynchronize(s)); return DZO_OK; }
     volatile const double *h = word;
     for (uint64_t spins = 1;; ++spins) {

@@ -50,7 +50,6 @@ struct dzo_lbfgs_s {
     int32_t newest = 0;             // slot of pair 0
     int64_t stride = 0;             // elements between slots
     void *S = nullptr, *Y = nullptr;
-    bool interleaved = true;
     void *d = nullptr;              // :337 step_direction
     int32_t mode = DZO_TWOLOOP_GRAM;
     int32_t n_alpha = 0;            // length(alpha_history) (:498-500)
@@ -70,9 +69,6 @@ struct dzo_lbfgs_s {
     int gram_grid = 0;
     bool speculate = true;          // enqueue the accepted-step tail before the host sees the decision
     unsigned int *gram_ticket = nullptr;   // (base of the scalar block)
-    int gram_variant = 1;           // 1 = lane-distributed accumulators
-    int gram_peel = 1;              // predicate-free path for full tiles
-    int gram_fresh_plain = 1, gram_skip0 = 1, combine_fresh_plain = 1;
     bool rho_pending = false;       // rho partials of the newest pair await their final sum
     int tail_grid = 0;              // grid of the last speculative tail (its partial count)
     int rho_pending_count = 0, rho_pending_slot = 0;
@@ -103,15 +99,13 @@ struct dzo_lbfgs_s {
     std::recursive_mutex mu;        // a step vs a settle coming from another host thread (recursive: a callback may call a getter)
     int64_t single_pass_steps = 0, single_pass_rejections = 0, single_pass_retries = 0;
     bool fused_post = true;         // use the problem's fused accept+gradient+delta kernel when it has one
-    bool combine_nts = true;        // non-temporal stores for d in the combine pass
-    int gram_u = 4, combine_u = 4, combine_blocks_per_cu = 0, gram_bpc = 0;   // tuning knobs (DZO_TUNE_* env, dev only)
 
     int device = 0;                 // the GPU this optimizer lives on
     int32_t nslots = 0;             // ring slots: m + 1 (pairs + the spare); m + 2 for a blocked ring (it may hold m + 1 POINTS + the spare)
     int slot_of(int i) const { return ((newest - i) % nslots + nslots) % nslots; }
     int spare() const { return (newest + 1) % nslots; }
-    // layout 1 (default): ONE slab, slots interleaved s_0 y_0 s_1 y_1 ... (Y = S + stride, pair
-    // stride 2*stride): consecutive streams sit an odd number of KiB apart.  layout 0: two slabs.
+    // slabs: ONE slab, slots alternating s_0 y_0 s_1 y_1 ... (Y = S + stride, pair stride 2*stride):
+    // consecutive streams sit an odd number of KiB apart
     int64_t pair_stride = 0;        // elements between consecutive slots of the same history
     // layout 2 (blocked, see "blocked history ring"): S is the ring, a slot's s / y stream starts at tile
     // 2*slot / 2*slot + 1 of row 0, consecutive rows are rowbytes apart.  delta_point / delta_gradient are
@@ -166,9 +160,7 @@ struct dzo_lbfgs_s {
     // step_direction is not written by the passes (nothing on the point ring reads it: every trial recomputes it in
     // registers): it is formed when somebody asks, by one more pass over the view of the ring the step started from
     const void *stage_kern = nullptr; size_t stage_bytes = 0; bool stage_small = false;   // dynamic-LDS attribute of the point pass
-    bool lazy_d = true;             // DZO_TUNE_LAZY_D
     bool fused_finish = false;      // DZO_TUNE_FUSED_FINISH: reduce + finish of a Gram pass in one launch when the partials are few (measured slower)
-    int64_t fused_finish_max = 65536;   // DZO_TUNE_FUSED_FINISH_MAX: ... at most this many partial sums
     int point_sets = 1;             // DZO_TUNE_POINT_SETS: register sets per wave of the point pass (1: two waves per SIMD; the default where it fits)
     bool d_stale = false;
     int dview_k = 0, dview_newest = 0;
@@ -370,8 +362,6 @@ template <typename T> struct GramParams {
     const T *sp;                // pivot pair (the pair whose Gram row/column is (re)computed)
     const T *yp;
     int k;
-    int peel;                   // 1: full tiles run the predicate-free path
-    int fresh_plain;            // 1: g / pivot pair (written by the previous kernel) with plain loads
     int pivot_first;            // 1: pivot == logical pair 0 -> pair 0 is served from the pivot registers
     const T *s[kMaxHistory];    // logical pair -> slot base (wave-uniform index -> scalar loads)
     const T *y[kMaxHistory];
@@ -615,6 +605,7 @@ __global__ __launch_bounds__(kBlock) void gram_finish_kernel(GramFinishParams p)
 // the launches were never the cost: round 2's 70.8 us per direction were 8 HIP event records per direction in the timed
 // loop (the bench now times without events and takes the per-kernel numbers from a second, untimed stretch).
 constexpr int kFusedFinishThreads = 1024;
+constexpr int64_t kFusedFinishMax = 65536;      // ... at most this many partial sums
 __global__ __launch_bounds__(kFusedFinishThreads) void gram_reduce_finish_kernel(GramFinishParams p, const double *__restrict__ partials, int grid,
                                                                                  double *__restrict__ vals_out, int nvals,
                                                                                  const double *__restrict__ rho_partials, int rho_count,
@@ -721,15 +712,10 @@ __global__ __launch_bounds__(kBlock) void gram_pass_lanes_kernel(GramParams<T> p
                 }
             } else
             if (ok[u]) {
-                if (p.fresh_plain) {
-                    L::load(p.g + vi * N, gv[u]);
-                    L::load(hist_ptr<BLK>(sp, vi, p.rowbytes), spv[u]);
-                    L::load(hist_ptr<BLK>(yp, vi, p.rowbytes), ypv[u]);
-                } else {
-                    L::load_nt(p.g + vi * N, gv[u]);
-                    L::load_nt(hist_ptr<BLK>(sp, vi, p.rowbytes), spv[u]);
-                    L::load_nt(hist_ptr<BLK>(yp, vi, p.rowbytes), ypv[u]);
-                }
+                // g and the pivot pair were written by the previous kernel: plain loads
+                L::load(p.g + vi * N, gv[u]);
+                L::load(hist_ptr<BLK>(sp, vi, p.rowbytes), spv[u]);
+                L::load(hist_ptr<BLK>(yp, vi, p.rowbytes), ypv[u]);
             } else {
 #pragma unroll
                 for (int j = 0; j < N; ++j) { gv[u][j] = 0; spv[u][j] = 0; ypv[u][j] = 0; }
@@ -817,8 +803,7 @@ __global__ __launch_bounds__(kBlock) void gram_pass_lanes_kernel(GramParams<T> p
     // of the last ones -- a SIMD serves the oldest of its waves first -- and are done at 283 us against 514 us.  A priority
     // that falls with a block's progress evens that out, 491 ... 528 us, and the kernel takes exactly as long, 550 us: the
     // pass is bound by the memory system, which does not care whose requests it serves.  Not kept.)
-    if (p.peel) { for (int64_t tile = blockIdx.x; tile < full_tiles; tile += gridDim.x) do_tile(tile * tile_v, std::true_type{}); }
-    else { for (int64_t tile = blockIdx.x; tile < full_tiles; tile += gridDim.x) do_tile(tile * tile_v, std::false_type{}); }
+    for (int64_t tile = blockIdx.x; tile < full_tiles; tile += gridDim.x) do_tile(tile * tile_v, std::true_type{});
     (void)nthreads;
     // scalar tail (n not a multiple of the vector width): lane i of wave 0 in block 0 owns pair i
     if constexpr (POST) {
@@ -863,7 +848,6 @@ template <typename T> struct CombineParams {
     const T *g;
     T *d;
     int k;
-    int fresh_plain;            // 1: newest pair (written by the previous step's tail) with plain loads
     const double *alpha, *coef, *scale;
     const T *s[kMaxHistory];    // logical pair -> slot base
     const T *y[kMaxHistory];
@@ -876,7 +860,7 @@ template <typename T> struct CombineParams {
 // The 2k coefficients are staged once per block in LDS (wave-uniform broadcast reads), the
 // slot pointers come from the kernel-argument segment (scalar loads), and the history is
 // streamed with non-temporal 16-B loads, UI of them in flight per stream step.
-template <typename T, bool VEC, int U, bool NTS, bool BLK = false>
+template <typename T, bool VEC, int U, bool BLK = false>
 __global__ __launch_bounds__(kBlock) void combine_kernel(CombineParams<T> p) {
     using L = Ld<T, VEC>;
     constexpr int N = L::N;
@@ -908,7 +892,7 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(CombineParams<T> p) {
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (ok[u]) {
-                    if (p.fresh_plain && i == 0) L::load(hist_ptr<BLK>(yi, base + (int64_t)u * kBlock + threadIdx.x, p.rowbytes), v[u]);
+                    if (i == 0) L::load(hist_ptr<BLK>(yi, base + (int64_t)u * kBlock + threadIdx.x, p.rowbytes), v[u]);
                     else L::load_nt(hist_ptr<BLK>(yi, base + (int64_t)u * kBlock + threadIdx.x, p.rowbytes), v[u]);
                 }
 #pragma unroll
@@ -930,7 +914,7 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(CombineParams<T> p) {
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (ok[u]) {
-                    if (p.fresh_plain && i == 0) L::load(hist_ptr<BLK>(si, base + (int64_t)u * kBlock + threadIdx.x, p.rowbytes), v[u]);
+                    if (i == 0) L::load(hist_ptr<BLK>(si, base + (int64_t)u * kBlock + threadIdx.x, p.rowbytes), v[u]);
                     else L::load_nt(hist_ptr<BLK>(si, base + (int64_t)u * kBlock + threadIdx.x, p.rowbytes), v[u]);
                 }
 #pragma unroll
@@ -942,7 +926,7 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(CombineParams<T> p) {
         for (int u = 0; u < U; ++u)
             if (ok[u]) {
                 T *dst = p.d + (base + (int64_t)u * kBlock + threadIdx.x) * N;
-                if constexpr (NTS) L::store_nt(dst, q[u]); else L::store(dst, q[u]);
+                if constexpr (VEC) L::store_nt(dst, q[u]); else L::store(dst, q[u]);
             }
     }
     if constexpr (VEC) {
@@ -2353,11 +2337,6 @@ static int resident_blocks(const void *kernel, size_t dyn_lds = 0) {
     return nb;
 }
 
-static int tune(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 static GramFinishParams gram_finish_params(dzo_lbfgs_s *o, int pivot, bool recurrence, const double *vals, bool rho_from_vals,
                                            const int32_t *gate) {
     GramFinishParams fp;
@@ -2368,7 +2347,7 @@ static GramFinishParams gram_finish_params(dzo_lbfgs_s *o, int pivot, bool recur
     fp.Gyy = o->Gyy; fp.Gsy = o->Gsy; fp.sg = o->sg; fp.yg = o->yg;
     fp.alpha = o->alpha; fp.coef = o->coef; fp.scale = o->scale;
     if (gate) { fp.alpha = o->alpha_sp; fp.coef = o->coef_sp; fp.scale = o->scale_sp; }   // next step's set
-    fp.fast_div = tune("DZO_TUNE_FAST_DIV", 1) != 0 ? 1 : 0;
+    fp.fast_div = tune_int("DZO_TUNE_FAST_DIV", 1) != 0 ? 1 : 0;
     return fp;
 }
 
@@ -2395,82 +2374,77 @@ template <typename T> static int32_t gram_pass(dzo_lbfgs_s *o, int pivot, bool r
     for (int i = 0; i < k; ++i) { gp.s[i] = o->s_slot<T>(o->slot_of(i)); gp.y[i] = o->y_slot<T>(o->slot_of(i)); }
     gp.partials = o->gram_partials;
     gp.rowbytes = o->rowbytes;
-    gp.debug = tune("DZO_TUNE_TP_DEBUG", 0) == 1;
-    gp.peel = o->gram_peel;
-    gp.fresh_plain = o->gram_fresh_plain;
-    gp.pivot_first = (o->gram_skip0 && pivot == 0) ? 1 : 0;
+    gp.debug = tune_int("DZO_TUNE_TP_DEBUG", 0) == 1;
+    gp.pivot_first = pivot == 0 ? 1 : 0;
     const bool post = o->post_pending;                    // (lbfgs_direction made sure: pivot 0, slabs, aligned operands, pivot served from registers)
     if (post) {
         gp.x = (const T *)c.x; gp.g_old = (const T *)o->post_g_old;
         gp.sp_out = o->s_slot<T>(o->slot_of(0)); gp.yp_out = o->y_slot<T>(o->slot_of(0));
     }
     const bool vec = al16(c.g);
-    if (o->gram_variant == 1) {
-        // lane-distributed accumulators: one launch shape for every k (the pair-per-wave
-        // variant, 5*ceil(k/4) accumulators per lane and 8 concurrent streams per block, measured
-        // 5 % slower at k = 20 and was removed)
-        // vectors per thread: as many as still leave >= 4 blocks per CU (small n would otherwise
-        // launch fewer blocks than there are CUs)
-        int gu = o->gram_u;
-        const int64_t vec_elems = (int64_t)kBlock * (vec ? Vec16<T>::N : 1);
-        while (gu > 1 && (c.n + vec_elems * gu - 1) / (vec_elems * gu) < (int64_t)ctx().cus * 4) gu >>= 1;
-        int64_t per_block = vec_elems * gu;
-        int64_t blocks = (c.n + per_block - 1) / per_block;
-        // grid = the blocks that are resident at once (occupancy x CUs): every block then walks
-        // the same number of tiles (+-1) and there is no second, partially filled round of
-        // blocks.  Measured at n = 1e7, k = 20: 494 us against 527 us with 8 blocks per CU.
-        double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
+    // lane-distributed accumulators: one launch shape for every k (the pair-per-wave
+    // variant, 5*ceil(k/4) accumulators per lane and 8 concurrent streams per block, measured
+    // 5 % slower at k = 20 and was removed)
+    // vectors per thread: as many as still leave >= 4 blocks per CU (small n would otherwise
+    // launch fewer blocks than there are CUs)
+    int gu = kStreamU;
+    const int64_t vec_elems = (int64_t)kBlock * (vec ? Vec16<T>::N : 1);
+    while (gu > 1 && (c.n + vec_elems * gu - 1) / (vec_elems * gu) < (int64_t)ctx().cus * 4) gu >>= 1;
+    int64_t per_block = vec_elems * gu;
+    int64_t blocks = (c.n + per_block - 1) / per_block;
+    // grid = the blocks that are resident at once (occupancy x CUs): every block then walks
+    // the same number of tiles (+-1) and there is no second, partially filled round of
+    // blocks.  Measured at n = 1e7, k = 20: 494 us against 527 us with 8 blocks per CU.
+    double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
 #define GL(UU)                                                                                                  \
     do {                                                                                                        \
         auto kern = o->blocked ? gram_pass_lanes_kernel<T, true, UU, true>                                      \
                     : post ? gram_pass_lanes_kernel<T, true, UU, false, true>                                   \
                     : vec ? gram_pass_lanes_kernel<T, true, UU> : gram_pass_lanes_kernel<T, false, UU>;         \
         int64_t cap = o->gram_grid;                                                                             \
-        if (o->gram_bpc <= 0) { const int64_t res = (int64_t)ctx().cus * resident_blocks((const void *)kern); if (res < cap) cap = res; } \
+        const int64_t res = (int64_t)ctx().cus * resident_blocks((const void *)kern);                           \
+        if (res < cap) cap = res;                                                                               \
         if (blocks > cap) blocks = cap;                                                                         \
         lgrid = (int)(blocks < 1 ? 1 : blocks);                                                                 \
         DZO_TIMED("lbfgs_gram_pass", s);                                                                        \
         hipLaunchKernelGGL(kern, dim3(lgrid), dim3(kBlock), 0, s, gp);                                          \
     } while (0)
-        int lgrid = 1;
-        if (gu == 1) GL(1); else if (gu == 2) GL(2); else GL(4);      // (8 vectors per lane spills: not offered)
+    int lgrid = 1;
+    if (gu == 1) GL(1); else if (gu == 2) GL(2); else GL(4);      // (8 vectors per lane spills: not offered)
 #undef GL
-        const int pcount = lgrid;
-        const int nvals = kGramValues * k;
-        const bool rho = o->rho_pending;
-        if (post) {                                       // rho of the new pair is value 4 of pair 0 (s_p . y_p): gram_finish takes it from there
-            o->post_pending = false;
-            {
-                DZO_TIMED("lbfgs_gram_reduce", s);
-                hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals), dim3(kBlock), 0, s, o->gram_partials, pcount, vals, nvals, (const double *)nullptr, 0,
-                                   (double *)nullptr, 0);
-            }
-            return gram_finish_launch(o, pivot, recurrence, vals, true);
-        }
-        if (o->fused_finish && (int64_t)nvals * pcount <= o->fused_finish_max) {
-            // small problem: the scalar stage in one launch (see gram_reduce_finish_kernel)
-            const GramFinishParams fp = gram_finish_params(o, pivot, recurrence, vals, false, nullptr);
-            {
-                DZO_TIMED("lbfgs_gram_reduce_finish", s);
-                hipLaunchKernelGGL(gram_reduce_finish_kernel, dim3(1), dim3(kFusedFinishThreads), gram_finish_lds_bytes(k), s, fp,
-                                   (const double *)o->gram_partials, pcount, vals, nvals, (const double *)c.partials(),
-                                   rho ? o->rho_pending_count : 0, o->rho + o->rho_pending_slot, c.dtype == DZO_F32 ? 1 : 0);
-            }
-            o->rho_pending = false;
-            DZO_HIP(hipGetLastError());
-            return DZO_OK;
-        }
+    const int pcount = lgrid;
+    const int nvals = kGramValues * k;
+    const bool rho = o->rho_pending;
+    if (post) {                                       // rho of the new pair is value 4 of pair 0 (s_p . y_p): gram_finish takes it from there
+        o->post_pending = false;
         {
             DZO_TIMED("lbfgs_gram_reduce", s);
-            hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals + (rho ? 1 : 0)), dim3(kBlock), 0, s, o->gram_partials, pcount,
-                               vals, nvals, (const double *)c.partials(), o->rho_pending_count, o->rho + o->rho_pending_slot,
-                               c.dtype == DZO_F32 ? 1 : 0);
-            o->rho_pending = false;
+            hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals), dim3(kBlock), 0, s, o->gram_partials, pcount, vals, nvals, (const double *)nullptr, 0,
+                               (double *)nullptr, 0);
         }
-        return gram_finish_launch(o, pivot, recurrence, vals);
+        return gram_finish_launch(o, pivot, recurrence, vals, true);
     }
-    set_error("unknown Gram variant");
-    return DZO_ERR_INVALID;
+    if (o->fused_finish && (int64_t)nvals * pcount <= kFusedFinishMax) {
+        // small problem: the scalar stage in one launch (see gram_reduce_finish_kernel)
+        const GramFinishParams fp = gram_finish_params(o, pivot, recurrence, vals, false, nullptr);
+        {
+            DZO_TIMED("lbfgs_gram_reduce_finish", s);
+            hipLaunchKernelGGL(gram_reduce_finish_kernel, dim3(1), dim3(kFusedFinishThreads), gram_finish_lds_bytes(k), s, fp,
+                               (const double *)o->gram_partials, pcount, vals, nvals, (const double *)c.partials(),
+                               rho ? o->rho_pending_count : 0, o->rho + o->rho_pending_slot, c.dtype == DZO_F32 ? 1 : 0);
+        }
+        o->rho_pending = false;
+        DZO_HIP(hipGetLastError());
+        return DZO_OK;
+    }
+    {
+        DZO_TIMED("lbfgs_gram_reduce", s);
+        hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals + (rho ? 1 : 0)), dim3(kBlock), 0, s, o->gram_partials, pcount,
+                           vals, nvals, (const double *)c.partials(), o->rho_pending_count, o->rho + o->rho_pending_slot,
+                           c.dtype == DZO_F32 ? 1 : 0);
+        o->rho_pending = false;
+    }
+    return gram_finish_launch(o, pivot, recurrence, vals);
 }
 
 // alpha / coef / scale of the current history and gradient: from the dots the last single-pass step
@@ -2520,10 +2494,9 @@ template <typename T> static int32_t direction_gram(dzo_lbfgs_s *o) {
     for (int i = 0; i < k; ++i) { cp.s[i] = o->s_slot<T>(o->slot_of(i)); cp.y[i] = o->y_slot<T>(o->slot_of(i)); }
     cp.alpha = o->alpha; cp.coef = o->coef; cp.scale = o->scale;
     cp.rowbytes = o->rowbytes;
-    cp.debug = tune("DZO_TUNE_TP_DEBUG", 0) == 2;
-    cp.fresh_plain = o->combine_fresh_plain;
+    cp.debug = tune_int("DZO_TUNE_TP_DEBUG", 0) == 2;
     const bool vec = al16(c.g);
-    int u = o->combine_u;
+    int u = kStreamU;
     while (u > 1 && (c.n + (int64_t)kBlock * (vec ? Vec16<T>::N : 1) * u - 1) / ((int64_t)kBlock * (vec ? Vec16<T>::N : 1) * u) < (int64_t)ctx().cus * 4) u >>= 1;
     int64_t per_block = (int64_t)kBlock * (vec ? Vec16<T>::N : 1) * u;
     int64_t blocks = (c.n + per_block - 1) / per_block;
@@ -2531,11 +2504,9 @@ template <typename T> static int32_t direction_gram(dzo_lbfgs_s *o) {
         DZO_TIMED("lbfgs_combine", s);
 #define CB(UU)                                                                                                   \
     do {                                                                                                         \
-        auto kern = o->blocked ? combine_kernel<T, true, UU, true, true>                                         \
-                    : (vec && o->combine_nts) ? combine_kernel<T, true, UU, true>                                \
-                    : vec ? combine_kernel<T, true, UU, false> : combine_kernel<T, false, UU, false>;            \
-        const int bpc = o->combine_blocks_per_cu > 0 ? o->combine_blocks_per_cu : resident_blocks((const void *)kern); \
-        const int64_t cap = (int64_t)ctx().cus * bpc;                                                            \
+        auto kern = o->blocked ? combine_kernel<T, true, UU, true>                                               \
+                    : vec ? combine_kernel<T, true, UU> : combine_kernel<T, false, UU>;                          \
+        const int64_t cap = (int64_t)ctx().cus * resident_blocks((const void *)kern);                            \
         if (blocks > cap) blocks = cap;                                                                          \
         hipLaunchKernelGGL(kern, dim3((int)(blocks < 1 ? 1 : blocks)), dim3(kBlock), 0, s, cp);                 \
     } while (0)
@@ -2578,8 +2549,8 @@ static int32_t lbfgs_flush_post(dzo_lbfgs_s *o) {
 static int32_t lbfgs_direction(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
     // the deferred tail rides in the Gram pass only in its plain form: GRAM mode, one pass with pivot 0 served from registers
-    if (o->post_pending && (o->mode != DZO_TWOLOOP_GRAM || o->k == 0 || o->blocked || o->gram_rebuild || o->gram_stale > 1 || !o->gram_skip0 ||
-                            o->gram_variant != 1 || o->spec_scalars || o->scalars_ready || o->gram_ready ||
+    if (o->post_pending && (o->mode != DZO_TWOLOOP_GRAM || o->k == 0 || o->blocked || o->gram_rebuild || o->gram_stale > 1 ||
+                            o->spec_scalars || o->scalars_ready || o->gram_ready ||
                             !(al16(c.x) && al16(c.g) && al16(o->post_g_old) && al16(o->s_slot_v(o->newest)) && al16(o->y_slot_v(o->newest)))))
         DZO_TRY(lbfgs_flush_post(o));
     if (o->k == 0) {                                      // :438 then the :443 guard
@@ -2829,7 +2800,7 @@ static int32_t lbfgs_unblock(dzo_lbfgs_s *o) {
     DZO_HIP(hipMemcpyAsync((char *)Yb + (size_t)sp * ps * es, o->dg_lin, (size_t)c.n * es, hipMemcpyDeviceToDevice, c.stream));
     DZO_HIP(hipStreamSynchronize(c.stream));
     (void)hipFree(o->S);
-    o->S = ring; o->Y = Yb; o->interleaved = true; o->pair_stride = ps;
+    o->S = ring; o->Y = Yb; o->pair_stride = ps;
     o->blocked = false;
     // (after a push delta_point / delta_gradient are the newest pair; before the first step the zero-filled spare)
     if (c.iteration_count > 0 && o->k > 0) { c.dx = o->s_slot_v(o->newest); c.dg = o->y_slot_v(o->newest); }
@@ -3017,7 +2988,7 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
     // General path (callbacks, any objective without a fused tail): the accepted step's tail as ONE pass
     // (accept_delta_rho_kernel) with the gradient callback writing into the other gradient buffer -- no axpby, no copy of
     // g_old (DZO_TUNE_GENERIC_POST=0: the separate kernels, :145 / :478 / :480 / :505 one launch each)
-    const bool one_pass_tail = !fused && tune("DZO_TUNE_GENERIC_POST", 1) != 0 && lbfgs_ensure_twins(o);
+    const bool one_pass_tail = !fused && tune_int("DZO_TUNE_GENERIC_POST", 1) != 0 && lbfgs_ensure_twins(o);
     c.defer_delta = fused || one_pass_tail;
     c.speculative_tail = (fused && o->speculate) ? lbfgs_speculative_tail : nullptr;
     c.speculative_self = o;
@@ -3054,7 +3025,7 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
         int32_t rcg = core_gradient(c);
         if (rcg != DZO_OK) { c.g = g_old; return rcg; }
         o->g_twin = g_old;
-        if (!o->blocked && o->mode == DZO_TWOLOOP_GRAM && !safeguards && tune("DZO_TUNE_GENERIC_POST", 1) >= 2) {
+        if (!o->blocked && o->mode == DZO_TWOLOOP_GRAM && !safeguards && tune_int("DZO_TUNE_GENERIC_POST", 1) >= 2) {
             // deferred: the next step's Gram pass forms the pair on its way (gram_pass_lanes_kernel<POST>); the getters and
             // everything else that needs it earlier call lbfgs_flush_post
             lbfgs_mark_unsettled(o);
@@ -3209,7 +3180,7 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     fp.gram_partials = o->gram_partials;
     fp.obj_partials = c.problem->scratch;
     fp.changed = c.flag();
-    fp.debug_skip = tune("DZO_TUNE_SP_DEBUG", 0);
+    fp.debug_skip = tune_int("DZO_TUNE_SP_DEBUG", 0);
     // register footprint follows the history length: pick the smallest instantiation that holds m pairs
     const int pass_k = pair_pass_k(o->m);
     void (*kern)(FusedParams<T>) = pass_k == 8 ? lbfgs_single_pass_kernel<T, 8>
@@ -3222,7 +3193,6 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     // The pass runs at t = 1 and, when that trial is rejected while the objective at t/2 (which rode along) is a
     // decrease, once more at t = 1/2 -- the loop of take_backtracking_step! (:121-152) on the same kernel, x and g
     // untouched in between.  Deeper halvings continue on the cheap trial kernels.
-    const bool retry_pass = tune("DZO_TUNE_SP_RETRY", 1) != 0;
     DZO_REQUIRE(fused_params_ok<T>(fp, true), DZO_ERR_STATE, "single-pass step: a null operand (ring %p, x %p, g %p, twins %p %p, d %p)",
                 (void *)fp.ring, (const void *)fp.x, (const void *)fp.g, (void *)fp.x_out, (void *)fp.g_out, (void *)fp.d);
     double t = 1.0;
@@ -3288,15 +3258,15 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     // rejected: x and g are untouched
     if (attempt == 0) o->single_pass_rejections += 1;
     const double f_half = round_to_dtype(c.dtype, c.host[1]);
-    if (attempt == 0 && retry_pass && f_half < c.f) {     // :152, and the trial at t/2 will pass :139
+    if (attempt == 0 && f_half < c.f) {     // :152, and the trial at t/2 will pass :139
         t = round_to_dtype(c.dtype, t * 0.5);
         o->single_pass_retries += 1;
         continue;
     }
     // the reference's loop continues on the two-pass kernels (whose first trial saves x_old in delta_point, :118):
     // after this trial, and after the one at t/2 as well when its objective is already known to be no decrease
-    if (attempt == 0 && retry_pass) { c.last_trials += 1; return lbfgs_search_and_post(o, 2); }
-    return lbfgs_search_and_post(o, attempt + 1);
+    if (attempt == 0) c.last_trials += 1;
+    return lbfgs_search_and_post(o, 2);
     }
 }
 
@@ -3413,16 +3383,16 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
     fp.gram_partials = o->gram_partials;
     fp.obj_partials = c.problem->scratch;
     fp.changed = c.flag();
-    fp.debug_skip = tune("DZO_TUNE_SP_DEBUG", 0);
+    fp.debug_skip = tune_int("DZO_TUNE_SP_DEBUG", 0);
     fp.dec = point_decor<T>(o->ring_dec);
     fp.obj_lambda = (T)o->ring_obj_lambda;
-    fp.store_d = o->lazy_d ? 0 : 1;
-    // the launch shape (dzo_lbfgs_plan.h); its knobs are read per step
-    const PointLaunch pl = point_pass_launch(c.n, c.dtype, o->m, k, o->point_sets, DZO_PP_REGRAD != 0, tune("DZO_TUNE_POINT_STAGE_ROWS", 16),
-                                             tune("DZO_TUNE_POINT_PRIO", 1), tune("DZO_TUNE_POINT_PLAIN_MB", point_plain_mb_default(o->tile_stride)));
+    fp.store_d = 0;                                       // (step_direction is formed on demand: lbfgs_materialize_d)
+    // the launch shape (dzo_lbfgs_plan.h); its knob is read per step
+    const PointLaunch pl = point_pass_launch(c.n, c.dtype, o->m, k, o->point_sets, DZO_PP_REGRAD != 0, kPointStageRows,
+                                             tune_int("DZO_TUNE_POINT_PRIO", 1), point_plain_mb_default(o->tile_stride));
     fp.nt_tiles = pl.nt_tiles;
     fp.prio = pl.prio;
-    fp.leftover_even = tune("DZO_TUNE_POINT_LEFTOVER_EVEN", 1) != 0 ? 1 : 0;
+    fp.leftover_even = 1;
     fp.stage_rows = pl.stage_rows;
     size_t stage_bytes = pl.stage_bytes;
     if (o->stage_kern != (const void *)kern || o->stage_bytes != stage_bytes) {   // (once per kernel and size)
@@ -3445,7 +3415,7 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
                 (void *)fp.ring, (void *)fp.d, (const void *)fp.alpha, (const void *)fp.coef, (const void *)fp.scale);
     o->d_stale = false;                                   // (whatever was pending belonged to the previous step)
     const int view_k = k, view_newest = o->newest;
-    auto direction_pending = [&]() { if (k > 0 && o->lazy_d) { o->d_stale = true; o->dview_k = view_k; o->dview_newest = view_newest; } };
+    auto direction_pending = [&]() { if (k > 0) { o->d_stale = true; o->dview_k = view_k; o->dview_newest = view_newest; } };
     c.last_trials = 0;
     o->single_pass_steps += 1;
     int64_t halvings = 0;
@@ -3612,12 +3582,12 @@ template <typename T> static int32_t lbfgs_step_points_lse(dzo_lbfgs_s *o) {
     LseParams<T> lp;
     lse_fill_params<T>(o, lp, k, o->newest);
     lp.new_off = (uint32_t)((uint64_t)(2 * o->spare()) * (uint64_t)o->tile_stride); lp.new_slot = (uint8_t)o->spare();
-    lp.store_d = (k > 0 && !o->lazy_d) ? 1 : 0; lp.store_tile = 1;
+    lp.store_d = 0; lp.store_tile = 1;
     auto kern = lse_trial_kernel_for<T>(o, k == 0);
     const int grid = lse_grid<T>(o, (const void *)kern);
     o->d_stale = false;
     const int view_k = k, view_newest = o->newest;
-    auto direction_pending = [&]() { if (k > 0 && o->lazy_d) { o->d_stale = true; o->dview_k = view_k; o->dview_newest = view_newest; } };
+    auto direction_pending = [&]() { if (k > 0) { o->d_stale = true; o->dview_k = view_k; o->dview_newest = view_newest; } };
     auto stuck_fields = [&]() -> int32_t {                // delta_point = x_old (:118), delta_gradient still the previous step's
         if (o->k > 0) {
             DZO_TRY(lbfgs_ensure_g(o, o->slot_of(0))); DZO_TRY(lbfgs_ensure_g(o, o->slot_of(1)));
@@ -3779,30 +3749,15 @@ using namespace dzo;
 // the construction-time DZO_TUNE_* knobs (dev only), read once per construction
 static LbfgsKnobs lbfgs_read_knobs() {
     LbfgsKnobs k;
-    k.stride_skew = tune("DZO_TUNE_STRIDE_SKEW", 1);
-    k.blocked = tune("DZO_TUNE_BLOCKED", 1);
-    k.single_pass = tune("DZO_TUNE_SINGLE_PASS", 1);
-    k.point_ring = tune("DZO_TUNE_POINT_RING", 1);
-    k.interleave = tune("DZO_TUNE_INTERLEAVE", 1);
-    k.stream_major_set = getenv("DZO_TUNE_STREAM_MAJOR") != nullptr;
-    k.stream_major = tune("DZO_TUNE_STREAM_MAJOR", 0);
-    k.lse_points = tune("DZO_TUNE_LSE_POINTS", 1);
-    k.lazy_d = tune("DZO_TUNE_LAZY_D", 1);
-    k.point_sets = tune("DZO_TUNE_POINT_SETS", 1);
-    k.gram_u = tune("DZO_TUNE_GRAM_U", 4);
-    k.gram_bpc = tune("DZO_TUNE_GRAM_BPC", 0);
-    k.fused_finish = tune("DZO_TUNE_FUSED_FINISH", 0);
-    k.fused_finish_max = tune("DZO_TUNE_FUSED_FINISH_MAX", 65536);
-    k.speculate = tune("DZO_TUNE_SPECULATE", 1);
-    k.gram_variant = tune("DZO_TUNE_GRAM_VARIANT", 1);
-    k.gram_peel = tune("DZO_TUNE_GRAM_PEEL", 1);
-    k.gram_fresh_plain = tune("DZO_TUNE_GRAM_FRESH_PLAIN", 1);
-    k.gram_skip0 = tune("DZO_TUNE_GRAM_SKIP0", 1);
-    k.combine_fresh_plain = tune("DZO_TUNE_COMBINE_FRESH_PLAIN", 1);
-    k.combine_nts = tune("DZO_TUNE_COMBINE_NTS", 1);
-    k.combine_u = tune("DZO_TUNE_COMBINE_U", 4);
-    k.combine_bpc = tune("DZO_TUNE_COMBINE_BPC", 0);
-    k.fused_post = tune("DZO_TUNE_FUSED_POST", 1);
+    k.single_pass = tune_int("DZO_TUNE_SINGLE_PASS", 1);
+    k.point_ring = tune_int("DZO_TUNE_POINT_RING", 1);
+    k.stream_major = tune_int("DZO_TUNE_STREAM_MAJOR", INT_MIN);
+    k.stream_major_set = k.stream_major != INT_MIN;       // set at all
+    k.lse_points = tune_int("DZO_TUNE_LSE_POINTS", 1);
+    k.point_sets = tune_int("DZO_TUNE_POINT_SETS", 1);
+    k.fused_finish = tune_int("DZO_TUNE_FUSED_FINISH", 0);
+    k.speculate = tune_int("DZO_TUNE_SPECULATE", 1);
+    k.fused_post = tune_int("DZO_TUNE_FUSED_POST", 1);
     return k;
 }
 
@@ -3832,15 +3787,11 @@ static int32_t lbfgs_construct(int64_t n, int32_t history_length, int32_t dtype,
     o->last_step_length = round_to_dtype(dtype, initial_step_length);   // as legacy BFGS :779
     int32_t rc = core_alloc(c);
     if (rc != DZO_OK) { delete o; return rc; }
-    o->blocked = L.blocked; o->nslots = L.nslots; o->interleaved = L.interleaved; o->pair_stride = L.pair_stride;
+    o->blocked = L.blocked; o->nslots = L.nslots; o->pair_stride = L.pair_stride;
     o->ring_rows = L.ring_rows; o->tile_stride = L.tile_stride; o->rowbytes = L.rowbytes; o->ring_bytes = L.ring_bytes;
     o->gram_grid = L.gram_grid;
-    o->gram_u = kn.gram_u; o->gram_bpc = kn.gram_bpc;
-    o->fused_finish = kn.fused_finish != 0; o->fused_finish_max = kn.fused_finish_max;
+    o->fused_finish = kn.fused_finish != 0;
     o->speculate = kn.speculate != 0;
-    o->gram_variant = kn.gram_variant; o->gram_peel = kn.gram_peel; o->gram_fresh_plain = kn.gram_fresh_plain; o->gram_skip0 = kn.gram_skip0;
-    o->combine_fresh_plain = kn.combine_fresh_plain; o->combine_nts = kn.combine_nts != 0; o->combine_u = kn.combine_u;
-    o->combine_blocks_per_cu = kn.combine_bpc;
     o->single_pass = kn.single_pass != 0; o->fused_post = kn.fused_post != 0;
     // a failed allocation gives the state back: the ring alone is gigabytes
     auto alloc = [&](void **ptr, size_t bytes) -> int32_t {
@@ -3850,15 +3801,13 @@ static int32_t lbfgs_construct(int64_t n, int32_t history_length, int32_t dtype,
         if (e == hipErrorOutOfMemory) { set_error("out of device memory allocating the L-BFGS state (%zu bytes)", bytes); (void)hipGetLastError(); return DZO_ERR_NOMEM; }
         return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
     };
-    const size_t ring_alloc = L.blocked ? L.ring_bytes : (L.interleaved ? 2 * L.slab_bytes : L.slab_bytes);
+    const size_t ring_alloc = L.blocked ? L.ring_bytes : 2 * L.slab_bytes;
     DZO_TRY(alloc(&o->S, ring_alloc));
     if (L.blocked) {
         DZO_TRY(alloc(&o->dx_lin, L.lin_bytes));
         DZO_TRY(alloc(&o->dg_lin, L.lin_bytes));
-    } else if (L.interleaved) {
-        o->Y = (char *)o->S + L.lin_bytes;
     } else {
-        DZO_TRY(alloc(&o->Y, L.slab_bytes));
+        o->Y = (char *)o->S + L.lin_bytes;
     }
     DZO_TRY(alloc(&o->d_alloc, L.d_bytes));
     o->d = (char *)o->d_alloc + L.d_offset;             // off the allocator's alignment grid (see xbak / gbak)
@@ -3883,8 +3832,6 @@ static int32_t lbfgs_construct(int64_t n, int32_t history_length, int32_t dtype,
         if (L.blocked) {
             DZO_HIP(hipMemsetAsync(o->dx_lin, 0, L.lin_bytes, c.stream));
             DZO_HIP(hipMemsetAsync(o->dg_lin, 0, L.lin_bytes, c.stream));
-        } else if (!L.interleaved) {
-            DZO_HIP(hipMemsetAsync(o->Y, 0, L.slab_bytes, c.stream));
         }
         o->k = 0; o->newest = o->nslots - 1;   // spare() == 0
         o->refresh_delta_ptrs();
@@ -3892,7 +3839,6 @@ static int32_t lbfgs_construct(int64_t n, int32_t history_length, int32_t dtype,
         if (L.points) {
             // point ring: the start point and its gradient are point 0
             o->points = true;
-            o->lazy_d = L.lazy_d;
             o->point_sets = L.point_sets;
             o->xg_host_may_write = true;                      // (the caller owns x0 / g0 and may change them before the first step)
             DZO_DISPATCH(dtype, (ring_scatter<T>(o, x_dev, o->s_slot_v(o->newest)), ring_scatter<T>(o, g_dev, o->y_slot_v(o->newest))));
@@ -3934,7 +3880,6 @@ int32_t dzo_lbfgs_destroy(dzo_lbfgs_t o) {
     unsettled_retire(o);                                  // (a dzo_synchronize on another thread may be settling this handle right now)
     if (o->core.stream) (void)hipStreamSynchronize(o->core.stream);
     if (o->S) (void)hipFree(o->S);
-    if (o->Y && !o->interleaved && !o->blocked) (void)hipFree(o->Y);
     if (o->d_alloc) (void)hipFree(o->d_alloc);
     if (o->twin_slab) (void)hipFree(o->twin_slab);
     if (o->dx_lin) (void)hipFree(o->dx_lin);

@@ -25,6 +25,7 @@ constexpr int kPairMaxK = 20;                  // pairs the single-pass step ove
 // back to the two-pass kernels (n = 1e7, m = 24: 683 step!()/s there)
 static inline int point_max_k(int32_t dtype) { return dtype == DZO_F64 ? 24 : 20; }
 constexpr int kFusedMaxK = 24;                 // two register sets of 2k history vectors: 2*2*20 x 16 B per lane
+constexpr int kStreamU = 4;                    // 16-byte vectors per thread the Gram and combine passes start from (halved for a small n)
 
 static inline int64_t plan_dtype_size(int32_t dtype) { return dtype == DZO_F64 ? 8 : 4; }
 
@@ -41,15 +42,11 @@ struct RingDecor {
 // The DZO_TUNE_* values a constructor reads (dev only; the defaults are the product).  lbfgs_read_knobs fills it once
 // per construction.  The knobs that are read per step stay out: tests switch those on live handles.
 struct LbfgsKnobs {
-    int stride_skew = 1, blocked = 1, single_pass = 1, point_ring = 1, interleave = 1;
+    int single_pass = 1, point_ring = 1;
     bool stream_major_set = false;              // unset: stream-major from m = 9 on
     int stream_major = 0;
-    int lse_points = 1, lazy_d = 1, point_sets = 1;
-    int gram_u = 4, gram_bpc = 0;               // gram_bpc 0: as many blocks as are resident at once
-    int fused_finish = 0, fused_finish_max = 65536, speculate = 1;
-    int gram_variant = 1, gram_peel = 1, gram_fresh_plain = 1, gram_skip0 = 1;
-    int combine_fresh_plain = 1, combine_nts = 1, combine_u = 4, combine_bpc = 0;   // combine_bpc 0: resident blocks
-    int fused_post = 1;
+    int lse_points = 1, point_sets = 1;
+    int fused_finish = 0, speculate = 1, fused_post = 1;
 };
 
 // What dzo_lbfgs_create_problem knows and the constructor needs; empty for dzo_lbfgs_create (no problem: never blocked).
@@ -102,14 +99,12 @@ struct LbfgsLayout {
     int nslots = 0;                             // m + 1 (pairs + the spare); m + 2 for a tile ring (m + 1 POINTS + the spare)
     int64_t ring_rows = 0, tile_stride = kTileBytes, rowbytes = 0;
     size_t ring_bytes = 0;                      // tile ring: the one allocation
-    bool interleaved = true;                    // slabs: one slab s_0 y_0 s_1 y_1 ...; else two
-    int64_t pair_stride = 0;                    // elements between consecutive slots of the same history (slabs)
+    int64_t pair_stride = 0;                    // elements between consecutive slots of the same history (slabs: s_0 y_0 s_1 y_1 ...)
     size_t slab_bytes = 0;                      // nslots slots of one history
     size_t lin_bytes = 0;                       // one contiguous vector (dx_lin, dg_lin; the payload of d)
     size_t d_bytes = 0, d_offset = 0;           // d's allocation, and d within it: off the allocator's alignment grid
     int gram_grid = 0;                          // upper bound of the reducing grids (sizes the partials)
     int point_sets = 1;
-    bool lazy_d = true;
     LbfgsScalars scal;
 };
 
@@ -129,18 +124,17 @@ static inline LbfgsLayout lbfgs_plan_layout(int64_t n, int32_t dtype, int m, con
         // slot stride: n rounded up to 1 KiB, and an ODD number of KiB, so that the 2(m+1) streams
         // never sit a power-of-two distance apart (same HBM channel / bank for equal offsets)
         size_t sb = ((size_t)n * es + 1023) / 1024 * 1024;
-        if ((sb / 1024) % 2 == 0 && kn.stride_skew) sb += 1024;
+        if ((sb / 1024) % 2 == 0) sb += 1024;
         L.stride = (int64_t)(sb / es);
     }
     L.ring_obj = ring_obj_of_kind(st.kind) >= 1 ? ring_obj_of_kind(st.kind) : 0;
     // blocked (tile) ring: when the constructor knows that the single-pass step applies
     // (a ragged n: phantom padding, load_vec_tail -- on the POINT ring only)
-    L.blocked = lbfgs_plan_want_blocked(st, kn) && kn.blocked != 0 && kn.single_pass != 0 && m <= point_max_k(dtype) &&
+    L.blocked = lbfgs_plan_want_blocked(st, kn) && kn.single_pass != 0 && m <= point_max_k(dtype) &&
                 n >= 4 * vecn && (uint64_t)n * es < (1ull << 32) && (n % vecn == 0 || kn.point_ring != 0);
     L.nslots = m + (L.blocked ? 2 : 1);
     L.slab_bytes = (size_t)L.nslots * (size_t)L.stride * es;
     L.lin_bytes = (size_t)L.stride * es;
-    L.interleaved = kn.interleave != 0;
     if (L.blocked) {
         const int64_t nvec = (n + vecn - 1) / vecn;
         L.ring_rows = (nvec + kRowOwn - 1) / kRowOwn;
@@ -158,21 +152,20 @@ static inline LbfgsLayout lbfgs_plan_layout(int64_t n, int32_t dtype, int m, con
         }
         L.pair_stride = 0;
     } else {
-        L.pair_stride = L.interleaved ? 2 * L.stride : L.stride;
+        L.pair_stride = 2 * L.stride;
     }
     L.d_bytes = L.lin_bytes + 4096;
     L.d_offset = 3 * 1024;
-    L.gram_grid = cus * (kn.gram_bpc > 0 ? kn.gram_bpc : 8);
+    L.gram_grid = cus * 8;
     if (L.gram_grid > kPlanMaxPartialBlocks) L.gram_grid = kPlanMaxPartialBlocks;
     {
-        const int64_t tile_v = 64 * (int64_t)kn.gram_u;
+        const int64_t tile_v = 64 * (int64_t)kStreamU;
         const int64_t tiles = (n / vecn + tile_v - 1) / tile_v;
         if (tiles < L.gram_grid) L.gram_grid = (int)(tiles > 0 ? tiles : 1);
     }
     if (L.blocked && kn.point_ring != 0) {
         // point ring: the start point and its gradient are point 0
         L.points = true;
-        L.lazy_d = kn.lazy_d != 0;
         L.point_sets = kn.point_sets == 1 ? 1 : 2;
     }
     L.scal = lbfgs_plan_scalars(L.nslots, L.gram_grid);
@@ -274,6 +267,7 @@ constexpr int kPointPassGridCap = kPlanMaxPartialBlocks / 2;   // up to four (2 
 // n = 1e7); stream-major ring: non-temporal (655-672 vs 659-682 us over four interleaved rounds)
 static inline int point_plain_mb_default(int64_t tile_stride) { return tile_stride == kTileBytes ? 200 : 0; }
 
+constexpr int kPointStageRows = 16;             // what the host asks point_pass_launch for
 // Rows of new tiles a wave collects in LDS before it writes them: 1 KiB per staged tile, row and wave; the 160-KiB LDS
 // of a CU is one block's with two register sets per wave (144 KiB of it staged) and two blocks' with one (72 KiB each).
 struct PointLaunch {

@@ -192,10 +192,7 @@ __global__ __launch_bounds__(kBlock) void calib_fma_kernel(int64_t iters, T b, T
 // caches serve; it stops paying once ceil(N / 256) * js TILE blocks fill the chip by themselves.  DZO_TUNE_PAIRWISE_WAVE_MAX
 // overrides the threshold (tools/bench_pairwise.py sweeps it).
 static int64_t pw_wave_max() {
-    static const int64_t v = [] {
-        const char *e = getenv("DZO_TUNE_PAIRWISE_WAVE_MAX");
-        return e ? (int64_t)atoll(e) : (int64_t)2048;
-    }();
+    static const int64_t v = tune_int("DZO_TUNE_PAIRWISE_WAVE_MAX", 2048);
     return v;
 }
 constexpr int kPwMaxSplit = 64;

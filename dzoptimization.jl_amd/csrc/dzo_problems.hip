@@ -968,7 +968,7 @@ bool problem_phi6_async(dzo_problem_s *p, hipStream_t s, const void *x, const Ph
         }
         // DZO_TUNE_PHI6_COLS=1: the one-column kernel everywhere (32.4 us per round at config 2 against 27.3); it is the
         // only form for a ragged or a small n
-        const bool one_col = n % Vec16<T>::N != 0 || n < 64 || (getenv("DZO_TUNE_PHI6_COLS") && atoi(getenv("DZO_TUNE_PHI6_COLS")) == 1);
+        const bool one_col = n % Vec16<T>::N != 0 || n < 64 || tune_int("DZO_TUNE_PHI6_COLS", 0) == 1;
         const int ggrid = quad_grid(one_col ? n : (n + kPhi6Cols - 1) / kPhi6Cols);
         hipLaunchKernelGGL(one_col ? quadratic_phi6_kernel<T> : quadratic_phi6_cols_kernel<T>, dim3(ggrid), dim3(kBlock), 0, s, n,
                            (const T *)p->A, (const T *)x, d[0], d[1], p->scratch, flags, dreq);

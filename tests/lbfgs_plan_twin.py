@@ -16,9 +16,7 @@ K_ROW_LEAD = (64 - K_ROW_OWN) // 2                # :52
 K_PAIR_MAX_K, K_FUSED_MAX_K = 20, 24              # :997, :1002
 U32 = 1 << 32
 
-KNOB_DEFAULTS = dict(STRIDE_SKEW=1, BLOCKED=1, SINGLE_PASS=1, POINT_RING=1, INTERLEAVE=1, STREAM_MAJOR=None, LSE_POINTS=1, LAZY_D=1,
-                     POINT_SETS=1, GRAM_U=4, GRAM_BPC=0, FUSED_FINISH=0, FUSED_FINISH_MAX=65536, SPECULATE=1, GRAM_VARIANT=1, GRAM_PEEL=1,
-                     GRAM_FRESH_PLAIN=1, GRAM_SKIP0=1, COMBINE_FRESH_PLAIN=1, COMBINE_NTS=1, COMBINE_U=4, COMBINE_BPC=0, FUSED_POST=1)
+KNOB_DEFAULTS = dict(SINGLE_PASS=1, POINT_RING=1, STREAM_MAJOR=None, LSE_POINTS=1, POINT_SETS=1, FUSED_FINISH=0, SPECULATE=1, FUSED_POST=1)
 SCALARS = ["gram_ticket", "xg_differs", "pscal", "rho", "alpha", "coef", "scale", "alpha_sp", "coef_sp", "scale_sp", "Gyy", "Gsy", "sg", "yg",
            "gram_partials", "link_partials"]      # the order of :3965-3980
 
@@ -48,17 +46,16 @@ def layout(n, dtype, m, kind=NO_PROBLEM, decorated=False, x_al=True, g_al=True, 
     es = es_of(dtype)
     L = {}
     sb = (n * es + 1023) // 1024 * 1024           # :3882
-    if (sb // 1024) % 2 == 0 and kn["STRIDE_SKEW"]:   # :3883
+    if (sb // 1024) % 2 == 0:                     # :3883 (the skew: always)
         sb += 1024
     L["stride"] = sb // es
     wanted = kind != NO_PROBLEM and want_blocked(kind, decorated, x_al, g_al, c_al, kn)
     L["ring_obj"] = ring_obj_of(kind) if ring_obj_of(kind) >= 1 else 0      # :4085
     vecn = 16 // es
-    L["blocked"] = bool(wanted and kn["BLOCKED"] != 0 and kn["SINGLE_PASS"] != 0 and m <= point_max_k(dtype) and n >= 4 * vecn and
+    L["blocked"] = bool(wanted and kn["SINGLE_PASS"] != 0 and m <= point_max_k(dtype) and n >= 4 * vecn and
                         n * es < U32 and (n % vecn == 0 or kn["POINT_RING"] != 0))      # :3892-3894
     m1 = L["nslots"] = m + (2 if L["blocked"] else 1)                                 # :3896
     slab = L["slab_bytes"] = m1 * L["stride"] * es                                    # :3898
-    L["interleaved"] = kn["INTERLEAVE"] != 0                                          # :3903
     L["ring_rows"], L["tile_stride"], L["rowbytes"], L["ring_bytes"] = 0, K_TILE_BYTES, 0, 0   # the struct's defaults (:133, :140, :141)
     if L["blocked"]:
         nvec = (n + vecn - 1) // vecn                                                 # :3905
@@ -73,15 +70,13 @@ def layout(n, dtype, m, kind=NO_PROBLEM, decorated=False, x_al=True, g_al=True, 
             L["tile_stride"], L["rowbytes"] = K_TILE_BYTES, 2 * ms * K_TILE_BYTES
             L["ring_bytes"] = L["ring_rows"] * L["rowbytes"]
         L["pair_stride"] = 0                                                          # :3922
-    elif L["interleaved"]:
-        L["pair_stride"] = 2 * L["stride"]                                            # :3928
     else:
-        L["pair_stride"] = L["stride"]                                                # :3932
+        L["pair_stride"] = 2 * L["stride"]                                            # :3928 (one slab, s and y interleaved)
     L["lin_bytes"] = L["stride"] * es                                                 # :3923
     L["d_bytes"], L["d_offset"] = L["stride"] * es + 4096, 3 * 1024                   # :3934-3935
-    grid = cus * (kn["GRAM_BPC"] if kn["GRAM_BPC"] > 0 else 8)                        # :3951
+    grid = cus * 8                                                                    # :3951
     grid = min(grid, K_MAX_PARTIAL_BLOCKS)
-    tile_v = 64 * kn["GRAM_U"]
+    tile_v = 64 * 4
     tiles = (n // vecn + tile_v - 1) // tile_v                                        # :3955
     if tiles < grid:
         grid = tiles if tiles > 0 else 1
@@ -100,7 +95,6 @@ def layout(n, dtype, m, kind=NO_PROBLEM, decorated=False, x_al=True, g_al=True, 
     L["scalar_offsets"] = off
     L["link_partials_len"] = 4 * K_MAX_PARTIAL_BLOCKS      # (four columns of kMaxPartialBlocks: :80)
     L["points"] = bool(L["blocked"] and kn["POINT_RING"] != 0)                        # :3997
-    L["lazy_d"] = (kn["LAZY_D"] != 0) if L["points"] else True                        # :4000 / the struct's default :180
     L["point_sets"] = (1 if kn["POINT_SETS"] == 1 else 2) if L["points"] else 1       # :4001 / :183
     return L
 

@@ -178,7 +178,8 @@ def test_path_functions_restate_the_launchers():
     names = [tuple(re.findall(r"al16\((\w+)\)", c)) for c in conds]
     assert names == [tw.VEC_OPERANDS["symv"], tw.VEC_OPERANDS["fused"], tw.VEC_OPERANDS["update"]]
     assert "o->tri = !o->no_hessian && o->n % 2 == 0 && big && o->n < 65535LL * kTriCW;" in src
-    assert "const bool big = e ? o->n >= atoll(e) : (size_t)o->n * (size_t)o->n * es >= (128u << 20);" in src
+    assert 'const int min_n = tune_int("DZO_TUNE_BFGS_TRI_MIN_N", INT_MIN);' in src                 # (INT_MIN: the variable is unset)
+    assert "const bool big = min_n != INT_MIN ? o->n >= min_n : (size_t)o->n * (size_t)o->n * es >= (128u << 20);" in src
     assert re.search(r"constexpr int kTriCW = 32;", src) and tw.TRI_MAX_N == 65535 * 32 and tw.TRI_DEFAULT_BYTES == 128 << 20
     common = _source("dzo_common.h")
     assert "Vec16<double> { using type = double2; static constexpr int N = 2; }" in common
@@ -214,7 +215,7 @@ def test_batch_form_restates_the_source_at_every_table_entry():
     table's promise: the first and last size of every form and both sides of both 48 KiB edges."""
     src = _source("dzo_batch.hip")
     assert "b->rp = n <= 256 ? 1 : (n <= 512 ? 2 : 4);" in src
-    assert 'b->wide = (b->rp == 2 && n > tune_env("DZO_TUNE_BATCH_RP2_WIDE_ABOVE", 448)) ? 1 : 0;' in src
+    assert 'b->wide = (b->rp == 2 && n > tune_int("DZO_TUNE_BATCH_RP2_WIDE_ABOVE", 448)) ? 1 : 0;' in src
     assert "b->lds_bytes = 9 * np * es + (5 * np + 16) * sizeof(double) + 16;" in src
     assert "constexpr int UJ = RP == 1 ? 4 : (RP == 2 ? (WIDE ? 4 : 2) : 2);" in src
     assert "if (b->lds_bytes > 48 * 1024) {" in src

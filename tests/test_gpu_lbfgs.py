@@ -285,6 +285,52 @@ def test_each_step_matches_oracle_on_identical_state(n, m, steps, mode):
     print(f"worst per-step direction error n={n} m={m}: {worst:.3e}")
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("edge", ["full", "plus1", "minus1"])
+@pytest.mark.parametrize("U", [1, 2, 4])
+def test_gram_and_combine_match_the_oracle_at_their_tile_edges(U, edge, dtype, monkeypatch):
+    """The same per-step parity on the two-pass kernels (DZO_TUNE_SINGLE_PASS=0: Gram pass + combine pass over the slabs) at the
+    sizes where their tiling changes.  A tile is 256 U vectors of 16 bytes; the host starts from U = 4 and halves it while
+    ceil(n / tile) < 4 CUs, so t = 4 CUs tiles is the smallest count at which a U is kept.  n = t tile: full tiles only, all on
+    the predicate-free path; + 1: a ragged tile of one element (fp64: one scalar-tail element); + tile - 1: a ragged tile one
+    element short of full.  The oracle takes one step of its own first, so the three checked steps start from 1, 2 and 3 pairs:
+    the pair loop's "one pair left", "two pairs left" and steady-state bodies.  Tolerances: those of the test above; fp32 those
+    of the point ring's per-step test (the device sums in fp64, so the oracle does too)."""
+    monkeypatch.setenv("DZO_TUNE_SINGLE_PASS", "0")
+    tile = 256 * U * (16 // np.dtype(dtype).itemsize)
+    t = 4 * dzo.device_info()["compute_units"]
+    n = t * tile + {"full": 0, "plus1": 1, "minus1": tile - 1}[edge]
+    for u in (4, 2):                                      # the halving loop ends at this U
+        assert (-(-n // (256 * u * (16 // np.dtype(dtype).itemsize))) >= t) == (u <= U), (n, u)
+    m = 3
+    if dtype == np.float32:
+        orc.set_dot_mode(orc.DOT_WIDE)
+    try:
+        opt, ref, _ = _gpu_and_oracle(n, m, dtype)
+        assert opt.ring_layout == 0
+        ref.step()
+        tol_d, tol_x, tol_f = (TOL_DIRECTION, 1e-12, 1e-12) if dtype == np.float64 else (2e-4, 1e-6, 1e-5)
+        for it in range(3):
+            _sync_from_oracle(opt, ref)
+            assert opt.history_count == it + 1
+            opt.step(); ref.step()
+            assert opt.is_stuck == ref.is_stuck and not ref.is_stuck and opt.iteration_count == ref.iteration_count
+            e_d = rel(opt.step_direction.to_host().astype(np.float64), ref.step_direction.astype(np.float64))
+            x_new = opt.current_point.to_host()
+            e_x = rel(x_new.astype(np.float64), ref.current_point.astype(np.float64))
+            e_f = abs(opt.current_objective_value - ref.current_objective_value) / abs(ref.current_objective_value)
+            print(f"{np.dtype(dtype).name} U={U} n={n} step {it}: d {e_d:.3e} x {e_x:.3e} f {e_f:.3e} trials {opt.last_trials}/{ref.last_trials}")
+            assert e_d <= tol_d, it
+            assert opt.last_trials == ref.last_trials, it
+            moved_by = np.linalg.norm(ref.delta_point.astype(np.float64)) / np.linalg.norm(ref.current_point.astype(np.float64))
+            assert e_x <= (tol_x if dtype == np.float64 else max(tol_x, 2 * e_d * max(1.0, moved_by))), it
+            assert e_f <= tol_f, it
+            assert np.array_equal(opt.current_gradient.to_host(), ref.problem.grad(x_new)), it     # elementwise: bit-exact
+        assert opt.ring_layout == 0 and opt.single_pass_steps == 0
+    finally:
+        orc.set_dot_mode(orc.DOT_SEQUENTIAL)
+
+
 @pytest.mark.parametrize("mode", [dzo.TWOLOOP_CHAIN, dzo.TWOLOOP_GRAM], ids=["chain", "gram"])
 def test_free_running_trajectory_stays_close_then_converges(mode):
     n, m = 1000, 5

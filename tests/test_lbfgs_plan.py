@@ -11,6 +11,7 @@ import subprocess
 import pytest
 
 import lbfgs_plan_twin as tw
+from test_tuning_knobs import FOLDED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tools", "lbfgs_plan_table.cpp")
@@ -18,8 +19,8 @@ BEGIN, END = "<!-- lbfgs-plan-table:begin -->", "<!-- lbfgs-plan-table:end -->"
 DTYPES = [tw.F64, tw.F32]
 KINDS = [tw.NO_PROBLEM, tw.ROSENBROCK_CHAIN, tw.QUADRATIC_CHAIN, tw.LSE, tw.QUADRATIC]
 MS = list(range(1, 27)) + [64]
-LAYOUT_FIELDS = ["stride", "blocked", "points", "ring_obj", "nslots", "ring_rows", "tile_stride", "rowbytes", "ring_bytes", "interleaved",
-                 "pair_stride", "slab_bytes", "lin_bytes", "d_bytes", "d_offset", "gram_grid", "point_sets", "lazy_d", "scalar_total"]
+LAYOUT_FIELDS = ["stride", "blocked", "points", "ring_obj", "nslots", "ring_rows", "tile_stride", "rowbytes", "ring_bytes", "pair_stride",
+                 "slab_bytes", "lin_bytes", "d_bytes", "d_offset", "gram_grid", "point_sets", "scalar_total"]
 FACTS = ["points", "single_pass", "blocked", "mode", "line_search", "descent_check", "sd_fallback", "speculate", "fused_post", "callbacks",
          "box_on", "has_problem", "iteration_count", "n", "k", "m", "dtype", "ring_obj", "ring_decorated", "obj_agrees", "dec_agrees",
          "lambda_agrees", "lse_c_agrees", "spec_scalars", "d_al16"]
@@ -224,7 +225,11 @@ def test_reading_test_of_the_translation_unit():
     for k in knobs:
         name = '"DZO_TUNE_%s"' % k
         assert src.count(name) == reader.count(name) >= 1, k
-    code = "\n".join(line.split("//")[0] for line in src.splitlines())           # (comments may speak of an instantiation)
+    # the knobs folded into their defaults (tests/test_tuning_knobs.py keeps the list), and the state only they reached
+    gone = [k for k in FOLDED if not k.startswith("ADGD_")]
+    assert len(gone) >= 18 and not [k for k in gone if re.search(r"DZO_TUNE_%s(?![A-Z0-9_])" % k, src)]
+    assert not [word for word in ("gram_variant", "interleaved", "lazy_d", "combine_nts") if word in src]
+    code ="\n".join(line.split("//")[0] for line in src.splitlines())           # (comments may speak of an instantiation)
     assert code.count("lbfgs_point_pass_kernel<") == 1
     plan = open(os.path.join(ROOT, "dzoptimization.jl_amd", "csrc", "dzo_lbfgs_plan.h")).read()
     assert "#include <hip" not in plan and "__device__" not in plan and "__global__" not in plan

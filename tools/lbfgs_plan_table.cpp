@@ -18,12 +18,8 @@ using namespace dzo;
 // the knobs by the names of their DZO_TUNE_* variables
 static bool set_knob(LbfgsKnobs &k, const char *name, int v) {
     struct { const char *name; int *p; } t[] = {
-        {"STRIDE_SKEW", &k.stride_skew}, {"BLOCKED", &k.blocked}, {"SINGLE_PASS", &k.single_pass}, {"POINT_RING", &k.point_ring},
-        {"INTERLEAVE", &k.interleave}, {"LSE_POINTS", &k.lse_points}, {"LAZY_D", &k.lazy_d}, {"POINT_SETS", &k.point_sets},
-        {"GRAM_U", &k.gram_u}, {"GRAM_BPC", &k.gram_bpc}, {"FUSED_FINISH", &k.fused_finish}, {"FUSED_FINISH_MAX", &k.fused_finish_max},
-        {"SPECULATE", &k.speculate}, {"GRAM_VARIANT", &k.gram_variant}, {"GRAM_PEEL", &k.gram_peel},
-        {"GRAM_FRESH_PLAIN", &k.gram_fresh_plain}, {"GRAM_SKIP0", &k.gram_skip0}, {"COMBINE_FRESH_PLAIN", &k.combine_fresh_plain},
-        {"COMBINE_NTS", &k.combine_nts}, {"COMBINE_U", &k.combine_u}, {"COMBINE_BPC", &k.combine_bpc}, {"FUSED_POST", &k.fused_post},
+        {"SINGLE_PASS", &k.single_pass}, {"POINT_RING", &k.point_ring}, {"LSE_POINTS", &k.lse_points}, {"POINT_SETS", &k.point_sets},
+        {"FUSED_FINISH", &k.fused_finish}, {"SPECULATE", &k.speculate}, {"FUSED_POST", &k.fused_post},
     };
     if (!strcmp(name, "STREAM_MAJOR")) { k.stream_major_set = true; k.stream_major = v; return true; }
     for (auto &e : t) if (!strcmp(name, e.name)) { *e.p = v; return true; }
@@ -47,9 +43,9 @@ static int answer(FILE *in) {
             LbfgsKnobs kn;
             if (strcmp(kname, "-") && !set_knob(kn, kname, kv)) return 3;
             const LbfgsLayout L = lbfgs_plan_layout(n, dtype, m, st, kn, cus);
-            printf("L %lld %d %d %d %d %lld %lld %lld %zu %d %lld %zu %zu %zu %zu %d %d %d %zu", (long long)L.stride, (int)L.blocked, (int)L.points,
-                   L.ring_obj, L.nslots, (long long)L.ring_rows, (long long)L.tile_stride, (long long)L.rowbytes, L.ring_bytes, (int)L.interleaved,
-                   (long long)L.pair_stride, L.slab_bytes, L.lin_bytes, L.d_bytes, L.d_offset, L.gram_grid, L.point_sets, (int)L.lazy_d, L.scal.total);
+            printf("L %lld %d %d %d %d %lld %lld %lld %zu %lld %zu %zu %zu %zu %d %d %zu", (long long)L.stride, (int)L.blocked, (int)L.points,
+                   L.ring_obj, L.nslots, (long long)L.ring_rows, (long long)L.tile_stride, (long long)L.rowbytes, L.ring_bytes,
+                   (long long)L.pair_stride, L.slab_bytes, L.lin_bytes, L.d_bytes, L.d_offset, L.gram_grid, L.point_sets, L.scal.total);
             for (int i = 0; i < kScalCount; ++i) printf(" %zu", L.scal.off[i]);
             printf("\n");
         } else if (tag == 'V') {
