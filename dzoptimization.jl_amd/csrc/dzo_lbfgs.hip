@@ -2259,6 +2259,16 @@ static SlotMap make_map(const dzo_lbfgs_s *o) {
     return mp;
 }
 
+// ---------------------------------------------------------------------------- addresses the drivers share
+// the reduced Gram values (kGramValues per pair), behind the per-block partials of the largest grid
+static inline double *gram_vals(const dzo_lbfgs_s *o) { return o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves; }
+// last slot of that block: no pair's value lives there (lbfgs_flush_rho's scratch)
+static inline double *gram_vals_scratch(const dzo_lbfgs_s *o) { return gram_vals(o) + kGramValues * kMaxHistory - 1; }
+// tile ring: 32-bit byte offset of a slot's first (s / point) tile; its y / gradient tile is tile_stride further
+static inline uint32_t ring_tile_off(const dzo_lbfgs_s *o, int slot) { return (uint32_t)((uint64_t)(2 * slot) * (uint64_t)o->tile_stride); }
+// a sum that lands in a T of the reference is rounded to fp32 on its way out
+static inline int f32_flag(const OptCore &c) { return c.dtype == DZO_F32 ? 1 : 0; }
+
 // ---------------------------------------------------------------------------- CHAIN driver
 template <typename T> static int32_t direction_chain(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
@@ -2343,7 +2353,7 @@ static GramFinishParams gram_finish_params(dzo_lbfgs_s *o, int pivot, bool recur
     fp.gate = gate;
     fp.k = o->k; fp.m1 = o->nslots; fp.pivot = pivot; fp.grid = 0; fp.do_recurrence = recurrence ? 1 : 0;
     fp.map = make_map(o); fp.partials = vals; fp.rho = o->rho;
-    fp.rho_from_vals = rho_from_vals ? 1 : 0; fp.rho_to_f32 = o->core.dtype == DZO_F32 ? 1 : 0;
+    fp.rho_from_vals = rho_from_vals ? 1 : 0; fp.rho_to_f32 = f32_flag(o->core);
     fp.Gyy = o->Gyy; fp.Gsy = o->Gsy; fp.sg = o->sg; fp.yg = o->yg;
     fp.alpha = o->alpha; fp.coef = o->coef; fp.scale = o->scale;
     if (gate) { fp.alpha = o->alpha_sp; fp.coef = o->coef_sp; fp.scale = o->scale_sp; }   // next step's set
@@ -2361,6 +2371,20 @@ static int32_t gram_finish_launch(dzo_lbfgs_s *o, int pivot, bool recurrence, co
     }
     DZO_HIP(hipGetLastError());
     return DZO_OK;
+}
+
+// the plain Gram reduction: `nvals` values from `pcount` partials each into `out`, no rho riding along
+static void gram_reduce_plain(dzo_lbfgs_s *o, const double *partials, int pcount, double *out, int nvals) {
+    hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals), dim3(kBlock), 0, o->core.stream, partials, pcount, out, nvals, (const double *)nullptr, 0,
+                       (double *)nullptr, 0);
+}
+
+// vectors per thread of a streaming pass over the history: as many (of kStreamU, halving) as still leave >= 4 blocks per CU
+// (small n would otherwise launch fewer blocks than there are CUs); vec_elems = the elements one block covers per vector
+static int stream_unroll(int64_t n, int64_t vec_elems) {
+    int u = kStreamU;
+    while (u > 1 && (n + vec_elems * u - 1) / (vec_elems * u) < (int64_t)ctx().cus * 4) u >>= 1;
+    return u;
 }
 
 template <typename T> static int32_t gram_pass(dzo_lbfgs_s *o, int pivot, bool recurrence) {
@@ -2385,18 +2409,15 @@ template <typename T> static int32_t gram_pass(dzo_lbfgs_s *o, int pivot, bool r
     // lane-distributed accumulators: one launch shape for every k (the pair-per-wave
     // variant, 5*ceil(k/4) accumulators per lane and 8 concurrent streams per block, measured
     // 5 % slower at k = 20 and was removed)
-    // vectors per thread: as many as still leave >= 4 blocks per CU (small n would otherwise
-    // launch fewer blocks than there are CUs)
-    int gu = kStreamU;
     const int64_t vec_elems = (int64_t)kBlock * (vec ? Vec16<T>::N : 1);
-    while (gu > 1 && (c.n + vec_elems * gu - 1) / (vec_elems * gu) < (int64_t)ctx().cus * 4) gu >>= 1;
+    const int gu = stream_unroll(c.n, vec_elems);
     int64_t per_block = vec_elems * gu;
     int64_t blocks = (c.n + per_block - 1) / per_block;
     // grid = the blocks that are resident at once (occupancy x CUs): every block then walks
     // the same number of tiles (+-1) and there is no second, partially filled round of
     // blocks.  Measured at n = 1e7, k = 20: 494 us against 527 us with 8 blocks per CU.
-    double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
-#define GL(UU)                                                                                                  \
+    double *vals = gram_vals(o);
+#define GL(UU)                                                                                                 \
     do {                                                                                                        \
         auto kern = o->blocked ? gram_pass_lanes_kernel<T, true, UU, true>                                      \
                     : post ? gram_pass_lanes_kernel<T, true, UU, false, true>                                   \
@@ -2419,8 +2440,7 @@ template <typename T> static int32_t gram_pass(dzo_lbfgs_s *o, int pivot, bool r
         o->post_pending = false;
         {
             DZO_TIMED("lbfgs_gram_reduce", s);
-            hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals), dim3(kBlock), 0, s, o->gram_partials, pcount, vals, nvals, (const double *)nullptr, 0,
-                               (double *)nullptr, 0);
+            gram_reduce_plain(o, o->gram_partials, pcount, vals, nvals);
         }
         return gram_finish_launch(o, pivot, recurrence, vals, true);
     }
@@ -2431,7 +2451,7 @@ template <typename T> static int32_t gram_pass(dzo_lbfgs_s *o, int pivot, bool r
             DZO_TIMED("lbfgs_gram_reduce_finish", s);
             hipLaunchKernelGGL(gram_reduce_finish_kernel, dim3(1), dim3(kFusedFinishThreads), gram_finish_lds_bytes(k), s, fp,
                                (const double *)o->gram_partials, pcount, vals, nvals, (const double *)c.partials(),
-                               rho ? o->rho_pending_count : 0, o->rho + o->rho_pending_slot, c.dtype == DZO_F32 ? 1 : 0);
+                               rho ? o->rho_pending_count : 0, o->rho + o->rho_pending_slot, f32_flag(c));
         }
         o->rho_pending = false;
         DZO_HIP(hipGetLastError());
@@ -2440,8 +2460,7 @@ template <typename T> static int32_t gram_pass(dzo_lbfgs_s *o, int pivot, bool r
     {
         DZO_TIMED("lbfgs_gram_reduce", s);
         hipLaunchKernelGGL(gram_reduce_kernel, dim3(nvals + (rho ? 1 : 0)), dim3(kBlock), 0, s, o->gram_partials, pcount,
-                           vals, nvals, (const double *)c.partials(), o->rho_pending_count, o->rho + o->rho_pending_slot,
-                           c.dtype == DZO_F32 ? 1 : 0);
+                           vals, nvals, (const double *)c.partials(), o->rho_pending_count, o->rho + o->rho_pending_slot, f32_flag(c));
         o->rho_pending = false;
     }
     return gram_finish_launch(o, pivot, recurrence, vals);
@@ -2460,13 +2479,11 @@ template <typename T> static int32_t gram_scalars(dzo_lbfgs_s *o) {
     }
     if (o->scalars_ready) return DZO_OK;
     if (o->gram_ready) {
-        double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
         {
             DZO_TIMED("lbfgs_gram_reduce", c.stream);
-            hipLaunchKernelGGL(gram_reduce_kernel, dim3(kGramValues * k), dim3(kBlock), 0, c.stream, o->gram_partials,
-                               o->gram_ready_grid, vals, kGramValues * k, (const double *)nullptr, 0, (double *)nullptr, 0);
+            gram_reduce_plain(o, o->gram_partials, o->gram_ready_grid, gram_vals(o), kGramValues * k);
         }
-        DZO_TRY(gram_finish_launch(o, 0, true, vals, true));
+        DZO_TRY(gram_finish_launch(o, 0, true, gram_vals(o), true));
         o->gram_ready = false;
     } else {
         if (o->gram_rebuild || o->gram_stale > 1) {
@@ -2496,9 +2513,9 @@ template <typename T> static int32_t direction_gram(dzo_lbfgs_s *o) {
     cp.rowbytes = o->rowbytes;
     cp.debug = tune_int("DZO_TUNE_TP_DEBUG", 0) == 2;
     const bool vec = al16(c.g);
-    int u = kStreamU;
-    while (u > 1 && (c.n + (int64_t)kBlock * (vec ? Vec16<T>::N : 1) * u - 1) / ((int64_t)kBlock * (vec ? Vec16<T>::N : 1) * u) < (int64_t)ctx().cus * 4) u >>= 1;
-    int64_t per_block = (int64_t)kBlock * (vec ? Vec16<T>::N : 1) * u;
+    const int64_t vec_elems = (int64_t)kBlock * (vec ? Vec16<T>::N : 1);
+    const int u = stream_unroll(c.n, vec_elems);
+    int64_t per_block = vec_elems * u;
     int64_t blocks = (c.n + per_block - 1) / per_block;
     {
         DZO_TIMED("lbfgs_combine", s);
@@ -2519,28 +2536,41 @@ template <typename T> static int32_t direction_gram(dzo_lbfgs_s *o) {
 
 static int32_t lbfgs_flush_rho(dzo_lbfgs_s *o);
 
+// fixed-order sum of `count` partials into *dst, rounded to T like the reference's dot; gate: only behind an accepted trial
+static void finish_to_launch(dzo_lbfgs_s *o, const double *partials, int count, double *dst, const int32_t *gate = nullptr) {
+    hipLaunchKernelGGL(finish_to_kernel, dim3(1), dim3(kBlock), 0, o->core.stream, partials, count, dst, f32_flag(o->core), gate);
+}
+
+// the accepted step's tail as ONE pass over x, g and the gradient buffer that was current: dx (holding x_old) <- x - x_old,
+// dg <- g - g_old, partials of rho = dx . dg into the workspace; *grid = their count
+static int32_t accept_delta_rho_launch(dzo_lbfgs_s *o, void *dx, const void *g_old, void *dg, int *grid) {
+    OptCore &c = o->core;
+    const bool vec = al16(c.x) && al16(dx) && al16(c.g) && al16(g_old) && al16(dg);
+    *grid = stream_grid(c.n, (vec ? 16 / (int)dtype_size(c.dtype) : 1) * 2);
+    {
+        DZO_TIMED("lbfgs_accept_delta_rho", c.stream);
+#define ADR(VEC) DZO_DISPATCH(c.dtype, hipLaunchKernelGGL((accept_delta_rho_kernel<T, VEC>), dim3(*grid), dim3(kBlock), 0, c.stream, c.n, (const T *)c.x, (T *)dx, \
+                                                          (const T *)c.g, (const T *)g_old, (T *)dg, c.partials()))
+        if (vec) ADR(true); else ADR(false);
+#undef ADR
+    }
+    DZO_HIP(hipGetLastError());
+    return DZO_OK;
+}
+
 // the deferred tail of the last accepted step, now (somebody needs delta_point / delta_gradient / rho or the buffers they
 // are formed from before a Gram pass could form them on its way): accept_delta_rho_kernel, as the undeferred path runs it
 static int32_t lbfgs_flush_post(dzo_lbfgs_s *o) {
     if (!o->post_pending) return DZO_OK;
     OptCore &c = o->core;
     o->post_pending = false;
-    void *dx = o->s_slot_v(o->newest), *dg = o->y_slot_v(o->newest);
-    const bool vec = al16(c.x) && al16(dx) && al16(c.g) && al16(o->post_g_old) && al16(dg);
-    const int grid = stream_grid(c.n, (vec ? 16 / (int)dtype_size(c.dtype) : 1) * 2);
-    {
-        DZO_TIMED("lbfgs_accept_delta_rho", c.stream);
-        if (vec) DZO_DISPATCH(c.dtype, hipLaunchKernelGGL((accept_delta_rho_kernel<T, true>), dim3(grid), dim3(kBlock), 0, c.stream, c.n, (const T *)c.x, (T *)dx,
-                                                          (const T *)c.g, (const T *)o->post_g_old, (T *)dg, c.partials()));
-        else DZO_DISPATCH(c.dtype, hipLaunchKernelGGL((accept_delta_rho_kernel<T, false>), dim3(grid), dim3(kBlock), 0, c.stream, c.n, (const T *)c.x, (T *)dx,
-                                                      (const T *)c.g, (const T *)o->post_g_old, (T *)dg, c.partials()));
-    }
-    DZO_HIP(hipGetLastError());
+    int grid = 0;
+    DZO_TRY(accept_delta_rho_launch(o, o->s_slot_v(o->newest), o->post_g_old, o->y_slot_v(o->newest), &grid));
     // rho of the newest pair: summed lazily like after any two-pass step (lbfgs_finish_push's rho_pending)
     if (o->mode == DZO_TWOLOOP_GRAM) { o->rho_pending = true; o->rho_pending_count = grid; o->rho_pending_slot = o->newest; }
     else {
         DZO_TIMED("lbfgs_rho_finish", c.stream);
-        hipLaunchKernelGGL(finish_to_kernel, dim3(1), dim3(kBlock), 0, c.stream, c.partials(), grid, o->rho + o->newest, c.dtype == DZO_F32 ? 1 : 0, (const int32_t *)nullptr);
+        finish_to_launch(o, c.partials(), grid, o->rho + o->newest);
         DZO_HIP(hipGetLastError());
     }
     return DZO_OK;
@@ -2574,13 +2604,9 @@ static int32_t lbfgs_post_gradient(dzo_lbfgs_s *o) {
     const int grid = stream_grid(c.n, (vec ? 16 / (int)dtype_size(c.dtype) : 1) * 2);
     {
         DZO_TIMED("lbfgs_delta_rho", s);
-        if (c.dtype == DZO_F64) {
-            if (vec) hipLaunchKernelGGL((delta_rho_kernel<double, true>), dim3(grid), dim3(kBlock), 0, s, c.n, (const double *)c.g, (double *)c.dg, (const double *)c.dx, c.partials());
-            else hipLaunchKernelGGL((delta_rho_kernel<double, false>), dim3(grid), dim3(kBlock), 0, s, c.n, (const double *)c.g, (double *)c.dg, (const double *)c.dx, c.partials());
-        } else {
-            if (vec) hipLaunchKernelGGL((delta_rho_kernel<float, true>), dim3(grid), dim3(kBlock), 0, s, c.n, (const float *)c.g, (float *)c.dg, (const float *)c.dx, c.partials());
-            else hipLaunchKernelGGL((delta_rho_kernel<float, false>), dim3(grid), dim3(kBlock), 0, s, c.n, (const float *)c.g, (float *)c.dg, (const float *)c.dx, c.partials());
-        }
+#define DR(VEC) hipLaunchKernelGGL((delta_rho_kernel<T, VEC>), dim3(grid), dim3(kBlock), 0, s, c.n, (const T *)c.g, (T *)c.dg, (const T *)c.dx, c.partials())
+        DZO_DISPATCH(c.dtype, if (vec) DR(true); else DR(false));
+#undef DR
     }
     DZO_HIP(hipGetLastError());
     return lbfgs_finish_push(o, grid, false);
@@ -2595,31 +2621,22 @@ static int32_t lbfgs_flush_rho(dzo_lbfgs_s *o) {
         // rho of the newest pair still sits in the single pass's dots (value 4 of pair 0 = s_p.y_p).
         // Sum it exactly as the coming gram_reduce launch will (same kernel, same order), so that
         // reading rho_history never changes what the optimizer computes next.
-        OptCore &c = o->core;
-        double *tmp = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves + kGramValues * kMaxHistory - 1;   // last, unused slot of the reduced values
-        hipLaunchKernelGGL(gram_reduce_kernel, dim3(1), dim3(kBlock), 0, c.stream,
-                           o->gram_partials + (size_t)4 * o->gram_ready_grid, o->gram_ready_grid, tmp, 1,
-                           (const double *)nullptr, 0, (double *)nullptr, 0);
-        hipLaunchKernelGGL(finish_to_kernel, dim3(1), dim3(kBlock), 0, c.stream, (const double *)tmp, 1, o->rho + o->newest,
-                           c.dtype == DZO_F32 ? 1 : 0, (const int32_t *)nullptr);
+        double *tmp = gram_vals_scratch(o);
+        gram_reduce_plain(o, o->gram_partials + (size_t)4 * o->gram_ready_grid, o->gram_ready_grid, tmp, 1);
+        finish_to_launch(o, tmp, 1, o->rho + o->newest);
         DZO_HIP(hipGetLastError());
     }
     if (!o->rho_pending) return DZO_OK;
-    OptCore &c = o->core;
-    DZO_TIMED("lbfgs_rho_finish", c.stream);
-    hipLaunchKernelGGL(finish_to_kernel, dim3(1), dim3(kBlock), 0, c.stream, c.partials(), o->rho_pending_count,
-                       o->rho + o->rho_pending_slot, c.dtype == DZO_F32 ? 1 : 0, (const int32_t *)nullptr);
+    DZO_TIMED("lbfgs_rho_finish", o->core.stream);
+    finish_to_launch(o, o->core.partials(), o->rho_pending_count, o->rho + o->rho_pending_slot);
     DZO_HIP(hipGetLastError());
     o->rho_pending = false;
     return DZO_OK;
 }
 
 static int32_t lbfgs_rho_finish(dzo_lbfgs_s *o, int grid, const int32_t *gate) {
-    OptCore &c = o->core;
-    DZO_TIMED("lbfgs_rho_finish", c.stream);
-    // stored by slot, rounded to T like the reference's dot
-    hipLaunchKernelGGL(finish_to_kernel, dim3(1), dim3(kBlock), 0, c.stream, c.partials(), grid, o->rho + o->spare(),
-                       c.dtype == DZO_F32 ? 1 : 0, gate);
+    DZO_TIMED("lbfgs_rho_finish", o->core.stream);
+    finish_to_launch(o, o->core.partials(), grid, o->rho + o->spare(), gate);   // stored by slot
     DZO_HIP(hipGetLastError());
     return DZO_OK;
 }
@@ -2871,6 +2888,15 @@ static int32_t lbfgs_steepest(dzo_lbfgs_s *o) {
     return DZO_OK;
 }
 
+// last_step_length = ||delta_point|| in T (legacy :625-627; delta_point stays valid after the push)
+static int32_t lbfgs_note_step_length(dzo_lbfgs_s *o) {
+    OptCore &c = o->core;
+    double ss = 0;
+    DZO_TRY(lbfgs_aux_dot(o, c.dx, c.dx, &ss));
+    o->last_step_length = c.dtype == DZO_F32 ? (double)sqrtf((float)ss) : sqrt(ss);
+    return DZO_OK;
+}
+
 static int32_t lbfgs_eval_at(OptCore &c, void *x, double *f) {
     if (c.objective) {
         DZO_HIP(hipStreamSynchronize(c.stream));
@@ -2972,11 +2998,7 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
         bool accepted = false;
         DZO_TRY(lbfgs_wolfe_search(o, &accepted));
         if (!accepted) return DZO_OK;
-        if (safeguards) {
-            double ss = 0;
-            DZO_TRY(lbfgs_aux_dot(o, c.dx, c.dx, &ss));
-            o->last_step_length = c.dtype == DZO_F32 ? (double)sqrtf((float)ss) : sqrt(ss);
-        }
+        if (safeguards) DZO_TRY(lbfgs_note_step_length(o));
         double r = 0;
         DZO_TRY(lbfgs_aux_dot(o, c.dx, c.dg, &r));                   // :505
         DZO_HIP(hipMemcpyAsync(o->rho + o->spare(), &r, sizeof(double), hipMemcpyHostToDevice, c.stream));
@@ -3034,16 +3056,8 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
             DZO_TRY(done);
             return DZO_OK;
         }
-        const bool vec = al16(c.x) && al16(c.dx) && al16(c.g) && al16(g_old) && al16(c.dg);
-        const int grid = stream_grid(c.n, (vec ? 16 / (int)dtype_size(c.dtype) : 1) * 2);
-        {
-            DZO_TIMED("lbfgs_accept_delta_rho", c.stream);
-            if (vec) DZO_DISPATCH(c.dtype, hipLaunchKernelGGL((accept_delta_rho_kernel<T, true>), dim3(grid), dim3(kBlock), 0, c.stream, c.n, (const T *)c.x, (T *)c.dx,
-                                                              (const T *)c.g, (const T *)g_old, (T *)c.dg, c.partials()));
-            else DZO_DISPATCH(c.dtype, hipLaunchKernelGGL((accept_delta_rho_kernel<T, false>), dim3(grid), dim3(kBlock), 0, c.stream, c.n, (const T *)c.x, (T *)c.dx,
-                                                          (const T *)c.g, (const T *)g_old, (T *)c.dg, c.partials()));
-        }
-        DZO_HIP(hipGetLastError());
+        int grid = 0;
+        DZO_TRY(accept_delta_rho_launch(o, c.dx, g_old, c.dg, &grid));
         lbfgs_mark_unsettled(o);
         done = lbfgs_finish_push(o, grid, false);
     } else {
@@ -3052,11 +3066,7 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
         done = lbfgs_post_gradient(o);                    // :480-507
     }
     DZO_TRY(done);
-    if (safeguards) {                                     // legacy :625-627 (delta_point stays valid after the push)
-        double ss = 0;
-        DZO_TRY(lbfgs_aux_dot(o, c.dx, c.dx, &ss));
-        o->last_step_length = c.dtype == DZO_F32 ? (double)sqrtf((float)ss) : sqrt(ss);
-    }
+    if (safeguards) DZO_TRY(lbfgs_note_step_length(o));
     return DZO_OK;
 }
 
@@ -3155,9 +3165,121 @@ static int32_t lbfgs_settle_entry(void *h) {
     return DZO_OK;
 }
 
+// ---------------------------------------------------------------------------- pieces the three pass steps share
+// (lbfgs_step_single_pass, lbfgs_step_points, lbfgs_step_points_lse.  Their trial loops stay apart -- what follows a
+// rejected trial differs in each -- and nothing here asks which of them is calling.)
+
+// one trial: the change flag zero (decide_body leaves it so -- flag_armed; otherwise a memset), then the pass
+template <typename P> static int32_t pass_trial_launch(OptCore &c, void (*kern)(P), int grid, size_t dyn_lds, const P &p, int attempt) {
+    if (!c.flag_armed) DZO_HIP(hipMemsetAsync(c.flag(), 0, sizeof(int32_t), c.stream));
+    c.flag_armed = false;
+    DZO_TIMED(attempt == 0 ? "lbfgs_single_pass" : "lbfgs_single_pass_retry", c.stream);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), dyn_lds, c.stream, p);
+    return DZO_OK;
+}
+
+// :128 / :139 on the device (outcome to pinned host memory) as one block of the launch that also sums the Gram partials the
+// pass left for the k_next pairs of the post-push history.  obj_partials: `grid` partials of f(x + t d), then as many of
+// f(x + t/2 d); l2_partials (nullptr: no L2 term, always so on the pair ring): the same two sets of norm2 (:232)
+static int32_t gram_reduce_decide_launch(dzo_lbfgs_s *o, int k_next, const double *obj_partials, int grid, const double *l2_partials) {
+    OptCore &c = o->core;
+    {
+        DZO_TIMED("lbfgs_gram_reduce", c.stream);
+        const int nvals = kGramValues * k_next;
+        DecideArgs da = decide_args(c, obj_partials, grid, 1.0);
+        da.partials2 = obj_partials + grid;
+        if (l2_partials) { da.l2_partials = l2_partials; da.l2_partials2 = l2_partials + grid; da.l2_lambda = o->ring_dec.l2; }
+        hipLaunchKernelGGL(gram_reduce_decide_kernel, dim3(nvals + 1), dim3(kBlock), 0, c.stream, (const double *)o->gram_partials, grid, gram_vals(o),
+                           nvals, da);
+        c.flag_armed = true;
+    }
+    DZO_HIP(hipGetLastError());
+    return DZO_OK;
+}
+
+// Enqueued BEFORE the host knows the trial's outcome and gated on that decision: the scalar part of the NEXT two-loop
+// (recurrence on the post-push history, from the reduced values), so the GPU has work while the host round-trips and the
+// next step starts with its scalars ready (alpha_sp / coef_sp / scale_sp).  The launch is formed with newest and k as
+// lbfgs_finish_push will leave them; the only place that moves them and puts them back.
+static int32_t next_scalars_gated(dzo_lbfgs_s *o, int k_next) {
+    const int sv_newest = o->newest, sv_k = o->k;
+    o->newest = o->spare(); o->k = k_next;
+    const int32_t rc = gram_finish_launch(o, 0, true, gram_vals(o), true, o->core.status());
+    o->newest = sv_newest; o->k = sv_k;
+    return rc;
+}
+
+// an accepted trial (:139-146; the pass already did :478-480): rho of the new pair was set by the gated gram_finish, the
+// pass wrote its tiles, and alpha_sp / coef_sp / scale_sp hold the next step's scalars
+static int32_t pass_accept(dzo_lbfgs_s *o, double f_new) {
+    OptCore &c = o->core;
+    c.df = round_to_dtype(c.dtype, f_new - c.f);
+    c.f = f_new;
+    DZO_TRY(lbfgs_finish_push(o, 0, true, true, true));
+    o->spec_scalars = true;
+    o->gram_ready = false;
+    o->gram_stale = 0;
+    return DZO_OK;
+}
+
+// ---- the two steps on the point ring
+// slot of point j in the view of the ring whose point 0 sat in slot view_newest
+static inline int ring_view_slot(const dzo_lbfgs_s *o, int view_newest, int j) { return ((view_newest - j) % o->nslots + o->nslots) % o->nslots; }
+
+// The view a step starts from.  step_direction is formed on demand (lbfgs_materialize_d) by one more pass over it: its points
+// are all still there after the step, whether it pushed or not.  (k = 0: the first step walks along the direction the
+// constructor left, nothing to form.)
+struct RingView { int k, newest; };
+static inline void direction_pending(dzo_lbfgs_s *o, RingView v) {
+    if (v.k > 0) { o->d_stale = true; o->dview_k = v.k; o->dview_newest = v.newest; }
+}
+
+// what the point pass and the direction on demand both put into FusedParams: a view of k + 1 points (points beyond k: point k
+// again, those pairs are zero), the spare slot, this step's scalars, the scratch, the decorators
+template <typename T> static void fused_fill_params(dzo_lbfgs_s *o, FusedParams<T> &fp, int k, int view_newest) {
+    OptCore &c = o->core;
+    memset(&fp, 0, sizeof(fp));
+    fp.n = c.n; fp.k = k; fp.k_next = k < o->m ? k + 1 : o->m;
+    fp.d = (T *)o->d;
+    fp.ring = (T *)o->S; fp.rowbytes = (uint32_t)o->rowbytes;
+    fp.new_off = ring_tile_off(o, o->spare()); fp.ystride = (uint32_t)o->tile_stride;
+    fp.alpha = o->alpha; fp.coef = o->coef; fp.scale = o->scale;
+    for (int j = 0; j <= kFusedMaxK; ++j) fp.soff[j] = ring_tile_off(o, ring_view_slot(o, view_newest, j < k ? j : k));
+    fp.gram_partials = o->gram_partials;
+    fp.obj_partials = c.problem->scratch;
+    fp.changed = c.flag();
+    fp.dec = point_decor<T>(o->ring_dec);
+    fp.obj_lambda = (T)o->ring_obj_lambda;
+}
+
+// a step that ends stuck (:128-131, or the halving limit): the fields as take_backtracking_step! leaves them -- delta_point =
+// x_old (:118), delta_gradient still the previous step's (pair 0 = point 0 - point 1) -- and the direction it walked along
+template <typename T> static int32_t points_end_stuck(dzo_lbfgs_s *o, RingView view) {
+    o->core.is_stuck = true;
+    direction_pending(o, view);
+    if (o->k > 0) {
+        DZO_TRY(lbfgs_ensure_g(o, o->slot_of(0))); DZO_TRY(lbfgs_ensure_g(o, o->slot_of(1)));
+        ring_gather_diff<T>(o, o->y_slot_v(o->slot_of(0)), o->y_slot_v(o->slot_of(1)), o->dg_lin);
+    }
+    ring_gather<T>(o, o->s_slot_v(o->newest), o->dx_lin);
+    DZO_HIP(hipGetLastError());
+    o->lin_stale = false;
+    return DZO_OK;
+}
+
+// an accepted trial: the spare slot becomes point 0.  wrote_g: the pass wrote its gradient tiles too (otherwise they are formed
+// on demand, lbfgs_ensure_g); noted for the spare slot BEFORE the push moves it
+static int32_t points_accept(dzo_lbfgs_s *o, RingView view, double f_new, bool wrote_g) {
+    if (wrote_g) o->g_valid |= 1u << o->spare(); else o->g_valid &= ~(1u << o->spare());
+    DZO_TRY(pass_accept(o, f_new));
+    o->xg_lin_stale = true;
+    direction_pending(o, view);
+    lbfgs_mark_unsettled(o);
+    return DZO_OK;
+}
+
 template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
-    hipStream_t s = c.stream;
     constexpr int N = Vec16<T>::N;
     const int k = o->k;
     const int64_t nvec = c.n / N;
@@ -3171,12 +3293,9 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     fp.x = (const T *)c.x; fp.g = (const T *)c.g; fp.x_out = (T *)o->x_twin; fp.g_out = (T *)o->g_twin;
     fp.d = (T *)o->d;
     fp.ring = (T *)o->S; fp.rowbytes = (uint32_t)o->rowbytes;
-    fp.new_off = (uint32_t)((uint64_t)(2 * o->spare()) * (uint64_t)o->tile_stride); fp.ystride = (uint32_t)o->tile_stride;
+    fp.new_off = ring_tile_off(o, o->spare()); fp.ystride = (uint32_t)o->tile_stride;
     fp.alpha = o->alpha; fp.coef = o->coef; fp.scale = o->scale;
-    for (int i = 0; i < kFusedMaxK; ++i) {                // entries >= k: any valid vector (zero coefficient)
-        const int slot = o->slot_of(i < k ? i : 0);
-        fp.soff[i] = (uint32_t)((uint64_t)(2 * slot) * (uint64_t)o->tile_stride);
-    }
+    for (int i = 0; i < kFusedMaxK; ++i) fp.soff[i] = ring_tile_off(o, o->slot_of(i < k ? i : 0));   // entries >= k: any valid vector (zero coefficient)
     fp.gram_partials = o->gram_partials;
     fp.obj_partials = c.problem->scratch;
     fp.changed = c.flag();
@@ -3198,37 +3317,12 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
     double t = 1.0;
     for (int attempt = 0;; ++attempt) {
     fp.t = (T)t; fp.t_half = (T)round_to_dtype(c.dtype, t * 0.5);
-    if (!c.flag_armed) DZO_HIP(hipMemsetAsync(c.flag(), 0, sizeof(int32_t), s));
-    c.flag_armed = false;
-    {
-        DZO_TIMED(attempt == 0 ? "lbfgs_single_pass" : "lbfgs_single_pass_retry", s);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, fp);
-    }
-    {
-        // :128 / :139 on the device (outcome to pinned host memory) as one block of the launch that also sums the
-        // Gram partials; then, enqueued BEFORE the host knows the outcome and gated on that decision, the scalar
-        // part of the NEXT two-loop (recurrence on the post-push history), so the GPU has work while the host
-        // round-trips and the next step starts with its scalars ready.
-        const int sv_newest = o->newest, sv_k = o->k;
-        o->newest = o->spare(); o->k = fp.k_next;         // as lbfgs_finish_push will leave them
-        double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
-        {
-            DZO_TIMED("lbfgs_gram_reduce", s);
-            const int nvals = kGramValues * o->k;
-            DecideArgs da = decide_args(c, fp.obj_partials, grid, 1.0);
-            da.partials2 = fp.obj_partials + grid;        // f(x + t/2 d)
-            hipLaunchKernelGGL(gram_reduce_decide_kernel, dim3(nvals + 1), dim3(kBlock), 0, s, (const double *)o->gram_partials, grid, vals,
-                               nvals, da);
-            c.flag_armed = true;
-        }
-        DZO_HIP(hipGetLastError());
-        int32_t rc = gram_finish_launch(o, 0, true, vals, true, c.status());
-        o->newest = sv_newest; o->k = sv_k;
-        DZO_TRY(rc);
-    }
+    DZO_TRY(pass_trial_launch(c, kern, grid, 0, fp, attempt));
+    DZO_TRY(gram_reduce_decide_launch(o, fp.k_next, fp.obj_partials, grid, nullptr));
+    DZO_TRY(next_scalars_gated(o, fp.k_next));
     DZO_TRY(core_wait_decision(c));
     // the host follows the DEVICE's decision (the gated kernels already acted on it): 0 reject, 1 accept, 2 stuck
-    const int32_t status = reinterpret_cast<int32_t *>(c.host + 3)[0];
+    const int32_t status = c.host_status();
     if (attempt == 0) { c.last_trials = 0; o->single_pass_steps += 1; }
     if (status == 2) {                                    // :128-131 (x_new == x_old everywhere; x and g were never written)
         c.is_stuck = true;
@@ -3236,19 +3330,13 @@ template <typename T> static int32_t lbfgs_step_single_pass(dzo_lbfgs_s *o) {
         // still the previous step's (= the newest pair of the ring; the pass wrote only spare slots)
         // (blocked ring: delta_gradient is gathered from the newest pair's tiles unless dg_lin still holds it)
         if (o->lin_stale && o->k > 0) { ring_gather<T>(o, o->y_slot_v(o->newest), o->dg_lin); o->lin_stale = false; }
-        DZO_HIP(hipMemcpyAsync(c.dx, c.x, (size_t)c.n * sizeof(T), hipMemcpyDeviceToDevice, s));
+        DZO_HIP(hipMemcpyAsync(c.dx, c.x, (size_t)c.n * sizeof(T), hipMemcpyDeviceToDevice, c.stream));
         DZO_HIP(hipGetLastError());
         return DZO_OK;
     }
     c.last_trials += 1;
-    const double f_new = round_to_dtype(c.dtype, c.host[0]);
-    if (status == 1) {                                    // :139-146 (f_new < f), and the kernel already did :478-480
-        c.df = round_to_dtype(c.dtype, f_new - c.f);
-        c.f = f_new;
-        DZO_TRY(lbfgs_finish_push(o, 0, true, true, true));   // rho of the new pair was set by the gated gram_finish; the pass wrote its tiles
-        o->spec_scalars = true;                           // alpha_sp / coef_sp / scale_sp hold the next step's scalars
-        o->gram_ready = false;
-        o->gram_stale = 0;
+    if (status == 1) {                                    // :139-146 (f_new < f)
+        DZO_TRY(pass_accept(o, round_to_dtype(c.dtype, c.host[0])));
         // the trial point and its gradient become the current ones: swap the buffers' roles
         std::swap(c.x, o->x_twin);
         std::swap(c.g, o->g_twin);
@@ -3322,22 +3410,12 @@ template <typename T> static void (*point_pass_kernel_for(dzo_lbfgs_s *o, bool f
 template <typename T> static int32_t lbfgs_materialize_d_t(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
     hipStream_t s = c.stream;
-    const int k = o->dview_k;
     FusedParams<T> fp;
-    memset(&fp, 0, sizeof(fp));
-    fp.n = c.n; fp.k = k; fp.k_next = 1; fp.t = (T)1; fp.t_half = (T)0.5;
-    fp.d = (T *)o->d; fp.store_d = 1;
-    fp.ring = (T *)o->S; fp.rowbytes = (uint32_t)o->rowbytes;
-    fp.new_off = (uint32_t)((uint64_t)(2 * o->spare()) * (uint64_t)o->tile_stride); fp.ystride = (uint32_t)o->tile_stride;   // (never written: no tile stores in this mode)
-    fp.alpha = o->alpha; fp.coef = o->coef; fp.scale = o->scale;
-    auto old_slot = [&](int j) { return ((o->dview_newest - j) % o->nslots + o->nslots) % o->nslots; };
-    for (int j = 0; j <= kFusedMaxK; ++j) fp.soff[j] = (uint32_t)((uint64_t)(2 * old_slot(j < k ? j : k)) * (uint64_t)o->tile_stride);
-    fp.gram_partials = o->gram_partials;                  // (consumed by the step's gated gram_finish; scratch here)
-    fp.obj_partials = c.problem->scratch;
-    fp.changed = c.flag();
+    fused_fill_params<T>(o, fp, o->dview_k, o->dview_newest);
+    fp.k_next = 1; fp.t = (T)1; fp.t_half = (T)0.5;
+    fp.store_d = 1;
+    // (the spare slot is never written and the Gram partials -- consumed by the step's gated gram_finish -- are scratch here:)
     fp.debug_skip = 1 | 64;                               // no pair dots, no tile stores (and with them no halo copies)
-    fp.dec = point_decor<T>(o->ring_dec);
-    fp.obj_lambda = (T)o->ring_obj_lambda;
     fp.stage_rows = 1;
     void (*kern)(FusedParams<T>) = point_pass_kernel_for<T>(o, false);
     DZO_REQUIRE(kern, DZO_ERR_STATE, "direction on demand: no point-pass kernel for history_length %d", o->m);
@@ -3363,7 +3441,6 @@ static int32_t lbfgs_materialize_d(dzo_lbfgs_s *o) {
 
 template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
     OptCore &c = o->core;
-    hipStream_t s = c.stream;
     const int k = o->k;
     void (*kern)(FusedParams<T>) = point_pass_kernel_for<T>(o, k == 0);
     DZO_REQUIRE(kern, DZO_ERR_STATE, "point pass: no kernel for history_length %d", o->m);   // (before anything is enqueued)
@@ -3372,20 +3449,8 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
         o->scalars_ready = false;
     }                                                     // (:463: the first step walks along the step_direction the constructor left)
     FusedParams<T> fp;
-    memset(&fp, 0, sizeof(fp));
-    fp.n = c.n; fp.k = k; fp.k_next = k < o->m ? k + 1 : o->m;
-    fp.d = (T *)o->d;
-    fp.ring = (T *)o->S; fp.rowbytes = (uint32_t)o->rowbytes;
-    fp.new_off = (uint32_t)((uint64_t)(2 * o->spare()) * (uint64_t)o->tile_stride); fp.ystride = (uint32_t)o->tile_stride;
-    fp.alpha = o->alpha; fp.coef = o->coef; fp.scale = o->scale;
-    for (int j = 0; j <= kFusedMaxK; ++j)                 // points beyond k: point k again (those pairs are zero)
-        fp.soff[j] = (uint32_t)((uint64_t)(2 * o->slot_of(j < k ? j : k)) * (uint64_t)o->tile_stride);
-    fp.gram_partials = o->gram_partials;
-    fp.obj_partials = c.problem->scratch;
-    fp.changed = c.flag();
+    fused_fill_params<T>(o, fp, k, o->newest);
     fp.debug_skip = tune_int("DZO_TUNE_SP_DEBUG", 0);
-    fp.dec = point_decor<T>(o->ring_dec);
-    fp.obj_lambda = (T)o->ring_obj_lambda;
     fp.store_d = 0;                                       // (step_direction is formed on demand: lbfgs_materialize_d)
     // the launch shape (dzo_lbfgs_plan.h); its knob is read per step
     const PointLaunch pl = point_pass_launch(c.n, c.dtype, o->m, k, o->point_sets, DZO_PP_REGRAD != 0, kPointStageRows,
@@ -3414,78 +3479,26 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
     DZO_REQUIRE(fused_params_ok<T>(fp, false), DZO_ERR_STATE, "point pass: a null operand (ring %p, d %p, scalars %p %p %p)",
                 (void *)fp.ring, (void *)fp.d, (const void *)fp.alpha, (const void *)fp.coef, (const void *)fp.scale);
     o->d_stale = false;                                   // (whatever was pending belonged to the previous step)
-    const int view_k = k, view_newest = o->newest;
-    auto direction_pending = [&]() { if (k > 0) { o->d_stale = true; o->dview_k = view_k; o->dview_newest = view_newest; } };
+    const RingView view{k, o->newest};
+    // the L2 decorator's term of the objective (:232  + lambda * norm2(x), both candidates) follows the objective's partials
+    const double *l2_partials = o->ring_dec.l2 != 0.0 ? fp.obj_partials + 2 * pgrid : nullptr;
     c.last_trials = 0;
     o->single_pass_steps += 1;
     int64_t halvings = 0;
     double t = 1.0;
     for (int attempt = 0;; ++attempt) {
         fp.t = (T)t; fp.t_half = (T)round_to_dtype(c.dtype, t * 0.5);
-        if (!c.flag_armed) DZO_HIP(hipMemsetAsync(c.flag(), 0, sizeof(int32_t), s));
-        c.flag_armed = false;
-        {
-            DZO_TIMED(attempt == 0 ? "lbfgs_single_pass" : "lbfgs_single_pass_retry", s);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), stage_bytes, s, fp);
-        }
-        {
-            // decision + Gram reduction in one launch, then the gated recurrence for the next step (as
-            // lbfgs_step_single_pass)
-            const int sv_newest = o->newest, sv_k = o->k;
-            o->newest = o->spare(); o->k = fp.k_next;
-            double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
-            {
-                DZO_TIMED("lbfgs_gram_reduce", s);
-                const int nvals = kGramValues * o->k;
-                DecideArgs da = decide_args(c, fp.obj_partials, pgrid, 1.0);
-                da.partials2 = fp.obj_partials + pgrid;   // f(x + t/2 d)
-                if (o->ring_dec.l2 != 0.0) {              // :232  + lambda * norm2(x), both candidates
-                    da.l2_partials = fp.obj_partials + 2 * pgrid; da.l2_partials2 = fp.obj_partials + 3 * pgrid;
-                    da.l2_lambda = o->ring_dec.l2;
-                }
-                hipLaunchKernelGGL(gram_reduce_decide_kernel, dim3(nvals + 1), dim3(kBlock), 0, s, (const double *)o->gram_partials, pgrid, vals,
-                                   nvals, da);
-                c.flag_armed = true;
-            }
-            DZO_HIP(hipGetLastError());
-            int32_t rc = gram_finish_launch(o, 0, true, vals, true, c.status());
-            o->newest = sv_newest; o->k = sv_k;
-            DZO_TRY(rc);
-        }
+        DZO_TRY(pass_trial_launch(c, kern, grid, stage_bytes, fp, attempt));
+        DZO_TRY(gram_reduce_decide_launch(o, fp.k_next, fp.obj_partials, pgrid, l2_partials));
+        DZO_TRY(next_scalars_gated(o, fp.k_next));
         DZO_TRY(core_wait_decision(c));
-        const int32_t status = reinterpret_cast<int32_t *>(c.host + 3)[0];
-        if (status == 2) {                                // :128-131 (x_new == x_old everywhere)
-            c.is_stuck = true;
-            direction_pending();
-            // delta_point = x_old (:118), delta_gradient still the previous step's
-            if (o->k > 0) {
-                DZO_TRY(lbfgs_ensure_g(o, o->slot_of(0))); DZO_TRY(lbfgs_ensure_g(o, o->slot_of(1)));
-                ring_gather_diff<T>(o, o->y_slot_v(o->slot_of(0)), o->y_slot_v(o->slot_of(1)), o->dg_lin);
-            }
-            ring_gather<T>(o, o->s_slot_v(o->newest), o->dx_lin);
-            DZO_HIP(hipGetLastError());
-            o->lin_stale = false;
-            return DZO_OK;
-        }
+        const int32_t status = c.host_status();
+        if (status == 2) return points_end_stuck<T>(o, view);   // :128-131 (x_new == x_old everywhere)
         c.last_trials += 1;
-        const double f_new = round_to_dtype(c.dtype, c.host[0]);
-        if (status == 1) {                                // :139-146, and the pass already did :478-480
-            c.df = round_to_dtype(c.dtype, f_new - c.f);
-            c.f = f_new;
-            {
-                // the spare slot becomes point 0: its gradient tiles are the new gradient only if this launch wrote them
-                // (the first step's kernel and builds that stream the gradients do; the recomputing pass does not)
-                const bool wrote_g = (k == 0) || DZO_PP_REGRAD == 0;
-                if (wrote_g) o->g_valid |= 1u << o->spare(); else o->g_valid &= ~(1u << o->spare());
-            }
-            DZO_TRY(lbfgs_finish_push(o, 0, true, true, true));   // rho by the gated gram_finish; the pass wrote the new point's tiles
-            o->spec_scalars = true;
-            o->gram_ready = false;
-            o->gram_stale = 0;
-            o->xg_lin_stale = true;
-            direction_pending();
-            lbfgs_mark_unsettled(o);
-            return DZO_OK;
+        if (status == 1) {
+            // the spare slot's gradient tiles are the new gradient only if this launch wrote them (the first step's kernel and
+            // builds that stream the gradients do; the recomputing pass does not)
+            return points_accept(o, view, round_to_dtype(c.dtype, c.host[0]), (k == 0) || DZO_PP_REGRAD == 0);
         }
         // rejected (:151-152)
         if (attempt == 0) o->single_pass_rejections += 1;
@@ -3501,18 +3514,7 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
             c.last_trials += 1;
             go_on = halve();
         }
-        if (!go_on) {                                     // build-added escape from the NaN loop
-            c.is_stuck = true;
-            direction_pending();
-            ring_gather<T>(o, o->s_slot_v(o->newest), o->dx_lin);
-            if (o->k > 0) {
-                DZO_TRY(lbfgs_ensure_g(o, o->slot_of(0))); DZO_TRY(lbfgs_ensure_g(o, o->slot_of(1)));
-                ring_gather_diff<T>(o, o->y_slot_v(o->slot_of(0)), o->y_slot_v(o->slot_of(1)), o->dg_lin);
-            }
-            DZO_HIP(hipGetLastError());
-            o->lin_stale = false;
-            return DZO_OK;
-        }
+        if (!go_on) return points_end_stuck<T>(o, view);  // build-added escape from the NaN loop
         o->single_pass_retries += 1;
     }
 }
@@ -3521,15 +3523,15 @@ template <typename T> static int32_t lbfgs_step_points(dzo_lbfgs_s *o) {
 template <typename T> static void lse_fill_params(dzo_lbfgs_s *o, LseParams<T> &lp, int k, int view_newest) {
     OptCore &c = o->core;
     memset(&lp, 0, sizeof(lp));
-    auto slot_at = [&](int j) { return ((view_newest - j) % o->nslots + o->nslots) % o->nslots; };
     lp.n = c.n; lp.k = k; lp.k_next = k < o->m ? k + 1 : o->m;
     lp.ring = (T *)o->S; lp.rowbytes = (uint32_t)o->rowbytes;
     for (int j = 0; j <= kLseMaxK; ++j) {
-        const int sl = slot_at(j < k ? j : k);
-        lp.soff[j] = (uint32_t)((uint64_t)(2 * sl) * (uint64_t)o->tile_stride);
+        const int sl = ring_view_slot(o, view_newest, j < k ? j : k);
+        lp.soff[j] = ring_tile_off(o, sl);
         lp.slot[j] = (uint8_t)sl;
     }
-    lp.c_off = (uint32_t)((uint64_t)(2 * o->nslots) * (uint64_t)o->tile_stride);
+    lp.new_off = ring_tile_off(o, o->spare()); lp.new_slot = (uint8_t)o->spare();
+    lp.c_off = ring_tile_off(o, o->nslots);
     lp.pscal = o->pscal; lp.lambda = o->ring_obj_lambda;
     lp.alpha = o->alpha; lp.coef = o->coef; lp.scale = o->scale;
     lp.d = (T *)o->d;
@@ -3557,7 +3559,6 @@ template <typename T> static int32_t lbfgs_materialize_d_lse(dzo_lbfgs_s *o) {
     LseParams<T> lp;
     lse_fill_params<T>(o, lp, o->dview_k, o->dview_newest);
     lp.t = (T)1; lp.store_d = 1; lp.store_tile = 0;
-    lp.new_off = (uint32_t)((uint64_t)(2 * o->spare()) * (uint64_t)o->tile_stride); lp.new_slot = (uint8_t)o->spare();
     auto kern = lse_trial_kernel_for<T>(o, false);
     const int grid = lse_grid<T>(o, (const void *)kern);
     {
@@ -3581,90 +3582,49 @@ template <typename T> static int32_t lbfgs_step_points_lse(dzo_lbfgs_s *o) {
     }
     LseParams<T> lp;
     lse_fill_params<T>(o, lp, k, o->newest);
-    lp.new_off = (uint32_t)((uint64_t)(2 * o->spare()) * (uint64_t)o->tile_stride); lp.new_slot = (uint8_t)o->spare();
     lp.store_d = 0; lp.store_tile = 1;
     auto kern = lse_trial_kernel_for<T>(o, k == 0);
     const int grid = lse_grid<T>(o, (const void *)kern);
     o->d_stale = false;
-    const int view_k = k, view_newest = o->newest;
-    auto direction_pending = [&]() { if (k > 0) { o->d_stale = true; o->dview_k = view_k; o->dview_newest = view_newest; } };
-    auto stuck_fields = [&]() -> int32_t {                // delta_point = x_old (:118), delta_gradient still the previous step's
-        if (o->k > 0) {
-            DZO_TRY(lbfgs_ensure_g(o, o->slot_of(0))); DZO_TRY(lbfgs_ensure_g(o, o->slot_of(1)));
-            ring_gather_diff<T>(o, o->y_slot_v(o->slot_of(0)), o->y_slot_v(o->slot_of(1)), o->dg_lin);
-        }
-        ring_gather<T>(o, o->s_slot_v(o->newest), o->dx_lin);
-        DZO_HIP(hipGetLastError());
-        o->lin_stale = false;
-        return DZO_OK;
-    };
+    const RingView view{k, o->newest};
     c.last_trials = 0;
     o->single_pass_steps += 1;
     int64_t halvings = 0;
     double t = 1.0;
     for (int attempt = 0;; ++attempt) {
         lp.t = (T)t;
-        if (!c.flag_armed) DZO_HIP(hipMemsetAsync(c.flag(), 0, sizeof(int32_t), s));
-        c.flag_armed = false;
-        {
-            DZO_TIMED(attempt == 0 ? "lbfgs_single_pass" : "lbfgs_single_pass_retry", s);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, lp);
-        }
+        DZO_TRY(pass_trial_launch(c, kern, grid, 0, lp, attempt));
         {
             DZO_TIMED("lbfgs_lse_decide", s);
             DecideArgs da = decide_args(c, nullptr, 0, 1.0);
             hipLaunchKernelGGL(lse_decide_kernel, dim3(1), dim3(kBlock), 0, s, (const double *)lp.partials, grid, o->pscal, (int)lp.slot[0], (int)lp.new_slot,
-                               o->ring_obj_lambda, c.dtype == DZO_F32 ? 1 : 0, da);
+                               o->ring_obj_lambda, f32_flag(c), da);
             c.flag_armed = true;
         }
         DZO_HIP(hipGetLastError());
         DZO_TRY(core_wait_decision(c));
-        const int32_t status = reinterpret_cast<int32_t *>(c.host + 3)[0];
-        if (status == 2) {                                // :128-131
-            c.is_stuck = true;
-            direction_pending();
-            return stuck_fields();
-        }
+        const int32_t status = c.host_status();
+        if (status == 2) return points_end_stuck<T>(o, view);   // :128-131
         c.last_trials += 1;
         if (status == 1) {                                // :139-146; then the dots of the next two-loop over the k + 2 points
-            const double f_new = round_to_dtype(c.dtype, c.host[0]);
-            c.df = round_to_dtype(c.dtype, f_new - c.f);
-            c.f = f_new;
             auto dk = lse_dots_kernel_for<T>(o);
             const int dgrid = lse_grid<T>(o, (const void *)dk);
             {
                 DZO_TIMED("lbfgs_lse_dots", s);
                 hipLaunchKernelGGL(dk, dim3(dgrid), dim3(kBlock), 0, s, lp);
             }
-            const int sv_newest = o->newest, sv_k = o->k;
-            o->newest = o->spare(); o->k = lp.k_next;     // as lbfgs_finish_push will leave them
-            double *vals = o->gram_partials + (size_t)kGramValues * kMaxHistory * o->gram_grid * kWaves;
             {
                 DZO_TIMED("lbfgs_gram_reduce", s);
-                hipLaunchKernelGGL(gram_reduce_kernel, dim3(kGramValues * o->k), dim3(kBlock), 0, s, o->gram_partials, dgrid, vals, kGramValues * o->k,
-                                   (const double *)nullptr, 0, (double *)nullptr, 0);
+                gram_reduce_plain(o, o->gram_partials, dgrid, gram_vals(o), kGramValues * lp.k_next);
             }
             DZO_HIP(hipGetLastError());
-            int32_t rc = gram_finish_launch(o, 0, true, vals, true, c.status());   // (status is 1: the gate only selects the *_sp scalar set)
-            o->newest = sv_newest; o->k = sv_k;
-            DZO_TRY(rc);
-            o->g_valid &= ~(1u << o->spare());            // (the trial pass writes no gradient tiles: formed on demand)
-            DZO_TRY(lbfgs_finish_push(o, 0, true, true, true));
-            o->spec_scalars = true;
-            o->gram_ready = false;
-            o->gram_stale = 0;
-            o->xg_lin_stale = true;
-            direction_pending();
-            lbfgs_mark_unsettled(o);
-            return DZO_OK;
+            DZO_TRY(next_scalars_gated(o, lp.k_next));    // (status is 1: the gate only selects the *_sp scalar set)
+            // (the trial pass writes no gradient tiles: formed on demand)
+            return points_accept(o, view, round_to_dtype(c.dtype, c.host[0]), false);
         }
         if (attempt == 0) o->single_pass_rejections += 1;
         t = round_to_dtype(c.dtype, t * 0.5);             // :151-152
-        if (c.max_halvings > 0 && ++halvings >= c.max_halvings) {
-            c.is_stuck = true;
-            direction_pending();
-            return stuck_fields();
-        }
+        if (c.max_halvings > 0 && ++halvings >= c.max_halvings) return points_end_stuck<T>(o, view);
         o->single_pass_retries += 1;
     }
 }

@@ -48,6 +48,7 @@ struct OptCore {
     double *result() const { return ws + 2 * kMaxPartialBlocks; }          // [0]=f_new [1]=misc
     int32_t *flag() const { return reinterpret_cast<int32_t *>(ws + 2 * kMaxPartialBlocks + 4); }
     int32_t *status() const { return reinterpret_cast<int32_t *>(ws + 2 * kMaxPartialBlocks + 3); }  // 0 reject 1 accept 2 stuck
+    int32_t host_status() const { return reinterpret_cast<const int32_t *>(host + 3)[0]; }   // that word in the pinned mirror (valid after core_wait_decision)
     bool has_objective() const { return objective != nullptr || problem != nullptr; }
     bool has_gradient() const { return gradient != nullptr || problem != nullptr; }
 };

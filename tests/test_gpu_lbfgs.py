@@ -1133,6 +1133,18 @@ def test_log_sum_exp_point_ring_steps_match_the_oracle_from_the_same_state(n, m,
     _point_ring_steps_against_the_oracle(n, m, step0, dtype, {}, kind="lse")
 
 
+def _point_ring_problem(n, dtype, decor, kind):
+    """Start point, the oracle's and the device's problem, and the centre of the log-sum-exp cases (None otherwise)."""
+    x0, cc = orc.rosenbrock_chain_x0(n, dtype), None
+    if kind == "lse":
+        cc = (orc.pcg_fill(n, 6) - 0.5).astype(dtype)                              # SURVEY 8(d) C4: c = u - 1/2 (seed 6), lambda = 1e-2
+        x0 = (0.5 * (orc.pcg_fill(n, 8) - 0.5)).astype(dtype)
+        return x0, orc.Problem(orc.LSE, n, dtype, c=cc, lam=1e-2), dzo.Problem(dzo.LSE, n, dtype, c=cc, lam=1e-2), cc
+    if kind == "qchain":
+        return x0, orc.Problem(orc.QUADRATIC_CHAIN, n, dtype, lam=0.05), dzo.Problem(dzo.QUADRATIC_CHAIN, n, dtype, lam=0.05), cc
+    return x0, orc.Problem(orc.ROSENBROCK_CHAIN, n, dtype, **decor), dzo.Problem(dzo.ROSENBROCK_CHAIN, n, dtype, **decor), cc
+
+
 def _point_ring_steps_against_the_oracle(n, m, step0, dtype, decor, kind="rosen"):
     """The default optimizer on the built-in chained Rosenbrock keeps the last k + 1 POINTS and GRADIENTS tile-major
     (ring_layout == 2) and forms the pairs in registers; every trial of a step, the first step included, is one pass.
@@ -1140,21 +1152,10 @@ def _point_ring_steps_against_the_oracle(n, m, step0, dtype, decor, kind="rosen"
     the ORACLE follows: before every step it is given the GPU's point, gradient, objective value and history -- read
     through the public getters, which gather them without leaving the point layout -- and both take the step.
     step0 = 300 makes first trials fail (several halvings, all on the same pass)."""
-    x0 = orc.rosenbrock_chain_x0(n, dtype)
     if dtype == np.float32:
         orc.set_dot_mode(orc.DOT_WIDE)                    # the device sums in fp64
     try:
-        if kind == "lse":
-            cc = (orc.pcg_fill(n, 6) - 0.5).astype(dtype)                          # SURVEY 8(d) C4: c = u - 1/2 (seed 6), lambda = 1e-2
-            x0 = (0.5 * (orc.pcg_fill(n, 8) - 0.5)).astype(dtype)
-            ref_p = orc.Problem(orc.LSE, n, dtype, c=cc, lam=1e-2)
-            dev_p = dzo.Problem(dzo.LSE, n, dtype, c=cc, lam=1e-2)
-        elif kind == "qchain":
-            ref_p = orc.Problem(orc.QUADRATIC_CHAIN, n, dtype, lam=0.05)
-            dev_p = dzo.Problem(dzo.QUADRATIC_CHAIN, n, dtype, lam=0.05)
-        else:
-            ref_p = orc.Problem(orc.ROSENBROCK_CHAIN, n, dtype, **decor)
-            dev_p = dzo.Problem(dzo.ROSENBROCK_CHAIN, n, dtype, **decor)
+        x0, ref_p, dev_p, cc = _point_ring_problem(n, dtype, decor, kind)
         ref = orc.LBFGS(ref_p, x0.copy(), step0, m)
         opt = dzo.LBFGSOptimizer(None, dev_p, None, dzo.DeviceArray.from_host(x0), step0, m)
         assert opt.ring_layout == 2
@@ -1438,6 +1439,107 @@ def test_lbfgs_stuck_step_leaves_the_reference_deltas(n, m, layout, monkeypatch)
         assert opt.iteration_count == it and np.array_equal(opt.delta_point.to_host(), x)
     finally:
         orc.set_threads(1)
+
+
+# ---- the halving limit (set_max_halvings) ends a step on the point ring: the other exit of the trial loops, with the same fields
+def _oracle_follows(opt, ref, n, dtype):
+    """The device's state, read through the getters (which gather it without leaving the point layout), installed into the
+    oracle; returned as (x, g, f, S, Y)."""
+    k = opt.history_count
+    S = np.stack([h.to_host() for h in opt.delta_point_history]) if k else np.zeros((0, n), dtype)
+    Y = np.stack([h.to_host() for h in opt.delta_gradient_history]) if k else np.zeros((0, n), dtype)
+    x, g, f = opt.current_point.to_host(), opt.current_gradient.to_host(), opt.current_objective_value
+    ref.install_state(x, g, f, S, Y, opt.rho_history[:k], opt.iteration_count)
+    return x, g, f, S, Y
+
+
+def _limit_pair(kind, n, m, dtype, decor):
+    x0, ref_p, dev_p, _ = _point_ring_problem(n, dtype, decor, kind)
+    ref = orc.LBFGS(ref_p, x0.copy(), 300.0, m)
+    opt = dzo.LBFGSOptimizer(None, dev_p, None, dzo.DeviceArray.from_host(x0), 300.0, m)
+    assert opt.ring_layout == 2
+    return opt, ref
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["float64", "float32"])
+@pytest.mark.parametrize("kind,n,m", [("rosen", 16, 3), ("rosen", 385, 5), ("qchain", 385, 5), ("lse", 16, 3), ("lse", 385, 5)])
+def test_halving_limit_ends_the_first_step_on_the_point_ring(kind, n, m, dtype):
+    """initial_step_length = 300 and a limit of 3 halvings: the first step (k = 0, the FIRST kernels) finds no decrease in its
+    three trials and ends stuck through the limit, not through x + t d == x.  Everything is as before the step, bit for bit,
+    and delta_point = x_old (:118)."""
+    if dtype == np.float32:
+        orc.set_dot_mode(orc.DOT_WIDE)
+    try:
+        opt, ref = _limit_pair(kind, n, m, dtype, {})
+        opt.set_max_halvings(3); ref.set_max_halvings(3)
+        x0, g0, f0, _, _ = _oracle_follows(opt, ref, n, dtype)
+        dg0 = opt.delta_gradient.to_host()
+        opt.step(); ref.step()
+        assert opt.ring_layout == 2
+        assert ref.is_stuck and ref.last_trials == 3 and ref.iteration_count == 0
+        for again in (False, True):                            # the second round: after one more step(), which changes nothing
+            assert opt.is_stuck and opt.last_trials == 3 and opt.iteration_count == 0 and opt.history_count == 0
+            assert np.array_equal(opt.current_point.to_host(), x0) and np.array_equal(opt.current_gradient.to_host(), g0)
+            assert opt.current_objective_value == f0
+            assert np.array_equal(opt.delta_point.to_host(), x0)                   # :118
+            assert np.array_equal(opt.delta_gradient.to_host(), dg0)               # untouched
+            if not again:
+                opt.step()
+                assert opt.ring_layout == 2
+    finally:
+        orc.set_dot_mode(orc.DOT_SEQUENTIAL)
+
+
+@pytest.mark.parametrize("dtype", [np.float64], ids=["float64"])      # (fp32: see the docstring)
+@pytest.mark.parametrize("kind,n,m,decor", [("rosen", 16, 3, None), ("rosen", 385, 5, None), ("rosen", 4099, 6, None), ("lse", 16, 3, None),
+                                            ("rosen", 385, 5, "all")])
+def test_halving_limit_ends_a_steady_state_step_on_the_point_ring(kind, n, m, decor, dtype):
+    """m + 3 steps under the default limit (initial_step_length = 300: rejected trials on the way), then a limit of one halving:
+    the first step whose trial at t = 1 is no decrease ends stuck through the limit with last_trials == 1, on the device and in
+    the oracle, and leaves the fields of test_lbfgs_stuck_step_leaves_the_reference_deltas.
+    The five cases in fp32 are left out: every field below held bit for bit there as well (limit exits after 4, 3, 3, 3 and 1
+    further steps, as in fp64), but the direction on demand differs from the oracle's by 2.1e-7, 2.4e-8, 8.1e-8, 8.9e-8 and
+    9.5e-8 relative L2 -- fp32 rounding, above the 1e-9 of this test, before the shared host pieces and after them alike."""
+    if dtype == np.float32:
+        orc.set_dot_mode(orc.DOT_WIDE)
+    try:
+        opt, ref = _limit_pair(kind, n, m, dtype, _DECOR_SETS[decor] if decor else {})
+        for it in range(m + 3):
+            _oracle_follows(opt, ref, n, dtype)
+            opt.step(); ref.step()
+            assert opt.ring_layout == 2 and not opt.is_stuck and not ref.is_stuck, it
+        opt.set_max_halvings(1); ref.set_max_halvings(1)
+        for further in range(1, 11):                           # (within 10 further steps, or the case fails)
+            x, g, f, S, Y = _oracle_follows(opt, ref, n, dtype)
+            it, k = opt.iteration_count, opt.history_count
+            dg_before = opt.delta_gradient.to_host()
+            ref.delta_gradient[:] = dg_before                  # (a field the step may or may not touch: installed as well)
+            opt.step(); ref.step()
+            assert opt.ring_layout == 2
+            assert opt.is_stuck == ref.is_stuck, further       # stuck on the same step
+            if opt.is_stuck:
+                break
+        assert opt.is_stuck and ref.is_stuck, "no step ended by the halving limit"
+        assert opt.last_trials == 1 and ref.last_trials == 1
+        assert it == m + 3 + further - 1
+        e_d = rel(opt.step_direction.to_host(), ref.step_direction)                # formed on demand after the exit
+        print(f"limit exit after {further} further steps, direction differs from the oracle's by {e_d:.3e}")
+        for again in (False, True):                            # the second round: after one more step(), which changes nothing
+            assert opt.is_stuck and opt.iteration_count == it and ref.iteration_count == it
+            assert np.array_equal(opt.current_point.to_host(), x) and np.array_equal(opt.current_gradient.to_host(), g)   # :151 restored
+            assert opt.current_objective_value == f
+            assert np.array_equal(opt.delta_point.to_host(), x)                    # :118
+            assert np.array_equal(opt.delta_gradient.to_host(), dg_before) and np.array_equal(dg_before, Y[0])
+            assert opt.history_count == k
+            for i in range(k):
+                assert np.array_equal(opt.delta_point_history[i].to_host(), S[i]) and np.array_equal(opt.delta_gradient_history[i].to_host(), Y[i])
+            if not again:
+                opt.step()
+                assert opt.ring_layout == 2
+        assert np.array_equal(ref.current_point, x) and np.array_equal(ref.delta_point, x) and np.array_equal(ref.delta_gradient, Y[0])
+        assert e_d <= 1e-9
+    finally:
+        orc.set_dot_mode(orc.DOT_SEQUENTIAL)
 
 
 # ------------------------------------------------------------------------------ backend asserts (a8)
