@@ -193,6 +193,12 @@ ABI = {
     "dzo_lbfgs_batch_set_max_halvings": [_vp, _i64], "dzo_lbfgs_batch_step": [_vp, _i32, _P(_i32)],
     "dzo_lbfgs_batch_count_active": [_vp, _P(_i64)], "dzo_lbfgs_batch_get_ptr": [_vp, _i32, _P(_vp)],
     "dzo_lbfgs_batch_read": [_vp, _i32, _vp], "dzo_pairwise_batch_energy_gradient": [_i32, _i64, _i64, _i32, _vp, _vp, _vp],
+    "dzo_sphere_batch_project": [_i64, _i64, _i32, _vp],
+    "dzo_sphere_batch_energy_gradient": [_i32, _i64, _i64, _i32, _vp, _vp, _vp, _i32],
+    "dzo_sphere_lbfgs_batch_create": [_i32, _i64, _i64, _i32, _vp, _dbl, _i32, _P(_vp)], "dzo_sphere_lbfgs_batch_destroy": [_vp],
+    "dzo_sphere_lbfgs_batch_set_max_halvings": [_vp, _i64], "dzo_sphere_lbfgs_batch_step": [_vp, _i32, _P(_i32)],
+    "dzo_sphere_lbfgs_batch_count_active": [_vp, _P(_i64)], "dzo_sphere_lbfgs_batch_get_ptr": [_vp, _i32, _P(_vp)],
+    "dzo_sphere_lbfgs_batch_read": [_vp, _i32, _vp],
     "dzo_basin_hopping_create": [_i32, _i64, _i64, _i32, _vp, _P(_dbl), _P(_dbl), _dbl, _dbl, _i32, _i32, C.c_uint64, _P(_vp)],
     "dzo_basin_hopping_destroy": [_vp], "dzo_basin_hopping_set_max_halvings": [_vp, _i64], "dzo_basin_hopping_hop": [_vp, _i64, _i32],
     "dzo_basin_hopping_set_record": [_vp, _i64], "dzo_basin_hopping_get_ptr": [_vp, _i32, _P(_vp)],
@@ -782,6 +788,48 @@ class BatchedLBFGS(_BatchedOptimizer):
 
     step_directions = property(lambda self: self.read(LBFGS_BATCH_DIRECTIONS))
     history_counts = property(lambda self: self.read(LBFGS_BATCH_HISTORY_COUNTS))
+
+
+# ------------------------------------------------------------------------------ the Thomson problem: Riesz energy on the unit sphere
+SPHERE_ENERGY_RIESZ1 = 0
+
+
+def sphere_project_(points, n_particles):
+    """Projects every particle of every instance of ``points`` (``3 * n_particles * batch`` elements, instance b ``[x | y | z]``
+    at ``3 * n_particles * b``) onto the unit sphere, in place: ``p / |p|`` by one square root and three IEEE divisions, the
+    ``constraint_function!`` of ``SphereLBFGS``.  Returns ``points``."""
+    n, batch = _batch_of(points, n_particles, least=1)
+    _check(lib().dzo_sphere_batch_project(n, batch, _dt(points.dtype), points.ptr))
+    return points
+
+
+def sphere_energy_gradient(points, n_particles, gradients=None, tangent=True):
+    """Riesz (Coulomb, s = 1) energy (host array, one per instance) of every instance of ``points`` (the layout of
+    ``sphere_project_``; the points are taken as they are) and, into ``gradients`` when given, its gradient: the raw
+    ``riesz_gradient!`` of legacy/ExampleFunctions.jl:47-83 with ``tangent=False``, after ``constrain_riesz_gradient_sphere!``
+    (:361-374) with ``tangent=True``.  The device routine and the summation order of ``SphereLBFGS``."""
+    n, batch = _batch_of(points, n_particles, least=1)
+    e = DeviceArray(batch, points.dtype)
+    _check(lib().dzo_sphere_batch_energy_gradient(SPHERE_ENERGY_RIESZ1, n, batch, _dt(points.dtype), points.ptr, e.ptr,
+                                                  gradients.ptr if gradients is not None else None, 1 if tangent else 0))
+    return e.to_host()
+
+
+class SphereLBFGS(_BatchedOptimizer):
+    """``LBFGSOptimizer`` (src/DZOptimization.jl:321-509) with the unit sphere as its ``constraint_function!`` over many
+    configurations of ``n_particles`` charges at once (the Thomson problem): the constrained sibling of ``BatchedLBFGS``, with
+    its arrays and their shapes.  ``points`` is aliased and projected in place by the constructor (:412-414); every trial point
+    is projected before it is evaluated (:133-135) and every gradient is made tangent."""
+    _prefix = "dzo_sphere_lbfgs_batch_"
+    _what = BatchedLBFGS._what
+    _shape = BatchedLBFGS._shape
+
+    def __init__(self, points, n_particles, initial_step_length, history_length, energy=SPHERE_ENERGY_RIESZ1):
+        self.history_length = int(history_length)
+        self._create(points, n_particles, energy, float(initial_step_length), self.history_length)
+
+    step_directions = BatchedLBFGS.step_directions
+    history_counts = BatchedLBFGS.history_counts
 
 
 # ------------------------------------------------------------------------------ batched basin hopping over Lennard-Jones clusters
@@ -2844,7 +2892,8 @@ __all__ = [
     "calibrate_read_bandwidth", "selftest_fast_div", "calibrate_read_bandwidth_of", "DeviceArray", "axpy_", "axpby_", "rmul_",
     "copy_", "fill_", "dot", "norm", "isequal", "norm2", "inv_norm", "negate_", "scale_", "box_clamp_", "trial_point_",
     "calibrate_fma_rate", "pairwise_radial_energy", "pairwise_radial_gradient_", "pairwise_radial_hvp_",
-    "pairwise_radial_energy_delta", "ParallelTempering", "pairwise_batch_energy_gradient", "BatchedLBFGS", "BasinHopping",
+    "pairwise_radial_energy_delta", "ParallelTempering", "pairwise_batch_energy_gradient", "BatchedLBFGS", "sphere_project_",
+    "sphere_energy_gradient", "SphereLBFGS", "BasinHopping",
     "BatchedAdGD", "pairwise_batch_hvp", "pairwise_batch_hessian", "hessian_eigenvalues", "morse_index", "symeig_plan",
     "symmetric_batch_eigen", "hessian_spectrum", "LowestModes", "lowest_modes", "modefollow_apply", "ModeFollowing",
     "polish_minima", "find_saddles", "hybridef_apply", "HybridModeFollowing", "find_saddles_hybrid", "structure_fingerprints",

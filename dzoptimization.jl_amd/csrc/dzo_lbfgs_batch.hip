@@ -23,6 +23,7 @@
 // in a fixed order that depends on N only.  No floating-point atomic.  The recursion is the chain form of :430-451.
 #include "dzo_cluster.h"
 #include "dzo_quench_core.h"
+#include "dzo_quench_args.h"
 
 #include <cmath>
 #include <new>
@@ -30,20 +31,6 @@
 namespace dzo {
 
 constexpr int kQuenchMaxM = DZO_LBFGS_BATCH_MAX_HISTORY;
-
-template <typename T> struct QuenchArgs {
-    int N, m, steps;
-    int init;                  // eval kernels: also build the constructor's state (:381-397)
-    int64_t max_halvings;
-    T step_length;
-    T *x, *g, *d, *dx, *dg;    // (3N, batch)
-    T *f, *df;                 // batch
-    int32_t *stuck, *hcount, *halv;
-    int64_t *iters;
-    T *S, *Y;                  // (3N, m, batch), newest first
-    double *rho;               // (m, batch), newest first
-    T *slab;                   // BLOCK shape without room in LDS: 2 m 3N elements per instance
-};
 
 // ------------------------------------------------------------------------------ WAVE shape: grid batch, block 64
 // (each kernel of this file is its body as a __device__ function and the entry point that calls it: written into the
@@ -213,31 +200,9 @@ __global__ __launch_bounds__(kBlock) void quench_count_active_kernel(int64_t bat
 
 using namespace dzo;
 
-struct dzo_lbfgs_batch_s {
-    ClCore core;
-    int m = 0;
-    void *d = nullptr, *S = nullptr, *Y = nullptr, *slab = nullptr;
-    int32_t *hcount = nullptr;
-    double *rho = nullptr;
-    bool hist_lds = true;
-};
+struct dzo_lbfgs_batch_s : QaHandle {};                      // ClCore plus the ring arrays (dzo_quench_args.h)
 
 namespace dzo {
-
-static void qb_free(dzo_lbfgs_batch_s *h) { cl_free(h, {h->d, h->S, h->Y, h->slab, h->hcount, h->rho}); }
-
-template <typename T> static QuenchArgs<T> qb_args(const dzo_lbfgs_batch_s *h, int steps, int init, double step_length) {
-    const ClCore &c = h->core;
-    QuenchArgs<T> a;
-    a.N = c.N; a.m = h->m; a.steps = steps; a.init = init;
-    a.max_halvings = c.max_halvings;
-    a.step_length = (T)step_length;
-    a.x = (T *)c.x; a.g = (T *)c.g; a.d = (T *)h->d; a.dx = (T *)c.dx; a.dg = (T *)c.dg;
-    a.f = (T *)c.f; a.df = (T *)c.df;
-    a.stuck = c.stuck; a.hcount = h->hcount; a.halv = c.halv; a.iters = c.iters;
-    a.S = (T *)h->S; a.Y = (T *)h->Y; a.rho = h->rho; a.slab = (T *)h->slab;
-    return a;
-}
 
 template <typename T, typename F> static void qb_launch_eval(hipStream_t s, int64_t batch, const QuenchArgs<T> &a) {
     if (a.N <= 64) hipLaunchKernelGGL((quench_wave_eval_kernel<T, F>), dim3((unsigned)batch), dim3(64), 0, s, a);
@@ -259,7 +224,7 @@ template <typename T, typename F> static const void *qb_step_kernel(const dzo_lb
 }
 
 template <typename T, typename F> static void qb_launch_step(hipStream_t s, const dzo_lbfgs_batch_s *h, int steps) {
-    const QuenchArgs<T> a = qb_args<T>(h, steps, 0, 0.0);
+    const QuenchArgs<T> a = qa_args<T>(h, steps, 0, 0.0);
     const dim3 grid((unsigned)h->core.B);
     const size_t lds = h->core.lds_bytes;
     if (a.N <= 64) hipLaunchKernelGGL((quench_wave_step_kernel<T, F>), grid, dim3(64), lds, s, a);
@@ -273,30 +238,6 @@ int32_t cl_count_active(ClCore *c, hipStream_t s, int64_t *active) {
     DZO_HIP(hipMemcpyAsync(c->active_host, c->active_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     DZO_HIP(hipStreamSynchronize(s));
     *active = c->active_host[0];
-    return DZO_OK;
-}
-
-// `what` -> device address, bytes
-static int32_t qb_array(dzo_lbfgs_batch_s *h, int32_t what, void **p, size_t *bytes) {
-    const ClCore &c = h->core;
-    const size_t es = dtype_size(c.dtype), B = (size_t)c.B, n3 = 3 * (size_t)c.N, m = (size_t)h->m;
-    switch (what) {
-    case DZO_LBFGS_BATCH_POINTS: *p = c.x; *bytes = es * n3 * B; break;
-    case DZO_LBFGS_BATCH_GRADIENTS: *p = c.g; *bytes = es * n3 * B; break;
-    case DZO_LBFGS_BATCH_DIRECTIONS: *p = h->d; *bytes = es * n3 * B; break;
-    case DZO_LBFGS_BATCH_DELTA_POINTS: *p = c.dx; *bytes = es * n3 * B; break;
-    case DZO_LBFGS_BATCH_DELTA_GRADIENTS: *p = c.dg; *bytes = es * n3 * B; break;
-    case DZO_LBFGS_BATCH_OBJECTIVES: *p = c.f; *bytes = es * B; break;
-    case DZO_LBFGS_BATCH_DELTA_OBJECTIVES: *p = c.df; *bytes = es * B; break;
-    case DZO_LBFGS_BATCH_IS_STUCK: *p = c.stuck; *bytes = 4 * B; break;
-    case DZO_LBFGS_BATCH_ITERATION_COUNTS: *p = c.iters; *bytes = 8 * B; break;
-    case DZO_LBFGS_BATCH_HISTORY_COUNTS: *p = h->hcount; *bytes = 4 * B; break;
-    case DZO_LBFGS_BATCH_S: *p = h->S; *bytes = es * n3 * m * B; break;
-    case DZO_LBFGS_BATCH_Y: *p = h->Y; *bytes = es * n3 * m * B; break;
-    case DZO_LBFGS_BATCH_RHO: *p = h->rho; *bytes = 8 * m * B; break;
-    case DZO_LBFGS_BATCH_LAST_HALVINGS: *p = c.halv; *bytes = 4 * B; break;
-    default: set_error("unknown batched L-BFGS array %d", what); return DZO_ERR_INVALID;
-    }
     return DZO_OK;
 }
 
@@ -321,30 +262,16 @@ int32_t dzo_lbfgs_batch_create(int32_t radial, int64_t n_particles, int64_t batc
     DZO_REQUIRE(h, DZO_ERR_NOMEM, "out of host memory");
     ClCore &c = h->core;
     c.device = ctx().device; c.dtype = dtype; c.radial = radial; c.N = (int)n_particles; c.B = batch; c.x = points_dev;
-    h->m = history_length;
-    const size_t es = dtype_size(dtype), B = (size_t)batch, n3 = 3 * (size_t)n_particles, m = (size_t)history_length;
-    const size_t small = 16 * m;                              // rho | alpha
-    if (n_particles <= 64) {
-        c.lds_bytes = small + 2 * m * 3 * 64 * es;
-    } else {
-        const size_t vectors = small + 16 * kWaves + 5 * n3 * es;
-        h->hist_lds = vectors + 2 * m * n3 * es <= kClLdsMax;
-        c.lds_bytes = h->hist_lds ? vectors + 2 * m * n3 * es : vectors;
-    }
-    int32_t rc = cl_alloc({{&c.g, es * n3 * B}, {&h->d, es * n3 * B}, {&c.dx, es * n3 * B}, {&c.dg, es * n3 * B}, {&c.f, es * B}, {&c.df, es * B},
-                           {&h->S, es * n3 * m * B}, {&h->Y, es * n3 * m * B}, {h->hist_lds ? nullptr : &h->slab, 2 * es * n3 * m * B},
-                           {(void **)&c.stuck, 4 * B}, {(void **)&h->hcount, 4 * B}, {(void **)&c.halv, 4 * B}, {(void **)&c.iters, 8 * B},
-                           {(void **)&c.active_dev, 8}, {(void **)&h->rho, 8 * m * B}},
-                          "the batched L-BFGS state");
+    int32_t rc = qa_alloc(h, history_length);
     const void *step_kernel = nullptr;
     if (rc == DZO_OK) rc = [&]() -> int32_t { DZO_DISPATCH_RADIAL(radial, dtype, step_kernel = (qb_step_kernel<T, F>(h))); return DZO_OK; }();
     if (rc == DZO_OK)
         rc = cl_finish_create(&c, step_kernel, "batched L-BFGS state", "batched L-BFGS constructor", [&](hipStream_t s) -> int32_t {
             DZO_TIMED("lbfgs_batch_init", s);
-            DZO_DISPATCH_RADIAL(radial, dtype, (qb_launch_eval<T, F>(s, batch, qb_args<T>(h, 0, 1, initial_step_length))));
+            DZO_DISPATCH_RADIAL(radial, dtype, (qb_launch_eval<T, F>(s, batch, qa_args<T>(h, 0, 1, initial_step_length))));
             return DZO_OK;
         });
-    if (rc != DZO_OK) { qb_free(h); return rc; }
+    if (rc != DZO_OK) { qa_free(h); return rc; }
     *out = h;
     return DZO_OK;
 }
@@ -353,7 +280,7 @@ int32_t dzo_lbfgs_batch_destroy(dzo_lbfgs_batch_t h) {
     if (!h) return DZO_OK;
     DeviceScope scope(h->core.device);
     (void)hipStreamSynchronize(ctx().stream);
-    qb_free(h);
+    qa_free(h);
     return DZO_OK;
 }
 
@@ -371,9 +298,9 @@ int32_t dzo_lbfgs_batch_step(dzo_lbfgs_batch_t h, int32_t steps, int32_t *all_st
 
 int32_t dzo_lbfgs_batch_count_active(dzo_lbfgs_batch_t h, int64_t *active) { return cl_count(h, active); }
 
-int32_t dzo_lbfgs_batch_get_ptr(dzo_lbfgs_batch_t h, int32_t what, void **ptr_dev) { return cl_get_ptr(h, qb_array, what, ptr_dev); }
+int32_t dzo_lbfgs_batch_get_ptr(dzo_lbfgs_batch_t h, int32_t what, void **ptr_dev) { return cl_get_ptr(h, qa_array, what, ptr_dev); }
 
-int32_t dzo_lbfgs_batch_read(dzo_lbfgs_batch_t h, int32_t what, void *out_host) { return cl_read(h, qb_array, what, out_host); }
+int32_t dzo_lbfgs_batch_read(dzo_lbfgs_batch_t h, int32_t what, void *out_host) { return cl_read(h, qa_array, what, out_host); }
 
 // objective_function and gradient_function! of every instance (:416-421), by the optimizer's own device routine
 int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, int64_t batch, int32_t dtype, const void *points_dev,

@@ -95,6 +95,26 @@ template <typename T, int RHO> struct MorseRadial {
     }
 };
 
+// The Riesz (Coulomb, s = 1) pair term 1 / r of legacy/ExampleFunctions.jl:30-83, as functions of r2 like the above:
+//   r = sqrt(r2) (IEEE), inv_r = 1 / r
+//   energy = inv_r
+//   first  = -0.5 * (inv_r / r2)                  inv_r / r2 is the reference's inv_dist_cubed (:62)
+//   second = 0.75 * ((inv_r / r2) / r2)
+// The scaling by 1/2 and the caller's doubling are exact, so a gradient term 2 first (r_i - r_j) has the bits of the reference's
+// dist * inv_dist_cubed.  At r2 = 0 all three are infinite or NaN and are dropped by the caller's select.  Not a DZO_RADIAL_*:
+// only the kernels of dzo_sphere.hip use it, and it does not pass through DZO_DISPATCH_RADIAL.
+template <typename T> struct RieszRadial {
+    static __device__ __forceinline__ T energy(T r2) { return T(1) / pw_sqrt<T>(r2); }
+    static __device__ __forceinline__ T first(T r2) {
+        const T inv_r = T(1) / pw_sqrt<T>(r2);
+        return T(-0.5) * (inv_r / r2);
+    }
+    static __device__ __forceinline__ T second(T r2) {
+        const T inv_r = T(1) / pw_sqrt<T>(r2);
+        return T(0.75) * ((inv_r / r2) / r2);
+    }
+};
+
 // (radial, dtype) -> (T, F): the statement runs with `using T` and `using F` of the selected pair; an unknown selector or type
 // leaves the calling function with DZO_ERR_INVALID (pw_check_args has the message for callers that check first).  Every
 // launch and every kernel-pointer lookup that depends on the radial goes through this one table.

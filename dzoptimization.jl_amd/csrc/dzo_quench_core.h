@@ -10,6 +10,40 @@
 
 namespace dzo {
 
+// ------------------------------------------------------------------------------ constraint policies
+// constraint_function! of take_backtracking_step! (:133-135) as the last template argument of qc_wave_run / qc_block_run: two
+// per-particle operations, both local to the lane or thread that owns the particle.  Inside a trial, as :124-139: form the trial
+// by the fma, run the stuck test on the UNPROJECTED trial, project, evaluate, make the trial's gradient tangent, compare energies.
+// On acceptance delta_point is projected-new minus old and delta_gradient the difference of tangent gradients.
+// QcFree: constraint_function! = nothing; the two run functions compile to the code they had without the parameter.
+struct QcFree {
+    static constexpr bool kConstrained = false;
+    template <typename T> static __device__ __forceinline__ void project(bool, T &, T &, T &) {}
+    template <typename T> static __device__ __forceinline__ void tangent(T, T, T, T &, T &, T &) {}
+};
+// QcUnitSphere: every particle on the unit sphere.  project is p / |p| with r = sqrt(pw_r2(x, y, z)) and three IEEE divisions;
+// it always reports success (a particle on the origin becomes NaN, the objective NaN, `Et < E` false: the step backtracks).
+// A particle that is not `live` (the padding lanes of the WAVE shape, which hold zeros that lane_read feeds to dropped pairs) is
+// left alone by a select, never by a branch around the divisions.  tangent is constrain_riesz_gradient_sphere!
+// (legacy/ExampleFunctions.jl:361-374), operation for operation: overlap = x gx + y gy + z gz summed in that order, unfused;
+// g -= overlap p, unfused.
+struct QcUnitSphere {
+    static constexpr bool kConstrained = true;
+    template <typename T> static __device__ __forceinline__ void project(bool live, T &x, T &y, T &z) {
+        const T r = pw_sqrt<T>(pw_r2(x, y, z));
+        const T px = pw_pin(x / r), py = pw_pin(y / r), pz = pw_pin(z / r);
+        x = live ? px : x;
+        y = live ? py : y;
+        z = live ? pz : z;
+    }
+    template <typename T> static __device__ __forceinline__ void tangent(T x, T y, T z, T &gx, T &gy, T &gz) {
+        const T overlap = x * gx + y * gy + z * gz;
+        gx = gx - overlap * x;
+        gy = gy - overlap * y;
+        gz = gz - overlap * z;
+    }
+};
+
 // ------------------------------------------------------------------------------ WAVE shape: lane i holds particle i
 // the optimizer's state of one instance: point, gradient, step_direction, delta_point, delta_gradient, the two objective values
 // and the counters.  The (s, y) ring is in LDS: rho[m] | alpha[m] as doubles, element (slot p, component c) of a lane at
@@ -33,7 +67,7 @@ template <typename T> __device__ __forceinline__ bool qc_wave_first_direction(T 
 }
 
 // up to `steps` calls of step!() of an instance that is not stuck; returns is_stuck
-template <typename T, typename F>
+template <typename T, typename F, typename C = QcFree>
 __device__ __forceinline__ bool qc_wave_run(int N, int m, int lane, int steps, int64_t max_halvings, QcWave<T> &w, double *rho, double *alpha,
                                             T *hS, T *hY) {
     T x = w.x, y = w.y, z = w.z, gx = w.gx, gy = w.gy, gz = w.gz, px = w.px, py = w.py, pz = w.pz;
@@ -71,10 +105,12 @@ __device__ __forceinline__ bool qc_wave_run(int N, int m, int lane, int steps, i
         T t = T(1);
         int h = 0;
         for (;;) {
-            const T xt = dfma<T>(t, px, x0), yt = dfma<T>(t, py, y0), zt = dfma<T>(t, pz, z0);   // :124
+            T xt = dfma<T>(t, px, x0), yt = dfma<T>(t, py, y0), zt = dfma<T>(t, pz, z0);   // :124
             if (__all(is_equal(xt, x0) && is_equal(yt, y0) && is_equal(zt, z0))) { stuck = true; break; }   // :128
+            if constexpr (C::kConstrained) C::template project<T>(lane < N, xt, yt, zt);   // :133-135
             T Et, tx, ty, tz;
             cl_wave_eval<T, F>(N, lane, xt, yt, zt, Et, tx, ty, tz);
+            if constexpr (C::kConstrained) C::template tangent<T>(xt, yt, zt, tx, ty, tz);
             if (Et < E) {                                    // :139
                 dE = Et - E; E = Et;                         // :142-144
                 sx = xt - x0; sy = yt - y0; sz = zt - z0;    // :145
@@ -129,7 +165,8 @@ __device__ __forceinline__ T qc_block_first_scale(int N, int tid, T step_length,
 }
 
 // up to `steps` calls of step!() of an instance that is not stuck; returns is_stuck.  The caller's barrier has made X complete.
-template <typename T, typename F> __device__ __forceinline__ bool qc_block_run(int N, int m, int tid, int steps, int64_t max_halvings, QcBlock<T> &w) {
+template <typename T, typename F, typename C = QcFree>
+__device__ __forceinline__ bool qc_block_run(int N, int m, int tid, int steps, int64_t max_halvings, QcBlock<T> &w) {
     const int n3 = 3 * N;
     T *const X = w.X, *const G = w.G, *const D = w.D, *const DX = w.DX, *const DG = w.DG, *const hS = w.hS, *const hY = w.hY;
     double *const rho = w.rho, *const alpha = w.alpha, *const red = w.red;
@@ -174,14 +211,29 @@ template <typename T, typename F> __device__ __forceinline__ bool qc_block_run(i
         T tx[kClPer], ty[kClPer], tz[kClPer];
         for (;;) {
             bool same = true;
-            CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) {
-                const T v = dfma<T>(t, D[c * N + i], DX[c * N + i]);
-                X[c * N + i] = v;
-                same = same && is_equal(v, DX[c * N + i]);
-            })
+            if constexpr (C::kConstrained) {
+                // a thread owns all three components of its particles: it votes on the unprojected values and writes the
+                // projected ones before the one barrier that publishes the trial
+                CL_FOR_OWN(i, {
+                    T v[3];
+                    for (int c = 0; c < 3; ++c) {
+                        v[c] = dfma<T>(t, D[c * N + i], DX[c * N + i]);
+                        same = same && is_equal(v[c], DX[c * N + i]);
+                    }
+                    C::template project<T>(true, v[0], v[1], v[2]);   // :133-135
+                    for (int c = 0; c < 3; ++c) X[c * N + i] = v[c];
+                })
+            } else {
+                CL_FOR_OWN(i, for (int c = 0; c < 3; ++c) {
+                    const T v = dfma<T>(t, D[c * N + i], DX[c * N + i]);
+                    X[c * N + i] = v;
+                    same = same && is_equal(v, DX[c * N + i]);
+                })
+            }
             if (__syncthreads_and(same ? 1 : 0)) { stuck = true; break; }   // :128; the barrier also publishes the trial point
             T Et;
             cl_block_eval<T, F>(N, tid, X, red, par, Et, tx, ty, tz);       // its barrier: every thread has read X
+            if constexpr (C::kConstrained) { CL_FOR_OWN(i, C::template tangent<T>(X[i], X[N + i], X[2 * N + i], tx[q], ty[q], tz[q]);) }
             if (Et < E) { dE = Et - E; E = Et; accepted = true; break; }   // :139-144
             t *= T(0.5);                                                    // :152
             if (++h >= max_halvings) { stuck = true; break; }

@@ -40,7 +40,8 @@ export HipVector, LBFGSOptimizer, BFGSOptimizer, AdGDOptimizer, GradientDescentO
        ElasticBand, interpolate_band!, neb_apply!, neb_plan, connect_minima, NEB_ACTIVE, NEB_CONVERGED, NEB_FAILED,
        assign_particles, align_pairs, ALIGN_TRIAL_IDENTITY, ALIGN_TRIAL_PRINCIPAL, ALIGN_CONVERGED, ALIGN_CYCLE_LIMIT, ALIGN_FAILED,
        band_candidates, PATHWAY_MAX_BATCH, PATHWAY_OVERFLOW,
-       BasinHopping, hop!, set_record!, set_array!
+       BasinHopping, hop!, set_record!, set_array!,
+       SphereLBFGS, sphere_project!, sphere_energy_gradient, DZO_SPHERE_ENERGY_RIESZ1
 
 const libdzo = get(ENV, "DZO_LIB", joinpath(@__DIR__, "..", "libdzo_hip.so"))
 
@@ -455,6 +456,114 @@ function pairwise_batch_energy_gradient!(energies::HipVector{T}, gradients::HipV
     check(ccall((:dzo_pairwise_batch_energy_gradient, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
                 Cint(radial), n_particles, batch, dtype_code(T), points.ptr, energies.ptr, gradients.ptr))
     return energies
+end
+
+################################################################################ the Thomson problem: Riesz energy on the unit sphere
+# (not exercised in the build container either; the Python class SphereLBFGS binds the same entry points and IS tested)
+#
+# The live LBFGSOptimizer WITH its constraint hook (constraint_function!, :133-135 and :412-414) on the reference author's own
+# example objective, riesz_energy / riesz_gradient! / constrain_riesz_gradient_sphere! of legacy/ExampleFunctions.jl (:30-45,
+# :47-83, :361-374), of `batch` configurations of `n_particles` charges at once.  `points` holds instance b as [x | y | z] at
+# 3 n_particles b (the legacy functions take a (3, N) matrix); it is aliased (:393) and projected in place (:412-414).
+
+const DZO_SPHERE_ENERGY_RIESZ1 = 0
+
+"""`sphere_project!(points, n_particles)`: every particle of every instance divided by its norm, in place; blocks."""
+function sphere_project!(points::HipVector{T}, n_particles::Integer) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    check(ccall((:dzo_sphere_batch_project, libdzo), Cint, (Int64, Int64, Cint, Ptr{Cvoid}),
+                n_particles, batch, dtype_code(T), points.ptr))
+    return points
+end
+
+"""`sphere_energy_gradient(energies, gradients, points, n_particles; tangent=true)`: the Riesz (s = 1) energy of every instance and,
+unless `gradients === nothing`, its gradient: raw (`riesz_gradient!`) or, with `tangent`, after
+`constrain_riesz_gradient_sphere!`; by the optimizer's own device routine.  Blocks."""
+function sphere_energy_gradient(energies::HipVector{T}, gradients::Union{Nothing,HipVector{T}}, points::HipVector{T}, n_particles::Integer;
+                                tangent::Bool=true) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    @assert length(energies) == batch
+    @assert gradients === nothing || length(gradients) == length(points)
+    check(ccall((:dzo_sphere_batch_energy_gradient, libdzo), Cint, (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint),
+                Cint(DZO_SPHERE_ENERGY_RIESZ1), n_particles, batch, dtype_code(T), points.ptr, energies.ptr,
+                gradients === nothing ? C_NULL : gradients.ptr, Cint(tangent)))
+    return energies
+end
+
+mutable struct SphereLBFGS{T}
+    handle::Ptr{Cvoid}
+    points::HipVector{T}
+    n_particles::Int
+    batch::Int
+    history_length::Int
+end
+
+"""`SphereLBFGS(points, n_particles, initial_step_length, history_length)` (:400-427 per instance, the unit sphere as constraint)."""
+function SphereLBFGS(points::HipVector{T}, n_particles::Integer, initial_step_length::Real, history_length::Integer) where {T}
+    ensure_init()
+    batch = div(length(points), 3 * n_particles)
+    @assert length(points) == 3 * n_particles * batch
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_sphere_lbfgs_batch_create, libdzo), Cint,
+                (Cint, Int64, Int64, Cint, Ptr{Cvoid}, Cdouble, Cint, Ref{Ptr{Cvoid}}),
+                Cint(DZO_SPHERE_ENERGY_RIESZ1), n_particles, batch, dtype_code(T), points.ptr, Float64(initial_step_length), history_length, h))
+    opt = SphereLBFGS{T}(h[], points, n_particles, batch, history_length)
+    finalizer(opt) do w
+        w.handle != C_NULL && ccall((:dzo_sphere_lbfgs_batch_destroy, libdzo), Cint, (Ptr{Cvoid},), w.handle)
+        w.handle = C_NULL
+    end
+    return opt
+end
+
+function step!(opt::SphereLBFGS, steps::Integer=1; wait::Bool=true)
+    if !wait
+        check(ccall((:dzo_sphere_lbfgs_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), opt.handle, steps, C_NULL))
+        return nothing
+    end
+    flag = Ref{Cint}(0)
+    check(ccall((:dzo_sphere_lbfgs_batch_step, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), opt.handle, steps, flag))
+    return flag[] != 0
+end
+
+set_max_halvings!(opt::SphereLBFGS, v::Integer) =
+    (check(ccall((:dzo_sphere_lbfgs_batch_set_max_halvings, libdzo), Cint, (Ptr{Cvoid}, Int64), opt.handle, v)); opt)
+
+function count_active(opt::SphereLBFGS)
+    n = Ref{Int64}(0)
+    check(ccall((:dzo_sphere_lbfgs_batch_count_active, libdzo), Cint, (Ptr{Cvoid}, Ref{Int64}), opt.handle, n))
+    return Int(n[])
+end
+
+"""current_objective_value of every instance (DZO_LBFGS_BATCH_OBJECTIVES); blocks."""
+function objective_values(opt::SphereLBFGS{T}) where {T}
+    r = Vector{T}(undef, opt.batch)
+    check(ccall((:dzo_sphere_lbfgs_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, 5, r))
+    return r
+end
+
+"""iteration_count of every instance (DZO_LBFGS_BATCH_ITERATION_COUNTS); blocks."""
+function iteration_counts(opt::SphereLBFGS)
+    r = Vector{Int64}(undef, opt.batch)
+    check(ccall((:dzo_sphere_lbfgs_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, 8, r))
+    return r
+end
+
+"""is_stuck of every instance (DZO_LBFGS_BATCH_IS_STUCK): with the gradient, what tells a minimum from a step without descent; blocks."""
+function stuck_flags(opt::SphereLBFGS)
+    r = Vector{Int32}(undef, opt.batch)
+    check(ccall((:dzo_sphere_lbfgs_batch_read, libdzo), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), opt.handle, 7, r))
+    return r .!= 0
+end
+
+"""Device address of one of the DZO_LBFGS_BATCH_* arrays of include/dzo.h (no wait)."""
+function array_pointer(opt::SphereLBFGS, what::Integer)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dzo_sphere_lbfgs_batch_get_ptr, libdzo), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), opt.handle, what, p))
+    return p[]
 end
 
 """`pairwise_batch_hvp!(products, points, directions, n_particles; curvatures=nothing, shared_point=false)`:

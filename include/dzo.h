@@ -402,6 +402,63 @@ int32_t dzo_pairwise_batch_energy_gradient(int32_t radial, int64_t n_particles, 
                                            const void *points_dev, void *energies_dev, void *gradients_dev);
 
 /* ---------------------------------------------------------------------------------------
+ * The Thomson problem: Riesz energy on the unit sphere and the sphere-constrained batched LBFGSOptimizer.  The objective is
+ * the reference author's example of legacy/ExampleFunctions.jl, the Riesz (Coulomb, s = 1) energy of N points:
+ *   riesz_energy                      :30-45     E = sum_{i < j} 1 / |p_i - p_j|
+ *   riesz_gradient!                   :47-83     g_j = sum_{i != j} (p_i - p_j) / |p_i - p_j|^3, i ascending, the self term skipped
+ *   constrain_riesz_gradient_sphere!  :361-374   g_i -= (p_i . g_i) p_i
+ * and the optimizer is the live LBFGSOptimizer (src/DZOptimization.jl:321-509) WITH its constraint hook: the short constructor
+ * projects the initial point (:412-414) and take_backtracking_step! projects every trial point before it is evaluated
+ * (:133-135).  The sibling of dzo_lbfgs_batch_* above, whose constraint_function! is nothing: many random configurations of N
+ * charges, each quenched to a local minimum in one launch.
+ *
+ * Layout.  points_dev is (3N, batch): instance b at element 3N b, [x(0..N) | y | z], the layout of every cluster unit.  (The
+ * legacy functions take a (3, N) matrix; particle i here is column i there.)
+ *
+ * Arithmetic.  Per pair, from r2 = dx^2 + dy^2 + dz^2 summed in that order: r = sqrt(r2), inv_r = 1 / r (IEEE), energy inv_r,
+ * gradient term 2 (-0.5 (inv_r / r2)) (p_i - p_j); inv_r / r2 is the reference's inv_dist_cubed (:62), the scaling by 1/2 and the
+ * doubling are exact, so a term has the bits of the reference's dist * inv_dist_cubed, and a row is summed over j ascending like
+ * :55-80.  E is half the sum over ordered pairs: row sums in T, rows added in fp64 in the fixed trees of dzo_lbfgs_batch_*, one
+ * rounding to T.
+ *   project(x, y, z):  r = sqrt(x^2 + y^2 + z^2) summed in that order, then x / r, y / r, z / r (IEEE divisions).  It always
+ *       reports success; a particle on the origin becomes NaN, its objective NaN, and the trial is rejected (the step backtracks),
+ *       which is what the reference does with a NaN objective.  The reference ships the gradient constraint but NOT the
+ *       projection (constraint_function! is the caller's): per-particle normalisation is ours.
+ *   tangent(p, g):     overlap = x gx + y gy + z gz summed in that order, unfused; g -= overlap p, unfused
+ *       (constrain_riesz_gradient_sphere!, operation for operation).
+ * Inside a trial (:124-139): trial = fma(t, direction, old point); stuck when the UNPROJECTED trial isequal the old point (:128);
+ * project (:133-135); evaluate; make the trial's gradient tangent; accept on strict decrease.  On acceptance delta_point is
+ * projected-new minus old and delta_gradient the difference of tangent gradients.  Everything else -- the constructor's first
+ * direction (:381-387, on the tangent gradient of the projected initial point), the recursion (:430-451), the ring, the launch
+ * shapes, determinism, max_halvings, errors and blocking rules -- is that of dzo_lbfgs_batch_*, with its `what` constants
+ * (DZO_LBFGS_BATCH_*) and limits (DZO_LBFGS_BATCH_MAX_PARTICLES, DZO_LBFGS_BATCH_MAX_HISTORY).
+ * ------------------------------------------------------------------------------------- */
+#define DZO_SPHERE_ENERGY_RIESZ1 0          /* the only `energy` selector; anything else is DZO_ERR_INVALID */
+/* constraint_function! (:133-135, :412-414) of every particle of every instance, in place: project above.  Blocking. */
+int32_t dzo_sphere_batch_project(int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev);
+/* riesz_energy (:30-45) into energies_dev (T, batch) and, unless NULL, riesz_gradient! (:47-83) into gradients_dev (T, 3N batch):
+ * raw when tangent == 0, after constrain_riesz_gradient_sphere! (:361-374) when tangent == 1, by the SAME device routine and
+ * summation order the optimizer uses.  The points are taken as they are (not projected).  Blocking. */
+int32_t dzo_sphere_batch_energy_gradient(int32_t energy, int64_t n_particles, int64_t batch, int32_t dtype, const void *points_dev,
+                                         void *energies_dev, void *gradients_dev, int32_t tangent);
+typedef struct dzo_sphere_lbfgs_batch_s *dzo_sphere_lbfgs_batch_t;
+/* LBFGSOptimizer(constraint_function!, f, g!, initial_point, initial_step_length, history_length) of every instance, :400-427
+ * and :347-397: points_dev is ALIASED (:393) and PROJECTED IN PLACE (:412-414), then f0, the tangent g0, the first direction and
+ * is_stuck = iszero(|g0|) (:381-387).  `energy` sits where dzo_lbfgs_batch_create takes `radial`.  Blocking. */
+int32_t dzo_sphere_lbfgs_batch_create(int32_t energy, int64_t n_particles, int64_t batch, int32_t dtype, void *points_dev,
+                                      double initial_step_length, int32_t history_length, dzo_sphere_lbfgs_batch_t *out);
+int32_t dzo_sphere_lbfgs_batch_destroy(dzo_sphere_lbfgs_batch_t h);
+/* the bound on the halvings of one step (the loop of :121-153 has none); at least 1 */
+int32_t dzo_sphere_lbfgs_batch_set_max_halvings(dzo_sphere_lbfgs_batch_t h, int64_t max_halvings);
+/* `steps` step!() calls (:454-509) of every instance that is not stuck, one launch; all_stuck may be NULL (then no host wait) */
+int32_t dzo_sphere_lbfgs_batch_step(dzo_sphere_lbfgs_batch_t h, int32_t steps, int32_t *all_stuck);
+/* instances with is_stuck == false (:456).  Blocking. */
+int32_t dzo_sphere_lbfgs_batch_count_active(dzo_sphere_lbfgs_batch_t h, int64_t *active);
+/* device address of a DZO_LBFGS_BATCH_* array (no wait) / a blocking copy of it to host memory, in the array's own element type */
+int32_t dzo_sphere_lbfgs_batch_get_ptr(dzo_sphere_lbfgs_batch_t h, int32_t what, void **ptr_dev);
+int32_t dzo_sphere_lbfgs_batch_read(dzo_sphere_lbfgs_batch_t h, int32_t what, void *out_host);
+
+/* ---------------------------------------------------------------------------------------
  * Batched basin hopping over Lennard-Jones clusters (Wales & Doye 1997): Monte Carlo over the QUENCHED landscape, the
  * composition of the tempering move (scripts/MonteCarlo.jl:49-55, applied to every particle), the quench above
  * (src/DZOptimization.jl:321-509) and the Metropolis test (scripts/MonteCarlo.jl:63-70) on the quenched energies.  Each walker
