@@ -2990,6 +2990,7 @@ static void lbfgs_mark_unsettled(dzo_lbfgs_s *o);
 static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
     OptCore &c = o->core;
     DZO_TRY(lbfgs_flush_post(o));                         // (a trial overwrites x: a deferred tail that no Gram pass consumed is formed first)
+    void *const dx_before = c.dx, *const dg_before = c.dg;
     o->refresh_delta_ptrs();                              // deltas move to the spare slots
     o->scalars_ready = false; o->gram_ready = false;      // x, g and the history are about to change
     o->spec_scalars = false;
@@ -2997,7 +2998,12 @@ static int32_t lbfgs_search_and_post(dzo_lbfgs_s *o, int trials_rejected = 0) {
     if (o->line_search == 1) {
         bool accepted = false;
         DZO_TRY(lbfgs_wolfe_search(o, &accepted));
-        if (!accepted) return DZO_OK;
+        if (!accepted) {
+            // a failed Wolfe search writes neither delta: both fields stay the last accepted step's, which on slabs live in
+            // the newest pair, not in the spare slot (a tile ring keeps them in dx_lin / dg_lin either way)
+            c.dx = dx_before; c.dg = dg_before;
+            return DZO_OK;
+        }
         if (safeguards) DZO_TRY(lbfgs_note_step_length(o));
         double r = 0;
         DZO_TRY(lbfgs_aux_dot(o, c.dx, c.dg, &r));                   // :505
@@ -3745,6 +3751,8 @@ static int32_t lbfgs_construct(int64_t n, int32_t history_length, int32_t dtype,
     o->m = history_length;
     o->stride = L.stride;
     o->last_step_length = round_to_dtype(dtype, initial_step_length);   // as legacy BFGS :779
+    o->wolfe_c1 = round_to_dtype(dtype, o->wolfe_c1);     // the defaults are values of the element type, like the ones
+    o->wolfe_c2 = round_to_dtype(dtype, o->wolfe_c2);     // dzo_lbfgs_set_line_search stores: ir == (T)1e-4 passes Armijo
     int32_t rc = core_alloc(c);
     if (rc != DZO_OK) { delete o; return rc; }
     o->blocked = L.blocked; o->nslots = L.nslots; o->pair_stride = L.pair_stride;

@@ -4,44 +4,10 @@ import numpy as np
 import pytest
 
 from dzo_loader import dzo
+from lbfgs_options_twin import _pair, _same_step, _sync, rel
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
-
-
-def _pair(n, m, dtype=np.float64, mode=dzo.TWOLOOP_GRAM):
-    x0 = orc.rosenbrock_chain_x0(n, dtype)
-    ref = orc.LBFGS(orc.Problem(orc.ROSENBROCK_CHAIN, n, dtype), x0.copy(), 1.0, m)
-    prob = dzo.Problem(dzo.ROSENBROCK_CHAIN, n, dtype)
-    opt = dzo.LBFGSOptimizer(None, prob, None, dzo.DeviceArray.from_host(x0), 1.0, m)
-    opt.set_two_loop_mode(mode)
-    return opt, ref, prob
-
-
-def _sync(opt, ref):
-    opt.current_point.upload(ref.current_point)
-    opt.current_gradient.upload(ref.current_gradient)
-    opt.set_objective_value(ref.current_objective_value)
-    S, Y = ref.history_arrays()
-    opt.set_history(S, Y, ref.rho_history, iteration_count=ref.iteration_count)
-    opt.set_last_step_length(ref.last_step_length)
-
-
-def _same_step(opt, ref, tol=1e-10):
-    assert opt.is_stuck == ref.is_stuck and opt.iteration_count == ref.iteration_count
-    assert opt.last_trials == ref.last_trials
-    assert opt.history_count == ref.history_count
-    assert opt.last_step_kind == ref.last_step_kind
-    assert rel(opt.current_point.to_host(), ref.current_point) <= 1e-12
-    assert abs(opt.current_objective_value - ref.current_objective_value) <= 1e-12 * max(abs(ref.current_objective_value), 1e-300)
-    if not ref.is_stuck:
-        assert rel(opt.delta_point.to_host(), ref.delta_point) <= tol
-        assert rel(opt.delta_gradient.to_host(), ref.delta_gradient) <= 1e-9
-        assert np.allclose(opt.rho_history, ref.rho_history, rtol=1e-9)
 
 
 @pytest.mark.parametrize("mode", [dzo.TWOLOOP_CHAIN, dzo.TWOLOOP_GRAM], ids=["chain", "gram"])
